@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W          # N > 1 launches its own N ranks (one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # + the last timed step's outputs as DIR/*.npy
 
 A "step" is one complete optimizer iteration of the reference's trainer._train_step
 (inference/trainer.py:166-206): theta ~ q -> SiT encoder (bf16 autocast) -> fused HIP GRU path
@@ -190,6 +191,53 @@ def timed(fn, steps, warmup, device, distributed):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+# ------------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # all files of one --dump-outputs directory together
+DUMP_SMALL_BYTES = 1 << 20         # arrays up to this size are always written whole
+DUMP_SAMPLE_SEED = 0
+
+
+def step_outputs(result, model, ema):
+    """What one timed step hands its caller, on the host: the ELBO and its components, the gradient norm, and the parameters and
+    EMA shadow the step updated (each flattened in ``named_parameters`` order into one vector)."""
+    c = result.elbo_result.components
+    out = {"elbo": result.elbo_result.evidence_lower_bound, "grad_norm": result.grad_norm}
+    out.update({f"elbo_{f}": getattr(c, f) for f in c.__dataclass_fields__})
+    named = list(model.named_parameters())
+    out["parameters"] = torch.cat([p.detach().reshape(-1).float() for _, p in named])
+    out["ema_parameters"] = torch.cat([ema.shadow[n].detach().reshape(-1).float() for n, _ in named])
+    return {k: v.detach().cpu() for k, v in out.items()}
+
+
+def write_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write ``{name: tensor}`` as ``directory/<name>.npy`` (float64 stays float64, everything else becomes float32), at most
+    ``budget`` bytes in all.  Arrays up to DUMP_SMALL_BYTES are written whole; the larger ones share what is left equally, and one
+    that does not fit its share is replaced by a fixed sample: the sorted element indices drawn without replacement by
+    ``numpy.random.default_rng(DUMP_SAMPLE_SEED)`` from its flattened form, so that two runs pick the same elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    header = 1024   # generous bound on one .npy header
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        host[name] = a.double().numpy() if a.dtype == torch.float64 else a.float().numpy()
+    small = {k: a for k, a in host.items() if a.nbytes <= DUMP_SMALL_BYTES}
+    large = {k: a for k, a in host.items() if k not in small}
+    left = budget - sum(a.nbytes + header for a in small.values()) - header * len(large)
+    if left < 0 or (large and left // len(large) < DUMP_SMALL_BYTES):
+        raise ValueError(f"--dump-outputs: {len(host)} arrays do not fit {budget} bytes")
+    share = left // len(large) if large else 0
+    for name, a in large.items():
+        flat = a.reshape(-1)
+        keep = share // flat.itemsize
+        if flat.size > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.size, size=keep, replace=False))
+            host[name] = flat[idx]
+    for name, a in host.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+    return sorted(host)
 
 
 # ------------------------------------------------------------------------------------------------------ CPU legs
@@ -402,10 +450,11 @@ def encoder_families(step_fn, device, B, N, C, depth, heads, mlp_hidden, mlp_pad
     return out
 
 
-def measure(workload, batch, args, device, distributed, world):
+def measure(workload, batch, args, device, distributed, world, dump_dir=None):
     """Everything the JSON line says about ONE workload on this rank's GPU: the timed full ELBO step (K steps after W warm-up,
     barrier + synchronize on both sides, MAX over ranks), the no-grad sampling calls, HIP-event timings of the head kernels
-    (-> roofline objects) and of the encoder alone (-> mfma_util).  Returns (fields, context for the CPU legs)."""
+    (-> roofline objects) and of the encoder alone (-> mfma_util).  ``dump_dir``: the outputs of the last timed step are written
+    there (step_outputs / write_outputs) before anything else runs.  Returns (fields, context for the CPU legs)."""
     from viforsdes_amd import _hip
     from viforsdes_amd.examples.sdes import lv_problem, ou_problem, synthetic_problem
     from viforsdes_amd.inference.data_parallel import FlatGradientAllReduce
@@ -422,8 +471,10 @@ def measure(workload, batch, args, device, distributed, world):
     tr = build_trainer(problem, batch, device, True, seed=1234, **enc)
     model, ctx = tr.ctx.model, tr.ctx
 
+    last = []   # the latest step's TrainStepResult (--dump-outputs)
+
     def train_step():
-        tr._train_step(model)
+        last[:] = [tr._train_step(model)]
         ctx.ema.update()
 
     # the step may replay from HIP graph(s) (same kernels, same work): a win when the step is launch-bound (OU), a small
@@ -448,7 +499,9 @@ def measure(workload, batch, args, device, distributed, world):
             dist.all_reduce(flag, op=dist.ReduceOp.MIN)
             use = bool(flag.item())
         if use:
-            train_step, graph_mode = replay, True
+            def train_step():
+                last[:] = [replay()]
+            graph_mode = True
         elif replay is not None:  # drop the graph and its private memory pool
             del replay
             tr._graph = None
@@ -459,6 +512,8 @@ def measure(workload, batch, args, device, distributed, world):
                 p.grad = None
 
     elapsed = timed(train_step, args.steps, args.warmup, device, distributed)
+    if dump_dir is not None:
+        write_outputs(dump_dir, step_outputs(last[0], model, ctx.ema))
     iters_per_sec = args.steps / elapsed
     global_batch = batch * world
 
@@ -800,7 +855,12 @@ def main():
                     "rocprofv3 --pmc passes (child processes, ~30 s) before the timed region")
     ap.add_argument("--detail-out", default=None, help="also write the FULL record (every field; the stdout line is the compact "
                     "headline, the full record always goes to stderr behind 'BENCH_DETAIL ') to this file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(ELBO and its components, gradient norm, updated parameters and EMA shadow) as DIR/<name>.npy, at most 64 MB "
+                    "(rank 0, headline workload)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", 1))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -825,7 +885,8 @@ def main():
 
     default_batch = {"lv": 512, "ou": 128, "synthetic": 256}
     batch = args.batch or default_batch[args.workload]
-    fields, (problem, enc) = measure(args.workload, batch, args, device, distributed, world)
+    fields, (problem, enc) = measure(args.workload, batch, args, device, distributed, world,
+                                     dump_dir=args.dump_outputs if rank == 0 else None)
     out = {
         "metric": "sampled-paths/sec + ELBO-iters/sec (full ELBO gradient step; value = global_batch * ELBO-iters/s)",
         "value": fields.pop("value"), "unit": fields.pop("unit"), "n_gpus": world, "steps": args.steps,

@@ -130,7 +130,9 @@ def test_theta_densities_and_state_space_vs_golden(name):
     xt = torch.from_numpy(d["x"])[:, :-1].reshape(B * T, S)
     th = torch.from_numpy(d["theta"]).unsqueeze(1).expand(B, T, P).reshape(B * T, P)
     assert rel_err(sde.drift(xt, th).reshape(B, T, S).numpy(), d["drift"]) < 1e-6
-    assert rel_err(sde.diffusion(xt, th).reshape(B, T, S, S).numpy(), d["diffusion"]) < 1e-6
+    # the diffusion in float64 on the same inputs: the LV Cholesky factor's l11 cancels (t3 v + uv - l10^2), so an fp32 evaluation
+    # already sits 9e-7 from the exact value and a 1-ulp difference in the host's fp32 sqrt moves it past 1e-6 of the reference
+    assert rel_err(sde.diffusion(xt.double(), th.double()).reshape(B, T, S, S).numpy(), d["diffusion"]) < 1e-6
 
 
 def test_encoder_matches_reference_forward_and_gradients():
