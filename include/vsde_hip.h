@@ -429,6 +429,24 @@ int vsde_elbo_tail_bwd(int B, int K, int S, int O, int P, const float *x_obs, co
                        const float *g_out6, float *g_x_obs, float *g_theta, float *g_post_mean, float *g_post_log_std,
                        float *g_sde, float *g_gen, float *g_jac, void *stream);
 
+/* Importance log-weights of posterior draws (VariationalPosterior.log_evidence): per sample b the ELBO integrand
+ *   log_w[b] = obs + sum_t (sde_t - gen_t + jac_t) + prior - post
+ * of vsde_elbo_path_terms + vsde_elbo_tail_fwd before their batch means, in one pass.  z[B][T+1][S] latent paths (softplus on
+ * the positive state dims: state_positive_mask_host, S bytes), means[B][T][S], chol[B][T][S][S] of the generating head,
+ * theta[B][P]; the observation states are read from z at the grid rows obs_rows[K] (device int32).  kind 1..3: drift /
+ * diffusion of the built-in SDE (VSDE_SDE_*) evaluated in registers (drift / diffusion may be NULL); kind 0: the caller's
+ * drift[B][T][S], diffusion[B][T][S][S].  Other arguments as vsde_elbo_tail_fwd.  S, O, P <= 16 (S beyond: VSDE_E_STATE). */
+int vsde_log_weights(int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol,
+                     const float *drift, const float *diffusion, const float *theta, const int *obs_rows, const float *obs_values,
+                     const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std,
+                     const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host,
+                     const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
+/* Merge the first n entries of log_w into the running fp64 state (device memory, 6 doubles; start from
+ * [-inf, 0, 0, 0, 0, 0]):  [M, sum exp(lw - M), sum exp(2 (lw - M)), sum lw, n, n_nonfinite], M the running max.  One
+ * single-workgroup launch per chunk, no host synchronisation, bitwise deterministic.  NaN / +inf entries count in n_nonfinite
+ * and n only; -inf entries are zero weights. */
+int vsde_log_weight_accumulate(int n, const float *log_w, double *state6, void *stream);
+
 /* Drift and diffusion factor of a built-in SDE on every grid point of a batch of paths -- what the ELBO evaluates through the
  * user's Python callables on the flattened [(B T), S] states (inference/evidence_lower_bound.py:37-40) -- and the
  * vector-Jacobian product its backward needs.  x[B][T+1][S] (rows 0..T-1 are read), theta[B][P] -> drift[B][T][S],

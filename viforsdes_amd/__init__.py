@@ -15,9 +15,10 @@ from .core.observations import GaussianObservationLikelihood, ObservationLikelih
 from .core.priors import Prior, PriorType
 from .core.sde import SDE, FunctionalSDE, make_sde
 from .infer import InferenceConfig, infer
-from .posterior.variational_posterior import VariationalPosterior
+from .posterior.variational_posterior import EvidenceEstimate, VariationalPosterior
 
 __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "TrainingConfig", "YamlConfig",
            "GaussianObservationLikelihood", "ObservationLikelihood", "Observations", "Prior", "PriorType", "SDE",
-           "FunctionalSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior"]
+           "FunctionalSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior",
+           "EvidenceEstimate"]
 __version__ = "0.1.0"

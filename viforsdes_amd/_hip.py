@@ -52,6 +52,7 @@ EXPORTS = (
     "vsde_head_forward_workspace_bytes", "vsde_head_forward",
     "vsde_head_backward_workspace_bytes", "vsde_head_backward",
     "vsde_elbo_path_terms", "vsde_elbo_path_terms_bwd", "vsde_elbo_tail_fwd", "vsde_elbo_tail_bwd",
+    "vsde_log_weights", "vsde_log_weight_accumulate",
     "vsde_profile_enable", "vsde_profile_elapsed_ms", "vsde_debug_force_v1", "vsde_debug_head_mp", "vsde_head_mfma_range_exceeded",
     "vsde_ln_modulate_fwd", "vsde_ln_modulate_bwd", "vsde_gated_residual_fwd", "vsde_gated_residual_bwd",
     "vsde_swiglu_fwd", "vsde_swiglu_bwd", "vsde_gate_merge_fwd", "vsde_gate_merge_bwd",
@@ -371,6 +372,58 @@ def elbo_tail_bwd(x_obs, obs_values, obs_matrix, variance: float, theta, prior_t
               _ptr(g_out), _ptr(g_x), _ptr(g_theta), _ptr(g_mean), _ptr(g_ls), _ptr(g_paths[0]), _ptr(g_paths[1]), _ptr(g_paths[2]),
               _stream(dev))
     return g_x, g_theta, g_mean, g_ls, g_paths[0], g_paths[1], g_paths[2]
+
+
+def log_weights(kind: str | None, z, means, chol, drift, diffusion, theta, obs_rows, obs_values, obs_matrix, variance: float,
+                prior_type: int, prior_mean: float, prior_std: float, post_mean, post_log_std, state_positive_dims,
+                theta_positive_dims, time_step: float):
+    """Per-sample importance log-weights [B] (see include/vsde_hip.h: vsde_log_weights).  ``kind`` in SDE_KINDS evaluates the
+    built-in drift / diffusion in the kernel (``drift`` / ``diffusion`` None); ``kind`` None reads the given tensors."""
+    lib = load()
+    dev = _require_hip(z, means, chol, drift, diffusion, theta, obs_rows, obs_values, post_mean, post_log_std)
+    z, means, chol, theta, obs_values, post_mean, post_log_std = (
+        _f32c(t) for t in (z, means, chol, theta, obs_values, post_mean, post_log_std))
+    drift, diffusion, obs_matrix = (None if t is None else _f32c(t) for t in (drift, diffusion, obs_matrix))
+    obs_rows = obs_rows.to(torch.int32).contiguous()
+    B, T1, S = z.shape
+    K, O, P = obs_rows.shape[0], obs_values.shape[1], theta.shape[1]
+    if tuple(means.shape) != (B, T1 - 1, S) or tuple(chol.shape) != (B, T1 - 1, S, S) or theta.shape[0] != B \
+            or obs_values.shape[0] != K or post_mean.numel() != P or post_log_std.numel() != P \
+            or (obs_matrix is not None and tuple(obs_matrix.shape) != (O, S)) or (obs_matrix is None and O != S):
+        raise ValueError("log_weights: inconsistent shapes")
+    if kind is None and (drift is None or tuple(drift.shape) != (B, T1 - 1, S) or tuple(diffusion.shape) != (B, T1 - 1, S, S)):
+        raise ValueError("log_weights: drift [B, T, S] and diffusion [B, T, S, S] are required without a built-in kind")
+    with torch.cuda.device(dev):
+        out = torch.empty(B, device=dev, dtype=torch.float32)
+        _call(lib.vsde_log_weights, ctypes.c_int(0 if kind is None else SDE_KINDS[kind]), ctypes.c_int(B), ctypes.c_int(T1 - 1),
+              ctypes.c_int(S), ctypes.c_int(K), ctypes.c_int(O), ctypes.c_int(P), _ptr(z), _ptr(means), _ptr(chol), _ptr(drift),
+              _ptr(diffusion), _ptr(theta), _ptr(obs_rows), _ptr(obs_values), _ptr(obs_matrix), ctypes.c_double(variance),
+              ctypes.c_int(prior_type), ctypes.c_double(prior_mean), ctypes.c_double(prior_std), _ptr(post_mean),
+              _ptr(post_log_std), _mask_bytes(state_positive_dims, S), _mask_bytes(theta_positive_dims, P),
+              ctypes.c_double(time_step), _ptr(out), _stream(dev))
+    return out
+
+
+def log_weight_state(device) -> torch.Tensor:
+    """A fresh accumulator state for ``log_weight_accumulate``: fp64 [M, S1, S2, sum lw, n, n_nonfinite] = [-inf, 0, ...] on
+    ``device`` (a HIP device: the accumulator has no CPU implementation)."""
+    state = torch.zeros(6, device=device, dtype=torch.float64)
+    _require_hip(state)
+    state[0] = float("-inf")
+    return state
+
+
+def log_weight_accumulate(log_w, n: int, state) -> None:
+    """Merge the first ``n`` entries of ``log_w`` [>= n] into ``state`` in place, in stream order (no host synchronisation)."""
+    lib = load()
+    dev = _require_hip(log_w, state)
+    log_w = _f32c(log_w)
+    if log_w.ndim != 1 or not 0 < n <= log_w.shape[0]:
+        raise ValueError(f"log_weight_accumulate: need 0 < n <= {log_w.shape[0] if log_w.ndim == 1 else '?'} (got {n})")
+    if state.dtype != torch.float64 or tuple(state.shape) != (6,) or not state.is_contiguous():
+        raise ValueError("log_weight_accumulate: state must be a contiguous float64 [6] tensor")
+    with torch.cuda.device(dev):
+        _call(lib.vsde_log_weight_accumulate, ctypes.c_int(n), _ptr(log_w), _ptr(state), _stream(dev))
 
 
 def sde_coefficients_fwd(kind: str, x, theta):

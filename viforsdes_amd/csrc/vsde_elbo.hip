@@ -4,7 +4,7 @@
 // B*T tiny matrices plus ~10 elementwise torch kernels of the reference
 // (src/variational_sde/inference/evidence_lower_bound.py:42-50,77-83; inference/types.py:23-24;
 // inference/state_space.py:35-38).  HBM-bound streaming kernels: every tensor is read once.
-#include "vsde_common.h"
+#include "vsde_sde_coef.h"
 
 namespace vsde {
 
@@ -219,20 +219,26 @@ template <int N> __device__ __forceinline__ void tail_block_sum(float (*red)[N],
     __syncthreads();
 }
 
-// observation term of path b; when GX, also d obs_lp / d x_obs scaled by w
-template <bool GX> __device__ __forceinline__ float tail_obs(const TailParams &p, int b, float w) {
+// the states of path b at its observed grid points, read from x_obs [B][K][S]
+struct XObsRows {
+    const TailParams &p;
+    int b;
+    __device__ float operator()(int k, int i) const { return p.x_obs[((int64_t)b * p.K + k) * p.S + i]; }
+};
+
+// observation term of path b, its state at observation k read as x(k, i); when GX, also d obs_lp / d x_obs scaled by w
+template <bool GX, class X> __device__ __forceinline__ float tail_obs(const TailParams &p, int b, float w, const X &x) {
     float lp = 0.f;
     for (int k = 0; k < p.K; ++k) {
-        const float *x = p.x_obs + ((int64_t)b * p.K + k) * p.S;
         float *gx = GX ? p.g_x_obs + ((int64_t)b * p.K + k) * p.S : nullptr;
         if (GX) for (int i = 0; i < p.S; ++i) gx[i] = 0.f;
         for (int o = 0; o < p.O; ++o) {
             float pred;
             if (p.obs_matrix) {
                 pred = 0.f;
-                for (int i = 0; i < p.S; ++i) pred += p.obs_matrix[o * p.S + i] * x[i];
+                for (int i = 0; i < p.S; ++i) pred += p.obs_matrix[o * p.S + i] * x(k, i);
             } else {
-                pred = x[o];
+                pred = x(k, o);
             }
             const float r = p.obs_values[k * p.O + o] - pred;
             lp += -0.5f * r * r * p.inv_var + p.log_norm;
@@ -246,23 +252,35 @@ template <bool GX> __device__ __forceinline__ float tail_obs(const TailParams &p
     return lp;
 }
 
+// per-sample tail of path b: observation log-density, log prior and log posterior of theta_b (the ELBO tail and the importance
+// log-weight kernel evaluate exactly this)
+struct TailTerms { float obs, prior, post; };
+
+template <class X> __device__ __forceinline__ TailTerms tail_terms(const TailParams &p, int b, const X &x) {
+    TailTerms r;
+    r.obs = tail_obs<false>(p, b, 0.f, x);
+    float prior = 0.f, post = 0.f;
+    for (int i = 0; i < p.P; ++i) {
+        const float th = p.theta[(int64_t)b * p.P + i];
+        const bool pos = (p.theta_pos >> i) & 1u;
+        const float lg = (pos || p.prior_lognormal) ? logf(th) : 0.f;
+        const float zp = ((p.prior_lognormal ? lg : th) - p.prior_mean) * p.prior_inv_std;
+        prior += -0.5f * zp * zp + p.prior_const - (p.prior_lognormal ? lg : 0.f);
+        const float ls = p.post_log_std[i];
+        const float zq = ((pos ? lg : th) - p.post_mean[i]) * expf(-ls);
+        post += -0.5f * zq * zq - ls - 0.5f * kLog2Pi - (pos ? lg : 0.f);
+    }
+    r.prior = prior; r.post = post;
+    return r;
+}
+
 __global__ void __launch_bounds__(256) elbo_tail_fwd_kernel(TailParams p) {
     __shared__ float red[256][6];
     const int tid = threadIdx.x;
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int b = tid; b < p.B; b += 256) {
-        const float obs = tail_obs<false>(p, b, 0.f);
-        float prior = 0.f, post = 0.f;
-        for (int i = 0; i < p.P; ++i) {
-            const float th = p.theta[(int64_t)b * p.P + i];
-            const bool pos = (p.theta_pos >> i) & 1u;
-            const float lg = (pos || p.prior_lognormal) ? logf(th) : 0.f;
-            const float zp = ((p.prior_lognormal ? lg : th) - p.prior_mean) * p.prior_inv_std;
-            prior += -0.5f * zp * zp + p.prior_const - (p.prior_lognormal ? lg : 0.f);
-            const float ls = p.post_log_std[i];
-            const float zq = ((pos ? lg : th) - p.post_mean[i]) * expf(-ls);
-            post += -0.5f * zq * zq - ls - 0.5f * kLog2Pi - (pos ? lg : 0.f);
-        }
+        const TailTerms tt = tail_terms(p, b, XObsRows{p, b});
+        const float obs = tt.obs, prior = tt.prior, post = tt.post;
         const float s = p.sde_lp[b], g = p.gen_lp[b];
         acc[0] += obs + s - g + p.jac[b] + prior - post;
         acc[1] += obs; acc[2] += s; acc[3] += g; acc[4] += prior; acc[5] += post;
@@ -281,7 +299,7 @@ __global__ void __launch_bounds__(256) elbo_tail_bwd_kernel(TailParams p) {
 #pragma unroll
     for (int i = 0; i < 2 * kTailMaxDim; ++i) gq[i] = 0.f;
     for (int b = tid; b < p.B; b += 256) {
-        tail_obs<true>(p, b, w_obs);
+        tail_obs<true>(p, b, w_obs, XObsRows{p, b});
         p.g_sde[b] = w_sde; p.g_gen[b] = w_gen; p.g_jac[b] = w_jac;
 #pragma unroll
         for (int i = 0; i < kTailMaxDim; ++i) {
@@ -324,6 +342,165 @@ static int tail_fill(TailParams &p, int B, int K, int S, int O, int P, const flo
     p.post_mean = post_mean; p.post_log_std = post_log_std; p.theta_pos = mask_bits(theta_positive_mask_host, P);
     p.sde_lp = sde_lp; p.gen_lp = gen_lp; p.jac = jac;
     return 0;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Importance log-weights of posterior draws (VariationalPosterior.log_evidence): the ELBO integrand of one sample,
+//   log w_b = obs_b + sum_t (sde_t - gen_t + jac_t) + prior_b - post_b,
+// in one pass over the path.  One workgroup per path, threads striding over t as in elbo_path_terms_kernel; x = softplus(z) on
+// the positive state dims and, for the built-in kinds 1..3, drift / diffusion are evaluated in registers (the [B,T,S] /
+// [B,T,S,S] coefficient tensors are never written); kind 0 reads the drift / diffusion the caller evaluated.  Each step's
+// three terms are summed before the sum over t (no cancellation of two large sums); the sum over t is a fixed tree, and thread
+// 0 adds the observation / prior / posterior terms through tail_terms, the per-sample body of the ELBO tail.
+struct LogWeightParams {
+    TailParams tail;           // observation / prior / posterior (x_obs unused: the states come from z at obs_rows)
+    int T;
+    const float *z, *means, *chol, *drift, *diffusion;
+    const int *obs_rows;       // [K] grid rows of the observations
+    uint32_t state_pos;
+    float dt, sqdt;
+    float *log_w;              // [B]
+};
+
+// the state of path b at its observed grid points: softplus(z) on the positive dims
+template <int S> struct XObsLatent {
+    const LogWeightParams &p;
+    int b;
+    __device__ float operator()(int k, int i) const {
+        const int r = min(max(p.obs_rows[k], 0), p.T);
+        const float v = p.z[((int64_t)b * (p.T + 1) + r) * S + i];
+        return ((p.state_pos >> i) & 1u) ? softplus_f(v) : v;
+    }
+};
+
+template <int KIND, int S>
+__global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p) {
+    constexpr int PK = KIND == 3 ? 2 * S : 3;
+    const int b = blockIdx.x;
+    float th[PK];
+#pragma unroll
+    for (int i = 0; i < PK; ++i) th[i] = KIND == 0 ? 0.f : p.tail.theta[(int64_t)b * p.tail.P + i];
+    float acc = 0.f;
+    for (int t = threadIdx.x; t < p.T; t += blockDim.x) {
+        const int64_t o1 = ((int64_t)b * (p.T + 1) + t) * S, o2 = ((int64_t)b * p.T + t) * S;
+        float z0[S], z1[S], x0[S], x1[S], w[S];
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+            z0[i] = p.z[o1 + i]; z1[i] = p.z[o1 + S + i];
+            const bool pos = (p.state_pos >> i) & 1u;
+            x0[i] = pos ? softplus_f(z0[i]) : z0[i];
+            x1[i] = pos ? softplus_f(z1[i]) : z1[i];
+        }
+        float sde;
+        if constexpr (KIND == 0) {
+            sde = tri_logpdf<S>(x1, x0, p.drift + o2, p.diffusion + o2 * S, p.dt, p.sqdt, w);
+        } else if constexpr (KIND == 3) {   // f = -a x, G = diag(softplus(b) + 1e-3): the triangular solve is elementwise
+            float quad = 0.f, logdet = 0.f;
+#pragma unroll
+            for (int i = 0; i < S; ++i) {
+                const float dii = (softplus_f(th[S + i]) + 1e-3f) * p.sqdt;
+                const float wi = (x1[i] - (x0[i] + (-th[i] * x0[i]) * p.dt)) / dii;
+                quad += wi * wi;
+                logdet += __logf(dii);
+            }
+            sde = -0.5f * ((float)S * kLog2Pi + quad) - logdet;
+        } else {
+            float f[S], G[S * S];
+            coef_fwd<KIND>(x0, th, f, G);
+            sde = tri_logpdf<S>(x1, x0, f, G, p.dt, p.sqdt, w);
+        }
+        const float gen = tri_logpdf<S>(z1, z0, p.means + o2, p.chol + o2 * S, p.dt, p.sqdt, w);
+        float jac = 0.f;
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+            if ((p.state_pos >> i) & 1u) jac += log_sigmoid(z1[i]);
+        acc += sde - gen + jac;
+    }
+    __shared__ float red[4];
+    acc = wave_sum(acc);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float path = 0.f;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) path += red[i];
+        const TailTerms tt = tail_terms(p.tail, b, XObsLatent<S>{p, b});
+        p.log_w[b] = tt.obs + path + tt.prior - tt.post;
+    }
+}
+
+template <int KIND, int S> static int launch_log_weights(const LogWeightParams &p, hipStream_t s) {
+    hipLaunchKernelGGL((log_weight_kernel<KIND, S>), dim3(p.tail.B), dim3(256), 0, s, p);
+    VSDE_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// kinds 0 (caller's coefficients) and 3 (linear-diagonal) at any S in 1..16
+template <int KIND, int S = 1> static int dispatch_log_weights(int s_dim, const LogWeightParams &p, hipStream_t s) {
+    if (s_dim == S) return launch_log_weights<KIND, S>(p, s);
+    if constexpr (S < kTailMaxDim) {
+        return dispatch_log_weights<KIND, S + 1>(s_dim, p, s);
+    } else {
+        set_error("state_dim %d not supported by the log-weight kernel (1..%d)", s_dim, kTailMaxDim);
+        return VSDE_E_STATE;
+    }
+}
+
+// Streamed reduction of log-weights into a running fp64 state
+//   state = [M, sum exp(lw - M), sum exp(2 (lw - M)), sum lw, n, n_nonfinite]
+// One workgroup per chunk: chunk max, then the chunk sums against it (thread-strided, then a fixed LDS tree: the same draws give
+// the same bits), merged into the state by rescaling both sides to the new max.  NaN and +inf weights are counted in n_nonfinite
+// and left out of the sums; -inf weights are zero weights and count in n only.
+__device__ __forceinline__ bool lw_finite(float v) { return v == v && v != INFINITY; }
+
+__global__ void __launch_bounds__(256) log_weight_accumulate_kernel(int n, const float *__restrict__ lw, double *__restrict__ st) {
+    __shared__ double red[256][4];
+    const int tid = threadIdx.x;
+    float m = -INFINITY;
+    double bad = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        const float v = lw[i];
+        if (lw_finite(v)) m = fmaxf(m, v);
+        else bad += 1.0;
+    }
+    red[tid][0] = m; red[tid][1] = bad;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) { red[tid][0] = fmax(red[tid][0], red[tid + w][0]); red[tid][1] += red[tid + w][1]; }
+        __syncthreads();
+    }
+    const double mc = red[0][0], nbad = red[0][1];
+    __syncthreads();
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int i = tid; i < n; i += 256) {
+        const float x = lw[i];
+        if (!lw_finite(x)) continue;
+        if (mc > -INFINITY) {
+            const double e = exp((double)x - mc);
+            v[0] += e; v[1] += e * e;
+        }
+        v[2] += (double)x;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) red[tid][j] = v[j];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) red[tid][j] += red[tid + w][j];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double m0 = st[0], mn = fmax(m0, mc);
+        const double a = mn > -INFINITY ? exp(m0 - mn) : 0.0, c = mn > -INFINITY ? exp(mc - mn) : 0.0;
+        st[0] = mn;
+        st[1] = st[1] * a + red[0][0] * c;
+        st[2] = st[2] * (a * a) + red[0][1] * (c * c);
+        st[3] += red[0][2];
+        st[4] += (double)n;
+        st[5] += nbad;
+    }
 }
 
 }  // namespace vsde
@@ -391,6 +568,46 @@ extern "C" int vsde_elbo_tail_bwd(int B, int K, int S, int O, int P, const float
     p.g_out = g_out6; p.g_x_obs = g_x_obs; p.g_theta = g_theta; p.g_post_mean = g_post_mean; p.g_post_log_std = g_post_log_std;
     p.g_sde = g_sde; p.g_gen = g_gen; p.g_jac = g_jac;
     hipLaunchKernelGGL(elbo_tail_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
+    VSDE_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+
+extern "C" int vsde_log_weights(int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means,
+                                const float *chol, const float *drift, const float *diffusion, const float *theta,
+                                const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                                int prior_type, double prior_mean, double prior_std, const float *post_mean,
+                                const float *post_log_std, const uint8_t *state_positive_mask_host,
+                                const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+    VSDE_CHECK_ARG(B > 0 && T > 0 && S > 0 && K >= 0, VSDE_E_BADARG, "bad log-weight dims B=%d T=%d S=%d K=%d", B, T, S, K);
+    VSDE_CHECK_ARG(S <= kTailMaxDim, VSDE_E_STATE, "state_dim %d not supported by the log-weight kernel (1..%d)", S, kTailMaxDim);
+    VSDE_CHECK_ARG(kind >= 0 && kind <= 3, VSDE_E_BADARG, "unknown SDE kind %d (0 = caller's coefficients, 1..3 built in)", kind);
+    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim");
+    VSDE_CHECK_ARG(kind != 0 || (drift && diffusion), VSDE_E_BADARG, "kind 0 needs the drift and diffusion tensors");
+    VSDE_CHECK_ARG(z && means && chol && log_w && (K == 0 || obs_rows) && time_step > 0, VSDE_E_BADARG,
+                   "NULL argument / bad time_step");
+    LogWeightParams p = {};
+    // the tail's x_obs and path-term inputs are not read here (the states come from z): any non-NULL pointer passes its check
+    int rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
+                       post_mean, post_log_std, theta_positive_mask_host, z, z, z);
+    if (rc) return rc;
+    p.T = T; p.z = z; p.means = means; p.chol = chol; p.drift = drift; p.diffusion = diffusion; p.obs_rows = obs_rows;
+    p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
+    hipStream_t s = (hipStream_t)stream;
+    switch (kind) {
+        case 1: return launch_log_weights<1, 1>(p, s);
+        case 2: return launch_log_weights<2, 2>(p, s);
+        case 3: return dispatch_log_weights<3>(S, p, s);
+        default: return dispatch_log_weights<0>(S, p, s);
+    }
+}
+
+extern "C" int vsde_log_weight_accumulate(int n, const float *log_w, double *state6, void *stream) {
+    VSDE_CHECK_ARG(n > 0, VSDE_E_BADARG, "log-weight count must be positive (got %d)", n);
+    VSDE_CHECK_ARG(log_w && state6, VSDE_E_BADARG, "NULL argument");
+    hipLaunchKernelGGL(log_weight_accumulate_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n, log_w, state6);
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -9,16 +9,12 @@
 // contiguous over time, so the 64 paths of a workgroup move CH steps at a time through LDS as coalesced row segments.
 // The backward is what torch autograd computes for trainer.py:208-259 (pre-training differentiates the simulation with
 // respect to theta): reverse recursion over the saved trajectory, a clamped entry (== 1e-6) passes no gradient.
-#include "vsde_common.h"
+#include "vsde_sde_coef.h"
 
 namespace vsde {
 
 constexpr int kEmPaths = 64;   // paths per workgroup (one wavefront)
 constexpr int kEmChunk = 32;   // time steps staged per LDS round
-constexpr float kEmFloor = 1e-6f;
-// clamp(min = 1e-6) that propagates NaN like torch.clamp / torch.maximum do (fmaxf(NaN, floor) would return the floor and hide a
-// diverged path from the non-finite-loss guards of the pre-training loop and the ELBO)
-__device__ __forceinline__ float floor_nan(float y) { return y < kEmFloor ? kEmFloor : y; }
 
 struct EmParams {
     int B, T, S, P;
@@ -27,10 +23,6 @@ struct EmParams {
     uint32_t pos_mask;
     float dt, sqdt;
 };
-
-template <int KIND> struct EmDims { static constexpr int S = KIND == 2 ? 2 : 1; static constexpr int P = KIND == 3 ? 2 : 3; };
-
-__device__ __forceinline__ float softplus_f(float b) { return b > 20.f ? b : log1pf(__expf(b)); }
 
 // y = x + f dt + (G eps) sqrt(dt)
 template <int KIND>
@@ -226,19 +218,7 @@ struct CoefParams {
     float *drift, *diff, *g_x, *g_theta;
 };
 
-template <int KIND> __device__ __forceinline__ void coef_fwd(const float *x, const float *th, float *f, float *G) {
-    if constexpr (KIND == 1) {
-        f[0] = th[0] * (th[1] - x[0]); G[0] = th[2];
-    } else {
-        const float u = x[0], v = x[1], uv = th[1] * u * v;
-        const float l00 = sqrtf(floor_nan(th[0] * u + uv));
-        const float l10 = -uv / floor_nan(l00);
-        const float l11 = sqrtf(floor_nan(th[2] * v + uv - l10 * l10));
-        f[0] = th[0] * u - uv; f[1] = uv - th[2] * v;
-        G[0] = l00; G[1] = 0.f; G[2] = l10; G[3] = l11;
-    }
-}
-
+// coef_fwd<KIND> (vsde_sde_coef.h) and its vector-Jacobian product
 template <int KIND>
 __device__ __forceinline__ void coef_bwd(const float *x, const float *th, const float *gf, const float *gG, float *gx, float *gth) {
     if constexpr (KIND == 1) {

@@ -138,6 +138,19 @@ def path_log_terms(sample: DiffusionPathSample, drift: Tensor, diffusion: Tensor
                             diffusion, sample.state_space.positive_dims, time_step)
 
 
+def tail_log_terms(observations: Observations, observation_likelihood: ObservationLikelihood, prior: Prior,
+                   sde_parameter_posterior: SDEParameterPosterior, x: Tensor, sde_parameters: Tensor, obs_idx: Tensor
+                   ) -> tuple[Tensor, Tensor, Tensor]:
+    """Per-sample ``(observation_log_prob, prior_log_prob, posterior_log_prob)``, each ``[B]``, through the objects' own
+    ``log_prob`` (any likelihood / prior / posterior; the closed forms of the package also have the fused tail kernel)."""
+    B = x.shape[0]
+    obs_lp = observation_likelihood.log_prob(observations.values.unsqueeze(0).expand(B, -1, -1), x[:, obs_idx]).sum(dim=-1)
+    prior_lp = prior.log_prob(sde_parameters)
+    if prior_lp.ndim > 1:
+        prior_lp = prior_lp.sum(dim=-1)
+    return obs_lp, prior_lp, sde_parameter_posterior.log_prob(sde_parameters)
+
+
 def compute_evidence_lower_bound(sde: SDE, observations: Observations, observation_likelihood: ObservationLikelihood,
                                  prior: Prior, sde_parameter_posterior: SDEParameterPosterior, sde_parameters: Tensor,
                                  sample: DiffusionPathSample, time_step: float) -> EvidenceLowerBoundResult:
@@ -159,11 +172,8 @@ def compute_evidence_lower_bound(sde: SDE, observations: Observations, observati
             components=EvidenceLowerBoundComponents(
                 observation_log_prob=out[1], sde_log_prob=out[2], generative_log_prob=out[3], prior_log_prob=out[4],
                 posterior_log_prob=out[5]))
-    obs_lp = observation_likelihood.log_prob(observations.values.unsqueeze(0).expand(B, -1, -1), x[:, obs_idx]).sum(dim=-1)
-    prior_lp = prior.log_prob(sde_parameters)
-    if prior_lp.ndim > 1:
-        prior_lp = prior_lp.sum(dim=-1)
-    post_lp = sde_parameter_posterior.log_prob(sde_parameters)
+    obs_lp, prior_lp, post_lp = tail_log_terms(observations, observation_likelihood, prior, sde_parameter_posterior, x,
+                                               sde_parameters, obs_idx)
 
     elbo = obs_lp + sde_lp - gen_lp + jac + prior_lp - post_lp
     return EvidenceLowerBoundResult(

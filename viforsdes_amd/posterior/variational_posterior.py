@@ -6,6 +6,7 @@ the EMA weights, summaries, diagnostics and the on-disk checkpoint
 which is byte-compatible with the reference's ``torch.save`` layout (same keys, same tensors)."""
 from __future__ import annotations
 
+import math
 import os
 
 from dataclasses import dataclass
@@ -16,8 +17,9 @@ import torch
 from pydantic import BaseModel, ConfigDict
 from torch import Tensor
 
-from ..core.observations import Observations
+from ..core.observations import ObservationLikelihood, Observations
 from ..core.priors import Prior
+from ..core.sde import SDE
 from ..inference import diffusion_path_sampler as _sampler
 from ..inference.diffusion_path_sampler import CapturedPathSampler, sample_diffusion_paths
 from ..inference.exponential_moving_average import ExponentialMovingAverage
@@ -56,6 +58,41 @@ class InferenceDiagnostics:
     evidence_lower_bound_history: list[float]
     final_evidence_lower_bound: float
     n_iterations: int
+
+
+@dataclass(frozen=True)
+class EvidenceEstimate:
+    """Importance-sampled estimate of the log evidence ``log p(y)`` of the Euler-Maruyama-discretised model (start state = first
+    observation), from ``n_samples`` posterior draws with log-weights ``log w`` (``VariationalPosterior.log_evidence``):
+
+    * ``log_evidence = logsumexp(log w) - log n``;
+    * ``effective_sample_size = (sum w)^2 / sum w^2`` in ``[0, n]``;
+    * ``standard_error = sqrt(1 / ESS - 1 / n)``: delta-method standard error of ``log_evidence``;
+    * ``evidence_lower_bound = mean(log w)`` on the same draws (``<= log_evidence``);
+    * ``n_nonfinite``: NaN (or +inf) log-weights; if any, every estimate above is NaN.  ``-inf`` weights are zero weights.
+    ``log_weights``: the ``[n]`` log-weights when asked for, else None."""
+    log_evidence: float
+    standard_error: float
+    effective_sample_size: float
+    evidence_lower_bound: float
+    n_samples: int
+    n_nonfinite: int
+    log_weights: Optional[Tensor] = None
+
+    @classmethod
+    def from_state(cls, state, log_weights: Optional[Tensor] = None) -> "EvidenceEstimate":
+        """Finalise the accumulator state ``[M, sum exp(lw - M), sum exp(2 (lw - M)), sum lw, n, n_nonfinite]`` (float64,
+        ``_hip.log_weight_accumulate``)."""
+        m, s1, s2, sum_lw, n, bad = (float(v) for v in state)
+        n_i, bad_i = int(round(n)), int(round(bad))
+        if bad_i > 0:
+            nan = float("nan")
+            return cls(nan, nan, nan, nan, n_i, bad_i, log_weights)
+        if s1 == 0.0:    # every weight is zero
+            return cls(float("-inf"), float("inf"), 0.0, sum_lw / n, n_i, 0, log_weights)
+        ess = s1 * s1 / s2
+        return cls(m + math.log(s1) - math.log(n), math.sqrt(max(1.0 / ess - 1.0 / n, 0.0)), ess, sum_lw / n, n_i, 0,
+                   log_weights)
 
 
 class VariationalPosteriorCheckpoint(BaseModel):
@@ -142,6 +179,68 @@ class VariationalPosterior:
         self._calls.clear()
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
+
+    @torch.no_grad()
+    def log_evidence(self, sde: SDE, observation_likelihood: ObservationLikelihood, n_samples: int = 4096, chunk_size: int = 512,
+                     mixed_precision: bool = False, return_log_weights: bool = False) -> EvidenceEstimate:
+        """Importance-sampled log evidence ``log p(y)`` of the model (``sde``, ``observation_likelihood``, the prior) with the
+        variational posterior as proposal, for model comparison (``log_evidence`` +- ``standard_error``) and as a fit
+        diagnostic (``effective_sample_size``).
+
+        The evidence is that of the Euler-Maruyama-discretised model on this posterior's time grid, conditioned -- like the
+        ELBO -- on the start state being the first observation (``x0 = y0``).  Draws use the EMA weights, as ``sample()`` does,
+        ``chunk_size`` paths at a time (the last chunk is drawn in full; only the first ``n_samples`` weights count).  The first
+        chunk is drawn eagerly, the others replay a captured sampling call that this call owns (``sample()``'s graphs are not
+        touched).  Per chunk: draw, one log-weight kernel, one accumulate kernel into an fp64 state on the device; the host
+        synchronises once, at the end.  ``mixed_precision``: run the encoder under bf16 autocast, as ``sample()`` does; the
+        weights stay exact for the paths drawn, since they use the head's own transition means / Cholesky factors.
+        ``return_log_weights``: keep the ``[n_samples]`` log-weights (device tensor) in the result."""
+        from .. import _hip
+        from ..inference.evidence import importance_log_weights
+        if n_samples < 1 or chunk_size < 1:
+            raise ValueError(f"n_samples and chunk_size must be >= 1 (got {n_samples}, {chunk_size})")
+        state = _hip.log_weight_state(self.device)   # raises HipLibraryError off the GPU: there is no CPU implementation
+        n_chunks = -(-n_samples // chunk_size)
+        kept = torch.empty(n_samples, device=self.device, dtype=torch.float32) if return_log_weights else None
+        self.model.eval()
+        amp = torch.bfloat16 if mixed_precision else None
+        model = self.model
+        sampler = None
+        with self.exponential_moving_average.apply():
+            for c in range(n_chunks):
+                count = min(chunk_size, n_samples - c * chunk_size)
+                if c > 0 and sampler is None:
+                    sampler = self._evidence_sampler(chunk_size, amp)
+                if sampler:
+                    theta, _, drawn = sampler()
+                else:
+                    theta = model.sde_parameter_posterior.rsample(chunk_size)
+                    x0 = self.observations.values[0].unsqueeze(0).expand(chunk_size, -1)
+                    with torch.autocast(device_type=self.device.type, dtype=amp, enabled=amp is not None):
+                        drawn = sample_diffusion_paths(model.encoder, model.head, self.observations, theta, x0, self.time_horizon,
+                                                       self.time_step, self.state_space)
+                log_w = importance_log_weights(sde, self.observations, observation_likelihood, self.prior,
+                                               model.sde_parameter_posterior, theta, drawn, self.time_step)
+                _hip.log_weight_accumulate(log_w, count, state)
+                if kept is not None:
+                    kept[c * chunk_size:c * chunk_size + count].copy_(log_w[:count])
+        del sampler
+        return EvidenceEstimate.from_state(state.tolist(), kept)
+
+    def _evidence_sampler(self, n: int, amp: Optional[torch.dtype]):
+        """A captured sampling call of ``n`` paths owned by one ``log_evidence`` call (kept out of ``sample()``'s caches), or
+        False when capture is off or fails (the chunks are then drawn eagerly: same kernels, same draws)."""
+        if not _sampler.SAMPLE_GRAPH:
+            return False
+        try:
+            return CapturedPathSampler(self.model, self.observations, self.time_horizon, self.time_step, self.state_space, n,
+                                       autocast_dtype=amp, warmup=1)
+        except Exception as err:
+            import logging
+            logging.getLogger("viforsdes_amd").warning(
+                "VariationalPosterior.log_evidence: HIP graph capture of %d paths failed (%s: %s); sampling eagerly", n,
+                type(err).__name__, err)
+            return False
 
     def summary(self, n_samples: int = 1000, mixed_precision: bool = False) -> VariationalPosteriorSummary:
         s = self.sample(n_samples, mixed_precision)
