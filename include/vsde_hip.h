@@ -183,6 +183,8 @@ int vsde_gated_residual_fwd(int dtype, const void *x, const void *y, const void 
                             int64_t mod_pitch, void *stream);
 int vsde_gated_residual_bwd(int dtype, const void *y, const void *gate, const void *dout, void *dy, void *dgate, int64_t B,
                             int N, int C, int64_t mod_pitch, void *workspace, size_t workspace_bytes, void *stream);
+/* gated_residual_bwd: C % 4 == 0 and at most 256 lanes of 16 (bf16: 8 or 16) bytes per token -- C <= 1024 in f32, in bf16
+ * C <= 2048 when C % 8 == 0 and C <= 1024 otherwise; wider rows return VSDE_E_BADARG. */
 int vsde_swiglu_fwd(int dtype, const void *u, void *out, int64_t M, int H2, void *stream);
 int vsde_swiglu_bwd(int dtype, const void *u, const void *dout, void *du, int64_t M, int H2, void *stream);
 /* token_major selects the memory layout of the per-head tensors (attn, dattn, q, k, v, v0, dq, dk, dv, dv0):

@@ -240,7 +240,7 @@ def test_head_layouts_agree(dtype):
     assert abs(float(outs[False][-1]) - float(outs[True][-1])) <= 1e-3 * (1 + abs(float(outs[False][-1])))
 
 
-@pytest.mark.parametrize("C", [64, 128, 192, 256, 512, 1024])
+@pytest.mark.parametrize("C", [64, 128, 192, 256, 384, 512, 768, 1024])
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-5), (torch.bfloat16, 2e-2)])
 def test_ln_modulate_and_gated_residual_channel_counts(C, dtype, tol):
     """Every vector-width / lanes-per-token dispatch of the norm and residual kernels, incl. the fused column sums and the

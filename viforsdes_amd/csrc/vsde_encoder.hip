@@ -682,8 +682,9 @@ using namespace vsde;
         else { set_error("dtype must be 0 (f32) or 1 (bf16), got %d", (dtype)); return VSDE_E_BADARG; }      \
     } while (0)
 
-// per-batch-row vectors (scale, shift, gate and their gradients) may be column ranges of one wider [B][pitch] buffer
-#define MOD_PITCH_OK(mp, C) ((mp) == 0 || ((mp) >= (C) && (mp) % 8 == 0))
+// per-batch-row vectors (scale, shift, gate and their gradients) may be column ranges of one wider [B][pitch] buffer; a pitch
+// of exactly C is the contiguous layout (the kernels' vector width divides C, so its rows stay aligned whatever C % 8 is)
+#define MOD_PITCH_OK(mp, C) ((mp) == 0 || (mp) == (C) || ((mp) > (C) && (mp) % 8 == 0))
 
 extern "C" int vsde_ln_modulate_fwd(int dtype, const void *x, const void *scale, const void *shift, void *y, float *mean,
                                     float *rstd, int64_t B, int N, int C, double eps, int64_t mod_pitch, void *stream) {
@@ -779,8 +780,11 @@ extern "C" int vsde_gated_residual_bwd(int dtype, const void *y, const void *gat
     const int64_t BC = B * C;
     VSDE_DTYPE_SWITCH(dtype, {
         constexpr int VF = VecOf<T>::v;
+        // one lane per V channels of a token and no loop over channel groups: C / V lanes must fit the 256-thread block
+        VSDE_CHECK_ARG(C / (C % VF == 0 ? VF : 4) <= 256, VSDE_E_BADARG,
+                       "gated_residual_bwd: C = %d needs more than 256 lanes per token (C <= %d for this dtype)", C, C % VF == 0 ? 256 * VF : 1024);
         dim3 grid(colsum_chunks(B, N), (unsigned)B);
-        if (C % VF == 0 && C / VF <= 256)
+        if (C % VF == 0)
             hipLaunchKernelGGL((gated_residual_bwd_kernel<T, VF>), grid, dim3(256), 256 * VF * sizeof(float), s, (const T *)y,
                                (const T *)gate, (const T *)dout, (T *)dy, part, N, C, mp);
         else

@@ -25,9 +25,19 @@ def fp16_autocast() -> bool:
     return torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16
 
 
+def ln_channels_supported(channels: int, dtype: torch.dtype) -> bool:
+    """Whether the LayerNorm kernels have a branch for this width: the four conditions of ln_mod_dispatch (csrc/vsde_encoder.hip),
+    lanes x vector width tiling C into at most four slabs.  Both dtypes accept C in {64, 128, 192, 256, 384, 512, 768, 1024}."""
+    if channels % 64 or channels > 1024:
+        return False
+    vf = 8 if dtype == torch.bfloat16 else 4
+    return any(channels % (lanes * v) == 0 and channels // (lanes * v) <= 4
+               for v, lanes in ((vf, 64), (vf, 32), (vf // 2, 64), (vf // 4, 64))) or channels // 64 <= 4
+
+
 def usable(x: Tensor, channels: int, head_dim: int) -> bool:
     half = head_dim // 2
-    return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and not fp16_autocast() and channels % 64 == 0 and channels <= 1024
+    return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and not fp16_autocast() and ln_channels_supported(channels, x.dtype)
             and head_dim % 2 == 0 and 1 <= half <= 64 and (half & (half - 1)) == 0)
 
 
