@@ -1199,15 +1199,27 @@ def swiglu_mlp(x: Tensor, pin: PackedWeight, pout: PackedWeight) -> Tensor:
 ATTN_FUSED_TRAIN = os.environ.get("VSDE_ATTN_FUSED_TRAIN", "1") != "0"
 # VSDE_GATE_BWD_GEMM=0: output projection's input gradient and the gate backward as two kernels (A/B runs)
 GATE_BWD_GEMM = os.environ.get("VSDE_GATE_BWD_GEMM", "1") != "0"
-_NONZERO: dict[int, tuple] = {}   # id(weight) -> (weakref, version, all entries non-zero)
+_NONZERO: dict[int, tuple] = {}   # id(weight) -> (weakref, version, weights usable by the fused backward)
+# The fused backward rebuilds the normalised row n_j = (R^T yhat)_j / w_j from the saved bf16 rotated row yhat, so yhat's rounding
+# (2^-8 of |yhat_j| + |yhat_p|, p the rotary partner) reaches dy divided by |w_j|: against the separate passes (which normalise the
+# raw row) the error of channel j grows by about max|w| / |w_j|.  Weights below max|w| / NORM_WEIGHT_RATIO take the separate passes
+# (bound in tests/attention_reference.py).
+NORM_WEIGHT_RATIO = 16.0
+
+
+def norm_weights_fusable(w: Tensor) -> bool:
+    """Every |w_j| >= max|w| / NORM_WEIGHT_RATIO (so none is zero)."""
+    a = w.detach().abs()
+    return bool((a * NORM_WEIGHT_RATIO >= a.max()).all()) and bool((a > 0).all())
 
 
 def _all_nonzero(w: Tensor) -> bool:
-    """The fused backward divides by the (frozen) RMS weights: checked once per weight version (one host sync)."""
+    """The fused backward divides by the (frozen) RMS weights (``norm_weights_fusable``): checked once per weight version (one
+    host sync)."""
     hit = _NONZERO.get(id(w))
     if hit is not None and hit[0]() is w and hit[1] == w._version:
         return hit[2]
-    ok = bool((w.detach() != 0).all())
+    ok = norm_weights_fusable(w)
     _NONZERO[id(w)] = (weakref.ref(w), w._version, ok)
     return ok
 
@@ -1290,7 +1302,8 @@ class _AttentionCore(torch.autograd.Function):
 
 def attention_core_usable(x: Tensor, pack: "PackedWeight", heads: int, d: int, wq: Tensor, wk: Tensor, cos: Tensor) -> bool:
     """Training-step form of the attention block's core (see ``_AttentionCore``): K in (128, 256), head_dim 64, a 64-wide gate block,
-    a sequence the LDS-resident attention kernels take, fp32 non-zero norm weights and fp32 rotary tables."""
+    a sequence the LDS-resident attention kernels take, fp32 norm weights none of which is below max|w| / NORM_WEIGHT_RATIO and fp32
+    rotary tables."""
     rows = x.numel() // x.shape[-1]
     return (ENABLED and OWN_GEMM and ATTN_FUSED_TRAIN and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.bfloat16
             and x.ndim == 3 and x.shape[-1] in (128, 256) and d == 64 and pack.weight.shape[0] == 3 * heads * 64 + 64 and rows >= OWN_GEMM_MIN_ROWS
