@@ -5,6 +5,11 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps K --warmup W --full     # + every other measurement and check listed below
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line: nothing else.  ``--full``
+adds, after the timed steps: the no-grad sampling rates, per-kernel roofline and MFMA figures, the data-parallel costs, the
+OU sub-object, the parity gate (exit status non-zero when it fails) and the CPU baseline, and two rocprofv3 --pmc passes before.
 
 A "step" is one complete optimizer iteration of the reference's trainer._train_step
 (inference/trainer.py:166-206): theta ~ q -> SiT encoder (bf16 autocast) -> fused HIP GRU path
@@ -15,8 +20,8 @@ randomised (the default all-zero init makes the GRU irrelevant), synthetic input
 observations.  Weak scaling: every rank draws its own 512 paths.
 
 Rank 0 prints ONE JSON line.  value = sample paths pushed through a full ELBO step per second over
-all ranks (= global_batch * ELBO-iters/s); ELBO-iters/s and the no-grad sampled-paths/s (encoder +
-head, the VariationalPosterior.sample path) are extra fields.
+all ranks (= global_batch * ELBO-iters/s); ELBO-iters/s and (--full) the no-grad sampled-paths/s (encoder +
+head, the VariationalPosterior.sample path) are extra fields.  The --full fields:
 
 * ``roofline``: the serial GRU time-stepping forward (training variant), HIP events on its launch stream, priced with
   SURVEY 8(d)'s algorithmic bytes (bf16 context); ``frac_incl_projection`` also charges the hoisted context-projection
@@ -452,9 +457,10 @@ def encoder_families(step_fn, device, B, N, C, depth, heads, mlp_hidden, mlp_pad
 
 def measure(workload, batch, args, device, distributed, world, dump_dir=None):
     """Everything the JSON line says about ONE workload on this rank's GPU: the timed full ELBO step (K steps after W warm-up,
-    barrier + synchronize on both sides, MAX over ranks), the no-grad sampling calls, HIP-event timings of the head kernels
-    (-> roofline objects) and of the encoder alone (-> mfma_util).  ``dump_dir``: the outputs of the last timed step are written
-    there (step_outputs / write_outputs) before anything else runs.  Returns (fields, context for the CPU legs)."""
+    barrier + synchronize on both sides, MAX over ranks) and, with ``args.full`` only, the no-grad sampling calls, HIP-event
+    timings of the head kernels (-> roofline objects) and of the encoder alone (-> mfma_util).  ``dump_dir``: the outputs of the
+    last timed step are written there (step_outputs / write_outputs) before anything else runs.  Returns (fields, context for
+    the CPU legs)."""
     from viforsdes_amd import _hip
     from viforsdes_amd.examples.sdes import lv_problem, ou_problem, synthetic_problem
     from viforsdes_amd.inference.data_parallel import FlatGradientAllReduce
@@ -516,6 +522,17 @@ def measure(workload, batch, args, device, distributed, world, dump_dir=None):
         write_outputs(dump_dir, step_outputs(last[0], model, ctx.ema))
     iters_per_sec = args.steps / elapsed
     global_batch = batch * world
+    H, L, C = model.head.hidden_dim, model.head.num_layers, model.head.context_dim
+    out = {
+        "value": global_batch * iters_per_sec, "unit": "paths/s", "ms_per_step": 1e3 * elapsed / args.steps,
+        "config": {"workload": f"{workload}: state_dim={S}, T={T} Euler steps (dt={dt}), batch={batch}/GPU, "
+                               f"encoder {enc['enc_hidden']}x{enc['enc_depth']}x4 heads, GRU {H}x{L}",
+                   "global_batch": global_batch, "parallelism": f"dp{world}", "hip_graph": graph_mode},
+        "elbo_iters_per_sec": iters_per_sec,
+        "rccl_ranks": dist.get_world_size() if distributed else 1,
+    }
+    if not args.full:
+        return out, (problem, enc)
 
     # no-grad sampling call: theta rsample -> encoder -> head (eval kernel), as VariationalPosterior.sample
     model.eval()
@@ -565,7 +582,6 @@ def measure(workload, batch, args, device, distributed, world, dump_dir=None):
         allreduce_ms = e0.elapsed_time(e1) / 10
 
     # per-kernel timing of the hand-written head kernels (HIP events on the launch stream) -- eager steps
-    H, L, C = model.head.hidden_dim, model.head.num_layers, model.head.context_dim
     ntril = S * (S + 1) // 2
     _hip.profile_enable(True)
     slots = {k: [] for k in range(7)}
@@ -731,18 +747,12 @@ def measure(workload, batch, args, device, distributed, world, dump_dir=None):
     fwd_kernel = ("multi-path MFMA kernel (csrc/vsde_head_mp.hip), "
                   + ("2" if batch <= 512 else "4" if batch <= 1024 else "8" if batch <= 2048 else "16") + " paths per workgroup"
                   if (batch >= 32 and H == 64 and L <= 2 and S <= 2) else "four-waves-per-path VALU kernel (csrc/vsde_head.hip)")
-    out = {
-        "value": global_batch * iters_per_sec, "unit": "paths/s", "ms_per_step": 1e3 * elapsed / args.steps,
-        "config": {"workload": f"{workload}: state_dim={S}, T={T} Euler steps (dt={dt}), batch={batch}/GPU, "
-                               f"encoder {enc['enc_hidden']}x{enc['enc_depth']}x4 heads, GRU {H}x{L}",
-                   "global_batch": global_batch, "parallelism": f"dp{world}", "hip_graph": graph_mode},
-        "elbo_iters_per_sec": iters_per_sec,
+    out.update({
         "sampled_paths_per_sec": global_batch * args.steps / s_elapsed,
         "sampling_hip_graph": sample_graph, "sampled_paths_per_sec_eager": global_batch * args.steps / s_eager_elapsed,
         "sampled_paths_per_sec_head_only": head_pps,
         "sampled_paths_per_sec_head_only_large_batch": {"batch": big, "value": head_pps_big, "serial_kernel_ms": eval_ms_big,
                                                         "frac_of_hbm_peak": eval_bytes_step * big * T / (eval_ms_big * 1e-3) / 1e9 / HBM_PEAK_GBS},
-        "rccl_ranks": dist.get_world_size() if distributed else 1,
         "allreduce_ms_per_step": allreduce_ms,
         "dp_pack_ms": dp_pack_ms,
         "dp_payload_bytes": dp_payload_bytes,
@@ -776,7 +786,7 @@ def measure(workload, batch, args, device, distributed, world, dump_dir=None):
                       "achieved_tflops": enc_flops / (enc_ms * 1e-3) / 1e12, "peak_tflops": MFMA_BF16_PEAK_TFLOPS,
                       "frac": enc_flops / (enc_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
                       "frac_of_whole_step": enc_flops / (elapsed / args.steps) / 1e12 / MFMA_BF16_PEAK_TFLOPS},
-    }
+    })
     del tr, model, ctx
     import gc
     gc.collect()
@@ -798,9 +808,10 @@ def quiet_stdout():
         sys.stdout = sys.stderr
 
 
-def headline(out):
-    """The ONE stdout line: the contract's fields + roofline + cpu_baseline + both halves of BASELINE's metric + the parity
-    verdict, kept under 1.8 kB so that a 2 kB tail holds all of it (the full record goes to stderr / --detail-out)."""
+def headline(out, full):
+    """The ONE stdout line: the contract's fields and, after a --full run, roofline + cpu_baseline + both halves of BASELINE's
+    metric + the parity verdict, kept under 1.8 kB so that a 2 kB tail holds all of it (the full record goes to stderr /
+    --detail-out)."""
     r3 = lambda v: None if v is None else float(f"{v:.4g}")   # four significant digits
     rf, cb, par = out.get("roofline") or {}, out.get("cpu_baseline"), out.get("parity")
     cfg = dict(out["config"])
@@ -811,6 +822,9 @@ def headline(out):
     h["value"], h["ms_per_step"] = r3(out["value"]), r3(out["ms_per_step"])
     h["config"] = cfg
     h["elbo_iters_per_sec"] = r3(out.get("elbo_iters_per_sec"))
+    detail = "full record: stderr line 'BENCH_DETAIL {...}' (or --detail-out FILE)"
+    if not full:
+        return dict(h, detail=detail)
     h["sampled_paths_per_sec"] = r3(out.get("sampled_paths_per_sec"))
     h["sampled_paths_per_sec_head_only"] = r3(out.get("sampled_paths_per_sec_head_only"))
     bw = rf.get("backward") or {}
@@ -832,7 +846,7 @@ def headline(out):
         h["ou"] = {"ms_per_step": r3(ou["ms_per_step"]), "elbo_iters_per_sec": r3(ou["elbo_iters_per_sec"]),
                    "sampled_paths_per_sec": r3(ou["sampled_paths_per_sec"]), "roofline_frac": r3(ou["roofline"]["frac"])}
     h["dp_early_fraction"] = r3(out.get("dp_early_fraction"))
-    h["detail"] = "full record: stderr line 'BENCH_DETAIL {...}' (or --detail-out FILE)"
+    h["detail"] = detail
     return h
 
 
@@ -844,14 +858,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=None, help="sample paths per GPU (default: 512 LV, 128 OU, 256 synthetic)")
     ap.add_argument("--workload", default="lv", choices=["lv", "ou", "synthetic"])
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the cpu_baseline and parity legs (host CPU work)")
-    ap.add_argument("--no-ou", action="store_true", help="skip the OU (BASELINE config 1/2) sub-object of the LV line")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything besides the "
+                    "headline (sampling rates, roofline and MFMA figures, data-parallel costs, OU, parity gate, CPU baseline) "
+                    "and run the live PMC passes before them; a plain run only times the step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline and parity legs (host CPU work)")
+    ap.add_argument("--no-ou", action="store_true", help="--full: skip the OU (BASELINE config 1/2) sub-object of the LV line")
     ap.add_argument("--no-hip-graph", action="store_true", help="step eagerly instead of replaying a captured HIP graph")
     ap.add_argument("--hip-graph", action="store_true", help="always replay the captured HIP graph (default: whichever of "
                     "eager / replay is faster in a 3-step probe before the warm-up; same kernels and work either way)")
     ap.add_argument("--cpu-micro-batch", type=int, default=64)
-    ap.add_argument("--no-families", dest="no_families", action="store_true", help="skip the encoder_families kernel table (one profiled eager step)")
-    ap.add_argument("--no-pmc", action="store_true", help="roofline.traffic from the committed PMC passes instead of two live "
+    ap.add_argument("--no-families", dest="no_families", action="store_true", help="--full: skip the encoder_families kernel table "
+                    "(one profiled eager step)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: roofline.traffic from the committed PMC passes instead of two live "
                     "rocprofv3 --pmc passes (child processes, ~30 s) before the timed region")
     ap.add_argument("--detail-out", default=None, help="also write the FULL record (every field; the stdout line is the compact "
                     "headline, the full record always goes to stderr behind 'BENCH_DETAIL ') to this file")
@@ -871,7 +889,7 @@ def main():
     if args.gpus != world and distributed:
         raise SystemExit(f"--gpus {args.gpus} does not match WORLD_SIZE {world}")
     global LIVE_TRAFFIC
-    if (world == 1 and args.gpus == 1 and not args.no_pmc and args.workload == "lv" and (args.batch or 512) == 512
+    if (args.full and world == 1 and args.gpus == 1 and not args.no_pmc and args.workload == "lv" and (args.batch or 512) == 512
             and torch.cuda.device_count() > 0):   # device_count() does not initialise the GPU: the children get it to themselves
         LIVE_TRAFFIC = measure_pmc_traffic(512)
     if not torch.cuda.is_available():
@@ -900,17 +918,17 @@ def main():
                              "weight-gradient reductions, large-batch sampler) with fp32-equivalent results",
     }
     out.update(fields)
-    if args.workload == "lv" and not args.no_ou and world == 1:   # (the multi-GPU runs measure the headline workload only)
+    if args.full and args.workload == "lv" and not args.no_ou and world == 1:   # (the multi-GPU runs measure the headline workload only)
         # BASELINE configs 1/2 (north_star's second target): OU S=1, T=100, B=128 in the same run, same measurements
         ou_fields, _ = measure("ou", 128, args, device, distributed, world)
         out["ou"] = ou_fields
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "lv":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "lv":
         out["parity"] = parity_gate(problem, enc, device, force_mp=2 if batch > 256 else 0)
         # BASELINE config 2: OU (B=128, T=100) fused HIP GRU + ELBO, fp32 and bf16, vs the CPU path, with the tolerance
         out["parity"]["ou"] = parity_gate(ou_problem(), dict(enc_hidden=256, enc_depth=8), device, batch=128, steps=3, name="OU")
         out["parity"]["pass"] = bool(out["parity"]["pass"] and out["parity"]["ou"]["pass"])
         out["cpu_baseline"] = cpu_baseline(problem, ou_problem(), args.cpu_micro_batch, enc)
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["parity"] = None
         out["cpu_baseline"] = None
     if rank == 0:
@@ -920,7 +938,7 @@ def main():
         if args.detail_out:
             with open(args.detail_out, "w") as fh:
                 fh.write(detail + "\n")
-        print(json.dumps(headline(out)), file=_JSON_OUT, flush=True)
+        print(json.dumps(headline(out, args.full)), file=_JSON_OUT, flush=True)
     if distributed:
         dist.barrier()
         dist.destroy_process_group()

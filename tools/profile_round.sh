@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 kernel trace (per-kernel durations) of the bench workloads; summaries under gpurun_out/<round>/, to be copied into profiles/.
 #   usage (on the GPU box): tools/profile_round.sh <round> <tag> [lv] [ou] [synthetic]      e.g.  tools/profile_round.sh r04 v1 lv ou
-# Per workload: the kernel table of a profiled `bench.py --workload W --no-cpu-baseline --no-ou` run, then the same command unprofiled
+# Per workload: the kernel table of a profiled `bench.py --full --workload W --no-cpu-baseline --no-ou` run, then the same command unprofiled
 # (its JSON line).  rocprofv3 needs the program itself after `--` (python3, no shell / env hop) and TMPDIR on /tmp.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
@@ -11,9 +11,9 @@ O=$R/gpurun_out/$ROUND
 mkdir -p $O
 for w in $WL; do
   case $w in
-    lv) args="--workload lv" ;;
-    ou) args="--workload ou" ;;
-    synthetic) args="--workload synthetic --steps 5 --warmup 2" ;;
+    lv) args="--full --workload lv" ;;
+    ou) args="--full --workload ou" ;;
+    synthetic) args="--full --workload synthetic --steps 5 --warmup 2" ;;
   esac
   rm -rf /tmp/prof_$w
   rocprofv3 --kernel-trace --stats -d /tmp/prof_$w -o b -- python3 $R/bench.py $args --no-cpu-baseline --no-ou --no-pmc > $O/bench_prof_${w}_$TAG.log 2>&1
