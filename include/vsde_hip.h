@@ -414,6 +414,20 @@ int vsde_euler_maruyama_bwd(int kind, int B, int T, int S, int P, const float *t
                             const float *g_traj, double time_step, const uint8_t *positive_mask_host, float *g_x0,
                             float *g_theta, void *stream);
 
+/* Forecast of a built-in SDE: the recursion of vsde_euler_maruyama_fwd (same step, same 1e-6 clamp of the positive dims, NaN
+ * passed through) run for T steps from x_start[B][S] with theta[B][P], keeping only the states after the K grid steps
+ * out_steps[K] (device int32, non-decreasing, values in 1..T, duplicates allowed) in out[B][K][S]; an entry above T reads NaN.
+ * The Gaussian increments are made in the kernel, so neither the noise nor the trajectory exists in memory (O(B K S)).
+ * Noise stream: the normal of path b, step t, dim i is number t % 4 of philox4x32_10(counter {t / 4, i, b, 0},
+ * key {key[0], key[1]}) (Random123), Box-Muller on the word pairs (w0, w1) -> (z0, z1) and (w2, w3) -> (z2, z3):
+ *   u = ((w >> 8) + 0.5) 2^-24 in fp32 (round to nearest even: u in (0, 1]),  r = sqrt(-2 ln u_a),
+ *   z_a = r cos(2 pi u_b),  z_b = r sin(2 pi u_b).
+ * The tails are cut at |z| <= sqrt(50 ln 2) ~ 5.89 sigma.  key: 2 words in DEVICE memory, read by the kernel, so a launch captured
+ * in a HIP graph takes a fresh key per replay.  Kinds 1, 2: a thread per path; kind 3 (S <= 32): a thread per (path, dim).
+ * Forward only (no gradient). */
+int vsde_forecast(int kind, int B, int T, int S, int P, int K, const float *x_start, const float *theta, const int *out_steps,
+                  const uint32_t *key, double time_step, const uint8_t *positive_mask_host, float *out, void *stream);
+
 /* The [B]-sized tail of the ELBO (inference/evidence_lower_bound.py:52-83): Gaussian observation log-density of the states at
  * the K observed grid points x_obs[B][K][S] (core/observations.py:57-74; obs_matrix [O][S] or NULL = identity), iid prior
  * (prior_type 0 Normal, 1 LogNormal; core/priors.py:46-60), mean-field posterior log q(theta)

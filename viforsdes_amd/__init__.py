@@ -15,10 +15,10 @@ from .core.observations import GaussianObservationLikelihood, ObservationLikelih
 from .core.priors import Prior, PriorType
 from .core.sde import SDE, FunctionalSDE, make_sde
 from .infer import InferenceConfig, infer
-from .posterior.variational_posterior import EvidenceEstimate, VariationalPosterior
+from .posterior.variational_posterior import EvidenceEstimate, PosteriorPredictive, VariationalPosterior
 
 __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "TrainingConfig", "YamlConfig",
            "GaussianObservationLikelihood", "ObservationLikelihood", "Observations", "Prior", "PriorType", "SDE",
            "FunctionalSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior",
-           "EvidenceEstimate"]
+           "EvidenceEstimate", "PosteriorPredictive"]
 __version__ = "0.1.0"

@@ -61,7 +61,7 @@ EXPORTS = (
     "vsde_attention_max_tokens", "vsde_attention_fwd_bf16", "vsde_attention_bwd_bf16",
     "vsde_attention_fused_supported", "vsde_attention_fwd_gated_bf16", "vsde_gate_bwd_delta", "vsde_attention_bwd_fused_partials",
     "vsde_attention_bwd_fused_bf16",
-    "vsde_euler_maruyama_fwd", "vsde_euler_maruyama_bwd", "vsde_sde_coefficients_fwd", "vsde_sde_coefficients_bwd", "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
+    "vsde_euler_maruyama_fwd", "vsde_euler_maruyama_bwd", "vsde_forecast", "vsde_sde_coefficients_fwd", "vsde_sde_coefficients_bwd", "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
 )
@@ -328,6 +328,28 @@ def euler_maruyama_bwd(kind: str, theta, noise, traj, g_traj, time_step: float, 
               ctypes.c_int(theta.shape[1]), _ptr(theta), _ptr(noise), _ptr(traj), _ptr(g_traj), ctypes.c_double(time_step),
               _mask_bytes(positive_dims, S), _ptr(g_x0), _ptr(g_theta), _stream(dev))
     return g_x0, g_theta
+
+
+def forecast(kind: str, x_start, theta, n_steps: int, out_steps, key, time_step: float, positive_dims=()):
+    """States [B, K, S] of a built-in model SDE (``kind`` in SDE_KINDS) after the grid steps ``out_steps`` (int32 device tensor
+    [K], non-decreasing, values in 1..n_steps) of an ``n_steps``-step Euler-Maruyama run from x_start [B, S] with theta [B, P]; the
+    increments come from the Philox stream of ``key`` (2 int32 words on the device; see include/vsde_hip.h: vsde_forecast)."""
+    lib = load()
+    dev = _require_hip(x_start, theta, out_steps, key)
+    x_start, theta = _f32c(x_start), _f32c(theta)
+    if out_steps.dtype != torch.int32 or out_steps.ndim != 1 or key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2:
+        raise ValueError("forecast: out_steps must be an int32 [K] tensor and key two int32 words")
+    out_steps, key = out_steps.contiguous(), key.contiguous()
+    B, S = x_start.shape
+    K = out_steps.shape[0]
+    if theta.shape[0] != B:
+        raise ValueError(f"forecast: theta has {theta.shape[0]} rows for {B} start states")
+    with torch.cuda.device(dev):
+        out = torch.empty(B, K, S, device=dev, dtype=torch.float32)
+        _call(lib.vsde_forecast, ctypes.c_int(SDE_KINDS[kind]), ctypes.c_int(B), ctypes.c_int(n_steps), ctypes.c_int(S),
+              ctypes.c_int(theta.shape[1]), ctypes.c_int(K), _ptr(x_start), _ptr(theta), _ptr(out_steps), _ptr(key),
+              ctypes.c_double(time_step), _mask_bytes(positive_dims, S), _ptr(out), _stream(dev))
+    return out
 
 
 def _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean, post_log_std, theta_positive_dims):

@@ -92,3 +92,8 @@ class GaussianObservationLikelihood(BaseModel):
         resid = observations - pred
         per_dim = -0.5 * resid * resid / self.variance - 0.5 * math.log(2.0 * math.pi * self.variance)
         return per_dim.sum(dim=-1)
+
+    def sample(self, state: Tensor) -> Tensor:
+        """One draw y ~ N(H x, variance * I) per state row: ``predict(state) + sqrt(variance) * eps`` (torch's generator)."""
+        pred = self.predict(state)
+        return pred + math.sqrt(self.variance) * torch.randn_like(pred)

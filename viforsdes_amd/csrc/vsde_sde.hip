@@ -205,6 +205,116 @@ __global__ void __launch_bounds__(256) em_diag_bwd_kernel(EmParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Forecast: the recursion of em_fwd_kernel / em_diag_fwd_kernel run for T steps from x_start with its Gaussian increments made
+// in the kernel, keeping only the states at K requested steps.  Neither the noise nor the trajectory exists in memory.
+// Noise stream (include/vsde_hip.h): the normal of (path b, step t, dim i) is number t % 4 of
+// philox4x32_10(counter {t / 4, i, b, 0}, key {key[0], key[1]}) through Box-Muller on the word pairs (w0, w1), (w2, w3).
+struct FcParams {
+    int B, T, S, P, K;
+    const float *x0, *theta;
+    const int *steps;
+    const uint32_t *key;
+    float *out;
+    uint32_t pos_mask;
+    float dt, sqdt;
+};
+
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+
+// u = ((w >> 8) + 0.5) 2^-24 in (0, 1] (fp32, round to nearest even), r = sqrt(-2 ln u_a): |z| <= sqrt(50 ln 2) ~ 5.89
+__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float &za, float &zb) {
+    const float ua = ((float)(wa >> 8) + 0.5f) * 5.9604644775390625e-8f, ub = ((float)(wb >> 8) + 0.5f) * 5.9604644775390625e-8f;
+    const float r = sqrtf(-2.f * logf(ua));
+    float s, c;
+    sincospif(2.f * ub, &s, &c);
+    za = r * c; zb = r * s;
+}
+
+// normals of steps 4 blk .. 4 blk + 3 of (path b, dim i)
+__device__ __forceinline__ void fc_normals(uint32_t blk, uint32_t i, uint32_t b, uint32_t k0, uint32_t k1, float *z) {
+    const uint4 w = philox4x32_10(make_uint4(blk, i, b, 0u), k0, k1);
+    box_muller(w.x, w.y, z[0], z[1]);
+    box_muller(w.z, w.w, z[2], z[3]);
+}
+
+// kinds 1, 2: thread = path (S = 1, 2 dims per thread); kind 3: thread = (path, dim), one dim per thread.  A block of 4 steps
+// is branch-free: the Philox / Box-Muller work of the NEXT block depends on no state, so it sits in the same basic block as the
+// 4-step serial chain and the scheduler interleaves the two.  Output rows are written after the block from the 4 kept states
+// (out_steps is the same for every thread: the write loop is uniform).  Steps that never come (out_steps above T) read NaN.
+template <int KIND>
+__global__ void __launch_bounds__(256) forecast_kernel(FcParams p) {
+    constexpr int S = EmDims<KIND>::S, P = EmDims<KIND>::P;
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int b, d0, rs;                          // path, first state dim of this thread, row stride of x_start / out
+    if constexpr (KIND == 3) {
+        if (q >= (int64_t)p.B * p.S) return;
+        b = (int)(q / p.S); d0 = (int)(q % p.S); rs = p.S;
+    } else {
+        if (q >= p.B) return;
+        b = (int)q; d0 = 0; rs = S;
+    }
+    const uint32_t k0 = p.key[0], k1 = p.key[1];
+    float x[S], th[P];
+    bool pos[S];
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        x[i] = p.x0[(int64_t)b * rs + d0 + i];
+        pos[i] = (p.pos_mask >> (d0 + i)) & 1u;
+    }
+    if constexpr (KIND == 3) {
+        th[0] = p.theta[(int64_t)b * p.P + d0]; th[1] = p.theta[(int64_t)b * p.P + p.S + d0];
+    } else {
+#pragma unroll
+        for (int k = 0; k < P; ++k) th[k] = p.theta[(int64_t)b * P + k];
+    }
+    float *o = p.out + (int64_t)b * p.K * rs + d0;
+    int k = 0, next = p.steps[0];
+    float zn[S][4];
+#pragma unroll
+    for (int i = 0; i < S; ++i) fc_normals(0u, (uint32_t)(d0 + i), (uint32_t)b, k0, k1, zn[i]);
+    const int nblk = (p.T + 3) / 4;
+    for (int blk = 0; blk < nblk && k < p.K; ++blk) {
+        float z[S][4], xs[4][S];
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[i][j] = zn[i][j];
+            fc_normals((uint32_t)(blk + 1), (uint32_t)(d0 + i), (uint32_t)b, k0, k1, zn[i]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float e[S], y[S];
+#pragma unroll
+            for (int i = 0; i < S; ++i) e[i] = z[i][j];
+            em_step<KIND>(x, th, e, p.dt, p.sqdt, y);
+#pragma unroll
+            for (int i = 0; i < S; ++i) xs[j][i] = x[i] = pos[i] ? floor_nan(y[i]) : y[i];
+        }
+        // steps past T in the last block are computed and never written: rows are written for out_steps <= t1 only
+        const int t1 = min(4 * blk + 4, p.T);
+        while (k < p.K && next <= t1) {
+            const int j = max(next - 4 * blk - 1, 0);
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+                o[(int64_t)k * rs + i] = j == 0 ? xs[0][i] : j == 1 ? xs[1][i] : j == 2 ? xs[2][i] : xs[3][i];
+            if (++k < p.K) next = p.steps[k];
+        }
+    }
+    for (; k < p.K; ++k)
+#pragma unroll
+        for (int i = 0; i < S; ++i) o[(int64_t)k * rs + i] = __builtin_nanf("");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Drift f(x_t, theta) and diffusion factor G(x_t, theta) of the built-in SDEs on every grid point of a batch of paths, and
 // the vector-Jacobian product the ELBO backward needs.  Replaces the ~35 (forward) + ~70 (autograd backward) tiny torch
 // kernels the Python drift / diffusion callables expand to on the flattened [(B T), S] states
@@ -397,6 +507,25 @@ extern "C" int vsde_euler_maruyama_bwd(int kind, int B, int T, int S, int P, con
     if (kind == 1) hipLaunchKernelGGL(em_bwd_kernel<1>, dim3(grid), dim3(kEmPaths), 0, s, p);
     else if (kind == 2) hipLaunchKernelGGL(em_bwd_kernel<2>, dim3(grid), dim3(kEmPaths), 0, s, p);
     else hipLaunchKernelGGL(em_diag_bwd_kernel, dim3((unsigned)(((int64_t)B * S + 255) / 256)), dim3(256), 0, s, p);
+    VSDE_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int vsde_forecast(int kind, int B, int T, int S, int P, int K, const float *x_start, const float *theta,
+                             const int *out_steps, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                             float *out, void *stream) {
+    int rc = em_check(kind, B, T, S, P);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(K > 0, VSDE_E_BADARG, "bad forecast output count K=%d", K);
+    VSDE_CHECK_ARG(S <= 32, VSDE_E_BADARG, "forecast state_dim %d above 32", S);
+    VSDE_CHECK_ARG(x_start && theta && out_steps && key && out && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
+    FcParams p = {};
+    p.B = B; p.T = T; p.S = S; p.P = P; p.K = K; p.x0 = x_start; p.theta = theta; p.steps = out_steps; p.key = key; p.out = out;
+    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+    hipStream_t s = (hipStream_t)stream;
+    if (kind == 1) hipLaunchKernelGGL(forecast_kernel<1>, dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0, s, p);
+    else if (kind == 2) hipLaunchKernelGGL(forecast_kernel<2>, dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0, s, p);
+    else hipLaunchKernelGGL(forecast_kernel<3>, dim3((unsigned)(((int64_t)B * S + 255) / 256)), dim3(256), 0, s, p);
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -95,6 +95,44 @@ class EvidenceEstimate:
                    log_weights)
 
 
+_QUANTILE_MAX_ELEMENTS = 1 << 24   # torch.quantile refuses larger inputs: wider tensors are taken in column blocks
+
+
+@dataclass(frozen=True)
+class PosteriorPredictive:
+    """Posterior predictive draws (``VariationalPosterior.predict``): ``n`` joint draws of theta and the model state at
+    ``times`` -- read from the posterior path inside the time horizon, and the model SDE continued from that path's end state
+    with the same theta after it -- and, when an observation likelihood was given, one fresh observation of every state.
+
+    ``times [K]``, ``sde_parameters [n, P]``, ``states [n, K, S]``, ``observations [n, K, O]`` or None."""
+    times: Tensor
+    sde_parameters: Tensor
+    states: Tensor
+    observations: Optional[Tensor] = None
+
+    def _draws(self, observations: bool) -> Tensor:
+        if not observations:
+            return self.states
+        if self.observations is None:
+            raise ValueError("no observation draws: predict() was called without an observation_likelihood")
+        return self.observations
+
+    def quantiles(self, observations: bool = False) -> Quantiles:
+        """Per-time, per-dimension quantiles ``[K, S]`` (``[K, O]`` for the observations) at the levels ``summary()`` uses."""
+        v = self._draws(observations)
+        levels = torch.tensor(QUANTILE_LEVELS, device=v.device, dtype=v.dtype)
+        flat = v.reshape(v.shape[0], -1)
+        cols = max(1, _QUANTILE_MAX_ELEMENTS // flat.shape[0])
+        q = torch.cat([torch.quantile(flat[:, c:c + cols], levels, dim=0) for c in range(0, flat.shape[1], cols)], dim=1)
+        return Quantiles(*q.reshape(len(QUANTILE_LEVELS), *v.shape[1:]).unbind(0))
+
+    def mean(self, observations: bool = False) -> Tensor:
+        return self._draws(observations).mean(dim=0)
+
+    def std(self, observations: bool = False) -> Tensor:
+        return self._draws(observations).std(dim=0)
+
+
 class VariationalPosteriorCheckpoint(BaseModel):
     model_config = ConfigDict(frozen=True, arbitrary_types_allowed=True)
     model_state: dict[str, Tensor]
@@ -227,9 +265,9 @@ class VariationalPosterior:
         del sampler
         return EvidenceEstimate.from_state(state.tolist(), kept)
 
-    def _evidence_sampler(self, n: int, amp: Optional[torch.dtype]):
-        """A captured sampling call of ``n`` paths owned by one ``log_evidence`` call (kept out of ``sample()``'s caches), or
-        False when capture is off or fails (the chunks are then drawn eagerly: same kernels, same draws)."""
+    def _evidence_sampler(self, n: int, amp: Optional[torch.dtype], caller: str = "log_evidence"):
+        """A captured sampling call of ``n`` paths owned by one ``log_evidence`` (or ``predict``) call (kept out of ``sample()``'s
+        caches), or False when capture is off or fails (the chunks are then drawn eagerly: same kernels, same draws)."""
         if not _sampler.SAMPLE_GRAPH:
             return False
         try:
@@ -238,9 +276,83 @@ class VariationalPosterior:
         except Exception as err:
             import logging
             logging.getLogger("viforsdes_amd").warning(
-                "VariationalPosterior.log_evidence: HIP graph capture of %d paths failed (%s: %s); sampling eagerly", n,
+                "VariationalPosterior.%s: HIP graph capture of %d paths failed (%s: %s); sampling eagerly", caller, n,
                 type(err).__name__, err)
             return False
+
+    @torch.no_grad()
+    def predict(self, sde: SDE, times, n_samples: int = 1000, observation_likelihood: Optional[ObservationLikelihood] = None,
+                chunk_size: int = 512, mixed_precision: bool = False) -> PosteriorPredictive:
+        """Posterior predictive draws of the state at ``times`` (1-D, sorted, >= 0) and, with ``observation_likelihood``, of
+        fresh observations of it: what the fitted model says about the process inside the data window and after it.
+
+        Each of the ``n_samples`` draws pairs a theta with its own posterior path, as ``sample()`` does (EMA weights, same RNG
+        order: the theta draw, then the path noise).  A time maps to the grid step ``round(t / time_step)`` (the rule of
+        ``grid_index``).  Steps inside the horizon are read from the path; steps after it come from the model SDE ``sde``
+        continued from the path's end state with the draw's theta (``forecast_states``: one launch over all draws for a built-in
+        SDE; the positive state dims are clamped at 1e-6 as in ``euler_maruyama``).  Paths are drawn ``chunk_size`` at a time,
+        as in ``log_evidence``: the first chunk eagerly, the others by replaying a captured sampling call that this call owns
+        (``sample()``'s graphs are not touched).  Then one forecast key, then the observation noise, are drawn.
+        ``observation_likelihood`` needs a ``sample(state)`` method (``GaussianObservationLikelihood`` has one).
+        ``mixed_precision``: run the encoder under bf16 autocast, as ``sample()`` does."""
+        from .. import _hip
+        from ..core.forecast import forecast_states
+        times = times if isinstance(times, Tensor) else torch.as_tensor(times, dtype=torch.float32)
+        if times.ndim != 1 or times.numel() < 1:
+            raise ValueError(f"times must be a non-empty 1-D tensor, got shape {tuple(times.shape)}")
+        times = times.detach().cpu()
+        if not times.is_floating_point():
+            times = times.float()
+        if not bool(torch.isfinite(times).all()) or bool((times < 0).any()) or bool((times[1:] < times[:-1]).any()):
+            raise ValueError("times must be finite, >= 0 and sorted in non-decreasing order")
+        if n_samples < 1 or chunk_size < 1:
+            raise ValueError(f"n_samples and chunk_size must be >= 1 (got {n_samples}, {chunk_size})")
+        S, P = self.state_space.dim, self.model.sde_parameter_posterior.sde_param_dim
+        if sde.state_dim != S or sde.sde_param_dim != P:
+            raise ValueError(f"sde has state_dim {sde.state_dim}, sde_param_dim {sde.sde_param_dim}; the posterior has {S}, {P}")
+        like = observation_likelihood
+        if like is not None and not callable(getattr(like, "sample", None)):
+            raise TypeError(f"{type(like).__name__} has no sample(state) method: observations cannot be drawn from it")
+        if self.device.type != "cuda":
+            raise _hip.HipLibraryError("VariationalPosterior.predict draws paths with the HIP kernels; there is no CPU implementation")
+        dev, dt = self.device, self.time_step
+        n_steps = round(self.time_horizon / dt)
+        steps = torch.round(times / dt).long()
+        n_in = int((steps <= n_steps).sum())
+        rows_in = steps[:n_in].to(dev)
+        chunk = min(chunk_size, n_samples)
+        theta_all = torch.empty(n_samples, P, device=dev)
+        ends = torch.empty(n_samples, S, device=dev)
+        inside = torch.empty(n_samples, n_in, S, device=dev)
+        self.model.eval()
+        amp = torch.bfloat16 if mixed_precision else None
+        model = self.model
+        sampler = None
+        with self.exponential_moving_average.apply():
+            for c in range(-(-n_samples // chunk)):
+                lo, count = c * chunk, min(chunk, n_samples - c * chunk)
+                if c > 0 and sampler is None:
+                    sampler = self._evidence_sampler(chunk, amp, caller="predict")
+                if sampler:
+                    theta, x, _ = sampler()
+                else:
+                    theta = model.sde_parameter_posterior.rsample(chunk)
+                    x0 = self.observations.values[0].unsqueeze(0).expand(chunk, -1)
+                    with torch.autocast(device_type=dev.type, dtype=amp, enabled=amp is not None):
+                        x = sample_diffusion_paths(model.encoder, model.head, self.observations, theta, x0, self.time_horizon,
+                                                   self.time_step, self.state_space).x
+                theta_all[lo:lo + count] = theta[:count]
+                ends[lo:lo + count] = x[:count, n_steps]
+                if n_in:
+                    inside[lo:lo + count] = x[:count, rows_in]
+        del sampler
+        states = inside
+        if n_in < steps.numel():
+            ahead = steps[n_in:] - n_steps
+            after = forecast_states(sde, ends, theta_all, int(ahead[-1]), ahead, dt, self.state_space.positive_dims)
+            states = torch.cat([inside, after.to(inside.dtype)], dim=1)
+        observations = like.sample(states) if like is not None else None
+        return PosteriorPredictive(times=times.to(dev), sde_parameters=theta_all, states=states, observations=observations)
 
     def summary(self, n_samples: int = 1000, mixed_precision: bool = False) -> VariationalPosteriorSummary:
         s = self.sample(n_samples, mixed_precision)
