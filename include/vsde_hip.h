@@ -473,6 +473,48 @@ int vsde_sde_coefficients_fwd(int kind, int B, int T, int S, int P, const float 
 int vsde_sde_coefficients_bwd(int kind, int B, int T, int S, int P, const float *x, const float *theta, const float *g_drift,
                               const float *g_diffusion, float *g_x, float *g_theta, void *stream);
 
+/* Mass-action chemical reaction networks in their diffusion (chemical Langevin) approximation (ReactionNetworkSDE): S species,
+ * R reactions, one rate constant per reaction (theta[B][R], so P = R).  With r_ji = order[j][i] and nu_ji = change[j][i]:
+ *   propensity  h_j = theta_j prod_i x_i^r_ji   (no combinatorial factor: such constants belong in theta_j)
+ *   drift       f = sum_j h_j nu_j,   covariance  Sigma = sum_j h_j nu_j nu_j^T,
+ *   diffusion   the floored Cholesky factor of Sigma, column by column:
+ *               L_jj = sqrt(max(Sigma_jj - sum_{k<j} L_jk^2, 1e-6)),  L_ij = (Sigma_ij - sum_{k<j} L_ik L_jk) / max(L_jj, 1e-6)
+ * with torch.clamp semantics (NaN propagates; the gradient passes where the clamped quantity is >= 1e-6).  At S = 2 these are
+ * the three clamps of VSDE_SDE_LOTKA_VOLTERRA.  The descriptor is HOST memory, copied into the kernel arguments at launch: no
+ * device allocation, so every vsde_crn_* call can be captured in a HIP graph.  Entries of rows >= R and columns >= S are
+ * ignored.  Each vsde_crn_* entry point takes the arguments of the entry point it mirrors with `kind` replaced by the
+ * descriptor, and returns VSDE_E_BADARG before any HIP call when the descriptor is bad (S outside 1..8, R outside 1..16, an
+ * order outside 0..3) or disagrees with S / P. */
+#define VSDE_SDE_REACTION_NETWORK 4
+#define VSDE_CRN_MAX_SPECIES 8
+#define VSDE_CRN_MAX_REACTIONS 16
+#define VSDE_CRN_MAX_ORDER 3
+typedef struct vsde_crn_network {
+    int32_t S;                                                     /* species = state_dim                      */
+    int32_t R;                                                     /* reactions = sde_param_dim                */
+    int8_t order[VSDE_CRN_MAX_REACTIONS][VSDE_CRN_MAX_SPECIES];   /* reactant order r_ji of species i, 0..3   */
+    int8_t change[VSDE_CRN_MAX_REACTIONS][VSDE_CRN_MAX_SPECIES];  /* net change nu_ji = products - reactants   */
+} vsde_crn_network;
+int vsde_crn_sde_coefficients_fwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *x, const float *theta,
+                                  float *drift, float *diffusion, void *stream);
+int vsde_crn_sde_coefficients_bwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *x, const float *theta,
+                                  const float *g_drift, const float *g_diffusion, float *g_x, float *g_theta, void *stream);
+int vsde_crn_euler_maruyama_fwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *x0, const float *theta,
+                                const float *noise, double time_step, const uint8_t *positive_mask_host, float *traj, void *stream);
+int vsde_crn_euler_maruyama_bwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *theta, const float *noise,
+                                const float *traj, const float *g_traj, double time_step, const uint8_t *positive_mask_host,
+                                float *g_x0, float *g_theta, void *stream);
+/* The noise stream of vsde_forecast (the same normals for the same key, path, step and dim). */
+int vsde_crn_forecast(const vsde_crn_network *net, int B, int T, int S, int P, int K, const float *x_start, const float *theta,
+                      const int *out_steps, const uint32_t *key, double time_step, const uint8_t *positive_mask_host, float *out,
+                      void *stream);
+/* vsde_log_weights with the network's drift / diffusion evaluated in registers (no drift / diffusion tensors). */
+int vsde_crn_log_weights(const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z, const float *means,
+                         const float *chol, const float *theta, const int *obs_rows, const float *obs_values,
+                         const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std,
+                         const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host,
+                         const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

@@ -61,7 +61,9 @@ EXPORTS = (
     "vsde_attention_max_tokens", "vsde_attention_fwd_bf16", "vsde_attention_bwd_bf16",
     "vsde_attention_fused_supported", "vsde_attention_fwd_gated_bf16", "vsde_gate_bwd_delta", "vsde_attention_bwd_fused_partials",
     "vsde_attention_bwd_fused_bf16",
-    "vsde_euler_maruyama_fwd", "vsde_euler_maruyama_bwd", "vsde_forecast", "vsde_sde_coefficients_fwd", "vsde_sde_coefficients_bwd", "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
+    "vsde_euler_maruyama_fwd", "vsde_euler_maruyama_bwd", "vsde_forecast", "vsde_sde_coefficients_fwd", "vsde_sde_coefficients_bwd",
+    "vsde_crn_sde_coefficients_fwd", "vsde_crn_sde_coefficients_bwd", "vsde_crn_euler_maruyama_fwd", "vsde_crn_euler_maruyama_bwd",
+    "vsde_crn_forecast", "vsde_crn_log_weights", "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
 )
@@ -298,24 +300,62 @@ def elbo_path_terms_bwd(z, x, means, chol, drift, diffusion, positive_dims, time
     return tuple(outs)
 
 
-SDE_KINDS = {"ornstein_uhlenbeck": 1, "lotka_volterra": 2, "linear_diagonal": 3}
+SDE_KINDS = {"ornstein_uhlenbeck": 1, "lotka_volterra": 2, "linear_diagonal": 3, "reaction_network": 4}
+CRN_MAX_SPECIES, CRN_MAX_REACTIONS, CRN_MAX_ORDER = 8, 16, 3
 
 
-def euler_maruyama_fwd(kind: str, x0, theta, noise, time_step: float, positive_dims=()):
-    """Trajectory [B, T+1, S] of a built-in model SDE (``kind`` in SDE_KINDS) for given noise [B, T, S]."""
+class CrnNetwork(ctypes.Structure):
+    """``vsde_crn_network`` (include/vsde_hip.h): a reaction network's reactant orders and net changes, passed by pointer to
+    host memory and copied into the kernel arguments at launch."""
+    _fields_ = [("S", ctypes.c_int32), ("R", ctypes.c_int32),
+                ("order", (ctypes.c_int8 * CRN_MAX_SPECIES) * CRN_MAX_REACTIONS),
+                ("change", (ctypes.c_int8 * CRN_MAX_SPECIES) * CRN_MAX_REACTIONS)]
+
+
+def crn_network(order, change) -> CrnNetwork:
+    """The descriptor of a network with reactant orders ``order`` and net changes ``change`` (both [R][S] integers)."""
+    R, S = len(order), len(order[0])
+    if not (1 <= S <= CRN_MAX_SPECIES and 1 <= R <= CRN_MAX_REACTIONS) or len(change) != R:
+        raise ValueError(f"reaction-network descriptor: {S} species / {R} reactions outside 1..{CRN_MAX_SPECIES} / 1..{CRN_MAX_REACTIONS}")
+    net = CrnNetwork()
+    net.S, net.R = S, R
+    for j in range(R):
+        if len(order[j]) != S or len(change[j]) != S:
+            raise ValueError(f"reaction-network descriptor: row {j} does not have {S} entries")
+        for i in range(S):
+            if not 0 <= order[j][i] <= CRN_MAX_ORDER or not -128 <= change[j][i] <= 127:
+                raise ValueError(f"reaction-network descriptor: reaction {j}, species {i}: order {order[j][i]} / change "
+                                 f"{change[j][i]} outside 0..{CRN_MAX_ORDER} / int8")
+            net.order[j][i], net.change[j][i] = order[j][i], change[j][i]
+    return net
+
+
+def _sde_entry(lib, name: str, kind: str, network):
+    """(entry point, first argument) of a built-in SDE: ``vsde_<name>(kind, ...)``, or for a reaction network the mirrored
+    ``vsde_crn_<name>(&descriptor, ...)``."""
+    if kind == "reaction_network":
+        if not isinstance(network, CrnNetwork):
+            raise ValueError("the reaction-network kernels need the network's descriptor (ReactionNetworkSDE.network_descriptor())")
+        return getattr(lib, "vsde_crn_" + name), ctypes.byref(network)
+    return getattr(lib, "vsde_" + name), ctypes.c_int(SDE_KINDS[kind])
+
+
+def euler_maruyama_fwd(kind: str, x0, theta, noise, time_step: float, positive_dims=(), network=None):
+    """Trajectory [B, T+1, S] of a built-in model SDE (``kind`` in SDE_KINDS; a reaction network also needs its ``network``
+    descriptor) for given noise [B, T, S]."""
     lib = load()
     dev = _require_hip(x0, theta, noise)
     x0, theta, noise = _f32c(x0), _f32c(theta), _f32c(noise)
     B, T, S = noise.shape
     with torch.cuda.device(dev):
         traj = torch.empty(B, T + 1, S, device=dev, dtype=torch.float32)
-        _call(lib.vsde_euler_maruyama_fwd, ctypes.c_int(SDE_KINDS[kind]), ctypes.c_int(B), ctypes.c_int(T), ctypes.c_int(S),
+        _call(*_sde_entry(lib, "euler_maruyama_fwd", kind, network), ctypes.c_int(B), ctypes.c_int(T), ctypes.c_int(S),
               ctypes.c_int(theta.shape[1]), _ptr(x0), _ptr(theta), _ptr(noise), ctypes.c_double(time_step),
               _mask_bytes(positive_dims, S), _ptr(traj), _stream(dev))
     return traj
 
 
-def euler_maruyama_bwd(kind: str, theta, noise, traj, g_traj, time_step: float, positive_dims=()):
+def euler_maruyama_bwd(kind: str, theta, noise, traj, g_traj, time_step: float, positive_dims=(), network=None):
     """(g_x0 [B,S], g_theta [B,P]) of ``euler_maruyama_fwd`` for the upstream gradient g_traj [B, T+1, S]."""
     lib = load()
     dev = _require_hip(theta, noise, traj, g_traj)
@@ -324,13 +364,13 @@ def euler_maruyama_bwd(kind: str, theta, noise, traj, g_traj, time_step: float, 
     with torch.cuda.device(dev):
         g_x0 = torch.empty(B, S, device=dev, dtype=torch.float32)
         g_theta = torch.empty_like(theta)
-        _call(lib.vsde_euler_maruyama_bwd, ctypes.c_int(SDE_KINDS[kind]), ctypes.c_int(B), ctypes.c_int(T), ctypes.c_int(S),
+        _call(*_sde_entry(lib, "euler_maruyama_bwd", kind, network), ctypes.c_int(B), ctypes.c_int(T), ctypes.c_int(S),
               ctypes.c_int(theta.shape[1]), _ptr(theta), _ptr(noise), _ptr(traj), _ptr(g_traj), ctypes.c_double(time_step),
               _mask_bytes(positive_dims, S), _ptr(g_x0), _ptr(g_theta), _stream(dev))
     return g_x0, g_theta
 
 
-def forecast(kind: str, x_start, theta, n_steps: int, out_steps, key, time_step: float, positive_dims=()):
+def forecast(kind: str, x_start, theta, n_steps: int, out_steps, key, time_step: float, positive_dims=(), network=None):
     """States [B, K, S] of a built-in model SDE (``kind`` in SDE_KINDS) after the grid steps ``out_steps`` (int32 device tensor
     [K], non-decreasing, values in 1..n_steps) of an ``n_steps``-step Euler-Maruyama run from x_start [B, S] with theta [B, P]; the
     increments come from the Philox stream of ``key`` (2 int32 words on the device; see include/vsde_hip.h: vsde_forecast)."""
@@ -346,7 +386,7 @@ def forecast(kind: str, x_start, theta, n_steps: int, out_steps, key, time_step:
         raise ValueError(f"forecast: theta has {theta.shape[0]} rows for {B} start states")
     with torch.cuda.device(dev):
         out = torch.empty(B, K, S, device=dev, dtype=torch.float32)
-        _call(lib.vsde_forecast, ctypes.c_int(SDE_KINDS[kind]), ctypes.c_int(B), ctypes.c_int(n_steps), ctypes.c_int(S),
+        _call(*_sde_entry(lib, "forecast", kind, network), ctypes.c_int(B), ctypes.c_int(n_steps), ctypes.c_int(S),
               ctypes.c_int(theta.shape[1]), ctypes.c_int(K), _ptr(x_start), _ptr(theta), _ptr(out_steps), _ptr(key),
               ctypes.c_double(time_step), _mask_bytes(positive_dims, S), _ptr(out), _stream(dev))
     return out
@@ -398,9 +438,10 @@ def elbo_tail_bwd(x_obs, obs_values, obs_matrix, variance: float, theta, prior_t
 
 def log_weights(kind: str | None, z, means, chol, drift, diffusion, theta, obs_rows, obs_values, obs_matrix, variance: float,
                 prior_type: int, prior_mean: float, prior_std: float, post_mean, post_log_std, state_positive_dims,
-                theta_positive_dims, time_step: float):
+                theta_positive_dims, time_step: float, network=None):
     """Per-sample importance log-weights [B] (see include/vsde_hip.h: vsde_log_weights).  ``kind`` in SDE_KINDS evaluates the
-    built-in drift / diffusion in the kernel (``drift`` / ``diffusion`` None); ``kind`` None reads the given tensors."""
+    built-in drift / diffusion in the kernel (``drift`` / ``diffusion`` None; a reaction network also needs its ``network``
+    descriptor: vsde_crn_log_weights); ``kind`` None reads the given tensors."""
     lib = load()
     dev = _require_hip(z, means, chol, drift, diffusion, theta, obs_rows, obs_values, post_mean, post_log_std)
     z, means, chol, theta, obs_values, post_mean, post_log_std = (
@@ -415,14 +456,20 @@ def log_weights(kind: str | None, z, means, chol, drift, diffusion, theta, obs_r
         raise ValueError("log_weights: inconsistent shapes")
     if kind is None and (drift is None or tuple(drift.shape) != (B, T1 - 1, S) or tuple(diffusion.shape) != (B, T1 - 1, S, S)):
         raise ValueError("log_weights: drift [B, T, S] and diffusion [B, T, S, S] are required without a built-in kind")
+    dims = (ctypes.c_int(B), ctypes.c_int(T1 - 1), ctypes.c_int(S), ctypes.c_int(K), ctypes.c_int(O), ctypes.c_int(P),
+            _ptr(z), _ptr(means), _ptr(chol))
+    tail = (_ptr(theta), _ptr(obs_rows), _ptr(obs_values), _ptr(obs_matrix), ctypes.c_double(variance),
+            ctypes.c_int(prior_type), ctypes.c_double(prior_mean), ctypes.c_double(prior_std), _ptr(post_mean),
+            _ptr(post_log_std), _mask_bytes(state_positive_dims, S), _mask_bytes(theta_positive_dims, P),
+            ctypes.c_double(time_step))
     with torch.cuda.device(dev):
         out = torch.empty(B, device=dev, dtype=torch.float32)
-        _call(lib.vsde_log_weights, ctypes.c_int(0 if kind is None else SDE_KINDS[kind]), ctypes.c_int(B), ctypes.c_int(T1 - 1),
-              ctypes.c_int(S), ctypes.c_int(K), ctypes.c_int(O), ctypes.c_int(P), _ptr(z), _ptr(means), _ptr(chol), _ptr(drift),
-              _ptr(diffusion), _ptr(theta), _ptr(obs_rows), _ptr(obs_values), _ptr(obs_matrix), ctypes.c_double(variance),
-              ctypes.c_int(prior_type), ctypes.c_double(prior_mean), ctypes.c_double(prior_std), _ptr(post_mean),
-              _ptr(post_log_std), _mask_bytes(state_positive_dims, S), _mask_bytes(theta_positive_dims, P),
-              ctypes.c_double(time_step), _ptr(out), _stream(dev))
+        if kind == "reaction_network":
+            fn, net = _sde_entry(lib, "log_weights", kind, network)
+            _call(fn, net, *dims, *tail, _ptr(out), _stream(dev))
+        else:
+            _call(lib.vsde_log_weights, ctypes.c_int(0 if kind is None else SDE_KINDS[kind]), *dims, _ptr(drift), _ptr(diffusion),
+                  *tail, _ptr(out), _stream(dev))
     return out
 
 
@@ -448,7 +495,7 @@ def log_weight_accumulate(log_w, n: int, state) -> None:
         _call(lib.vsde_log_weight_accumulate, ctypes.c_int(n), _ptr(log_w), _ptr(state), _stream(dev))
 
 
-def sde_coefficients_fwd(kind: str, x, theta):
+def sde_coefficients_fwd(kind: str, x, theta, network=None):
     """(drift [B,T,S], diffusion [B,T,S,S]) of a built-in SDE on the first T points of every path x [B, T+1, S]."""
     lib = load()
     dev = _require_hip(x, theta)
@@ -458,12 +505,12 @@ def sde_coefficients_fwd(kind: str, x, theta):
     with torch.cuda.device(dev):
         drift = torch.empty(B, T, S, device=dev, dtype=torch.float32)
         diffusion = torch.empty(B, T, S, S, device=dev, dtype=torch.float32)
-        _call(lib.vsde_sde_coefficients_fwd, ctypes.c_int(SDE_KINDS[kind]), ctypes.c_int(B), ctypes.c_int(T), ctypes.c_int(S),
+        _call(*_sde_entry(lib, "sde_coefficients_fwd", kind, network), ctypes.c_int(B), ctypes.c_int(T), ctypes.c_int(S),
               ctypes.c_int(theta.shape[1]), _ptr(x), _ptr(theta), _ptr(drift), _ptr(diffusion), _stream(dev))
     return drift, diffusion
 
 
-def sde_coefficients_bwd(kind: str, x, theta, g_drift, g_diffusion):
+def sde_coefficients_bwd(kind: str, x, theta, g_drift, g_diffusion, network=None):
     """(g_x [B,T+1,S], g_theta [B,P]) of ``sde_coefficients_fwd``."""
     lib = load()
     dev = _require_hip(x, theta, g_drift, g_diffusion)
@@ -472,7 +519,7 @@ def sde_coefficients_bwd(kind: str, x, theta, g_drift, g_diffusion):
     with torch.cuda.device(dev):
         g_x = torch.empty_like(x)
         g_theta = torch.empty_like(theta)
-        _call(lib.vsde_sde_coefficients_bwd, ctypes.c_int(SDE_KINDS[kind]), ctypes.c_int(B), ctypes.c_int(T1 - 1), ctypes.c_int(S),
+        _call(*_sde_entry(lib, "sde_coefficients_bwd", kind, network), ctypes.c_int(B), ctypes.c_int(T1 - 1), ctypes.c_int(S),
               ctypes.c_int(theta.shape[1]), _ptr(x), _ptr(theta), _ptr(g_drift), _ptr(g_diffusion), _ptr(g_x), _ptr(g_theta),
               _stream(dev))
     return g_x, g_theta

@@ -2,7 +2,7 @@
 pre-training stage.
 
 SDEs whose drift / diffusion are built into the HIP library (``sde.builtin_kind`` in ``_hip.SDE_KINDS``: the example
-Ornstein-Uhlenbeck and Lotka-Volterra models and the benchmark's linear-diagonal one) run as ONE kernel forward and ONE
+Ornstein-Uhlenbeck and Lotka-Volterra models, the benchmark's linear-diagonal one and reaction networks) run as ONE kernel forward and ONE
 backward (csrc/vsde_sde.hip: a thread per path, the time loop in the kernel) when the tensors live on the GPU; any other
 SDE -- the user's drift / diffusion are Python callables -- takes the torch loop below, which is also the specification."""
 from __future__ import annotations
@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from .sde import SDE, builtin_sde_kind
+from .sde import SDE, builtin_sde_route
 
 
 def euler_maruyama(sde: SDE, x0: Tensor, theta: Tensor, time_horizon: float, dt: float,
@@ -28,11 +28,11 @@ def euler_maruyama(sde: SDE, x0: Tensor, theta: Tensor, time_horizon: float, dt:
     if noise is None:
         noise = torch.randn(batch, n_steps, state_dim, device=x0.device, dtype=x0.dtype)
     pos = list(positive_dims)
-    kind = builtin_sde_kind(sde)
+    kind, network = builtin_sde_route(sde)
     if kind is not None and x0.is_cuda and x0.dtype == torch.float32 and HIP_SIMULATOR:
         from .. import _hip
         if kind in _hip.SDE_KINDS and noise.shape == (batch, n_steps, state_dim):
-            return _BuiltinEulerMaruyama.apply(x0, theta, noise, kind, float(dt), tuple(pos))
+            return _BuiltinEulerMaruyama.apply(x0, theta, noise, kind, float(dt), tuple(pos), network)
     root_dt = dt ** 0.5
     states = [x0]
     x = x0
@@ -53,12 +53,12 @@ class _BuiltinEulerMaruyama(torch.autograd.Function):
     """Trajectory of a built-in SDE through the HIP simulator; differentiable in theta and x0 (noise is a constant)."""
 
     @staticmethod
-    def forward(ctx, x0, theta, noise, kind, dt, pos):
+    def forward(ctx, x0, theta, noise, kind, dt, pos, network):
         from .. import _hip
         theta_c, noise_c = theta.detach().float().contiguous(), noise.detach().float().contiguous()
-        traj = _hip.euler_maruyama_fwd(kind, x0.detach(), theta_c, noise_c, dt, pos)
+        traj = _hip.euler_maruyama_fwd(kind, x0.detach(), theta_c, noise_c, dt, pos, network=network)
         ctx.save_for_backward(theta_c, noise_c, traj)
-        ctx.meta = (kind, dt, pos, theta.dtype)
+        ctx.meta = (kind, dt, pos, theta.dtype, network)
         return traj
 
     @staticmethod
@@ -66,9 +66,9 @@ class _BuiltinEulerMaruyama(torch.autograd.Function):
     def backward(ctx, g_traj):
         from .. import _hip
         theta, noise, traj = ctx.saved_tensors
-        kind, dt, pos, tdtype = ctx.meta
-        g_x0, g_theta = _hip.euler_maruyama_bwd(kind, theta, noise, traj, g_traj.contiguous(), dt, pos)
-        return g_x0, g_theta.to(tdtype), None, None, None, None
+        kind, dt, pos, tdtype, network = ctx.meta
+        g_x0, g_theta = _hip.euler_maruyama_bwd(kind, theta, noise, traj, g_traj.contiguous(), dt, pos, network=network)
+        return g_x0, g_theta.to(tdtype), None, None, None, None, None
 
 
 _FLOORS: dict = {}

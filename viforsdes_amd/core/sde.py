@@ -48,7 +48,8 @@ def builtin_sde_kind(sde: object) -> str | None:
     ``builtin_kind`` is a class attribute of the example SDEs and is therefore inherited: a subclass that overrides
     ``drift`` or ``diffusion`` (or an instance that shadows them) must NOT be routed to the built-in kernels, which would
     silently ignore the override.  The dispatch holds only if both callables still resolve to the functions of the class
-    that declared ``builtin_kind``, and the dimensions are inside what the kernels accept (linear-diagonal: state_dim <= 32)."""
+    that declared ``builtin_kind``, and the dimensions are inside what the kernels accept (linear-diagonal: state_dim <= 32;
+    reaction network: S <= 8 species, R <= 16 reactions, orders <= 3)."""
     cls = type(sde)
     owner = next((c for c in cls.__mro__ if "builtin_kind" in vars(c)), None)
     if owner is None or "builtin_kind" in getattr(sde, "__dict__", {}):
@@ -59,4 +60,14 @@ def builtin_sde_kind(sde: object) -> str | None:
             return None
     if kind == "linear_diagonal" and not (1 <= int(getattr(sde, "state_dim", 0)) <= 32):
         return None
+    if kind == "reaction_network" and not sde.kernel_compatible():
+        return None
     return kind
+
+
+def builtin_sde_route(sde: object) -> tuple[str | None, object]:
+    """``(kind, network)``: the HIP library's name for ``sde`` (``builtin_sde_kind``) and, for a reaction network, its C-ABI
+    descriptor (``_hip.CrnNetwork``; None for the other kinds).  Every GPU route -- ELBO coefficients, simulator, forecast,
+    log-weights -- picks its kernels from this pair."""
+    kind = builtin_sde_kind(sde)
+    return kind, (sde.network_descriptor() if kind == "reaction_network" else None)

@@ -349,7 +349,7 @@ static int tail_fill(TailParams &p, int B, int K, int S, int O, int P, const flo
 // Importance log-weights of posterior draws (VariationalPosterior.log_evidence): the ELBO integrand of one sample,
 //   log w_b = obs_b + sum_t (sde_t - gen_t + jac_t) + prior_b - post_b,
 // in one pass over the path.  One workgroup per path, threads striding over t as in elbo_path_terms_kernel; x = softplus(z) on
-// the positive state dims and, for the built-in kinds 1..3, drift / diffusion are evaluated in registers (the [B,T,S] /
+// the positive state dims and, for the built-in kinds 1..4, drift / diffusion are evaluated in registers (the [B,T,S] /
 // [B,T,S,S] coefficient tensors are never written); kind 0 reads the drift / diffusion the caller evaluated.  Each step's
 // three terms are summed before the sum over t (no cancellation of two large sums); the sum over t is a fixed tree, and thread
 // 0 adds the observation / prior / posterior terms through tail_terms, the per-sample body of the ELBO tail.
@@ -361,6 +361,7 @@ struct LogWeightParams {
     uint32_t state_pos;
     float dt, sqdt;
     float *log_w;              // [B]
+    CrnNet net;                // kind 4
 };
 
 // the state of path b at its observed grid points: softplus(z) on the positive dims
@@ -374,13 +375,13 @@ template <int S> struct XObsLatent {
     }
 };
 
-template <int KIND, int S>
+template <int KIND, int S, int NR = EmDims<KIND>::P>
 __global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p) {
-    constexpr int PK = KIND == 3 ? 2 * S : 3;
+    constexpr int PK = KIND == 3 ? 2 * S : KIND == 4 ? NR : 3;
     const int b = blockIdx.x;
     float th[PK];
 #pragma unroll
-    for (int i = 0; i < PK; ++i) th[i] = KIND == 0 ? 0.f : p.tail.theta[(int64_t)b * p.tail.P + i];
+    for (int i = 0; i < PK; ++i) th[i] = (KIND == 0 || (KIND == 4 && i >= p.tail.P)) ? 0.f : p.tail.theta[(int64_t)b * p.tail.P + i];
     float acc = 0.f;
     for (int t = threadIdx.x; t < p.T; t += blockDim.x) {
         const int64_t o1 = ((int64_t)b * (p.T + 1) + t) * S, o2 = ((int64_t)b * p.T + t) * S;
@@ -407,7 +408,8 @@ __global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p) {
             sde = -0.5f * ((float)S * kLog2Pi + quad) - logdet;
         } else {
             float f[S], G[S * S];
-            coef_fwd<KIND>(x0, th, f, G);
+            if constexpr (KIND == 4) crn_coef<S, NR>(p.net, x0, th, f, G);
+            else coef_fwd<KIND>(x0, th, f, G);
             sde = tri_logpdf<S>(x1, x0, f, G, p.dt, p.sqdt, w);
         }
         const float gen = tri_logpdf<S>(z1, z0, p.means + o2, p.chol + o2 * S, p.dt, p.sqdt, w);
@@ -430,8 +432,8 @@ __global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p) {
     }
 }
 
-template <int KIND, int S> static int launch_log_weights(const LogWeightParams &p, hipStream_t s) {
-    hipLaunchKernelGGL((log_weight_kernel<KIND, S>), dim3(p.tail.B), dim3(256), 0, s, p);
+template <int KIND, int S, int NR = EmDims<KIND>::P> static int launch_log_weights(const LogWeightParams &p, hipStream_t s) {
+    hipLaunchKernelGGL((log_weight_kernel<KIND, S, NR>), dim3(p.tail.B), dim3(256), 0, s, p);
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -610,4 +612,26 @@ extern "C" int vsde_log_weight_accumulate(int n, const float *log_w, double *sta
     hipLaunchKernelGGL(log_weight_accumulate_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n, log_w, state6);
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int vsde_crn_log_weights(const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z,
+                                    const float *means, const float *chol, const float *theta, const int *obs_rows,
+                                    const float *obs_values, const float *obs_matrix, double variance, int prior_type,
+                                    double prior_mean, double prior_std, const float *post_mean, const float *post_log_std,
+                                    const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host,
+                                    double time_step, float *log_w, void *stream) {
+    LogWeightParams p = {};
+    int rc = crn_net(net, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0 && K >= 0, VSDE_E_BADARG, "bad log-weight dims B=%d T=%d S=%d K=%d", B, T, S, K);
+    VSDE_CHECK_ARG(z && means && chol && log_w && (K == 0 || obs_rows) && time_step > 0, VSDE_E_BADARG,
+                   "NULL argument / bad time_step");
+    rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
+                   post_mean, post_log_std, theta_positive_mask_host, z, z, z);
+    if (rc) return rc;
+    p.T = T; p.z = z; p.means = means; p.chol = chol; p.obs_rows = obs_rows;
+    p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
+    return crn_dispatch(S, P, [&](auto ns, auto nr) {
+        return launch_log_weights<4, decltype(ns)::value, decltype(nr)::value>(p, (hipStream_t)stream);
+    });
 }

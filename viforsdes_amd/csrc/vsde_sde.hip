@@ -4,6 +4,7 @@
 //   kind 1  Ornstein-Uhlenbeck  (examples/ornstein_uhlenbeck.py:18-30)   f = kappa (mu - x),   G = sigma
 //   kind 2  Lotka-Volterra      (examples/lotka_volterra.py:18-46)       analytic 2x2 Cholesky factor, three clamp(min=1e-6)
 //   kind 3  linear / diagonal   (BASELINE config 5)                       f = -a x, G = diag(softplus(b) + 1e-3)
+//   kind 4  reaction network    (core/reaction_network.py)                S species (template, <= 8), R <= 16 reactions
 // One thread per sample path, the time loop inside the kernel, x_t in registers.  HBM-bound streaming (noise read once,
 // trajectory written once; the backward reads noise, trajectory and the upstream gradient once): a path's records are
 // contiguous over time, so the 64 paths of a workgroup move CH steps at a time through LDS as coalesced row segments.
@@ -14,7 +15,9 @@
 namespace vsde {
 
 constexpr int kEmPaths = 64;   // paths per workgroup (one wavefront)
-constexpr int kEmChunk = 32;   // time steps staged per LDS round
+constexpr int kEmChunk = 32;   // time steps staged per LDS round (S <= 2)
+// steps per LDS round at S dims: the backward stages three [64][(CH+1) S + 1] float buffers, 53 KiB at S = 4 and 56 KiB at S = 8
+constexpr int em_chunk(int S) { return S <= 2 ? kEmChunk : S <= 4 ? 16 : 8; }
 
 struct EmParams {
     int B, T, S, P;
@@ -22,6 +25,7 @@ struct EmParams {
     float *traj, *g_x0, *g_theta;
     uint32_t pos_mask;
     float dt, sqdt;
+    CrnNet net;    // kind 4
 };
 
 // y = x + f dt + (G eps) sqrt(dt)
@@ -85,10 +89,18 @@ __device__ __forceinline__ void em_rows(float *s, int sstride, float *g, int64_t
         }
 }
 
-// kinds 1, 2: thread = path
-template <int KIND>
+// row b of theta [B][np] into th [P] (kind 4: np = R <= P at run time, the rest 1)
+template <int KIND, int P>
+__device__ __forceinline__ void em_load_theta(float *th, const float *theta, int b, int np, bool valid) {
+    if constexpr (KIND != 4) np = P;
+#pragma unroll
+    for (int k = 0; k < P; ++k) th[k] = (valid && k < np) ? theta[(int64_t)b * np + k] : 1.f;
+}
+
+// kinds 1, 2, 4: thread = path
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
 __global__ void __launch_bounds__(kEmPaths) em_fwd_kernel(EmParams p) {
-    constexpr int S = EmDims<KIND>::S, P = EmDims<KIND>::P, RS = kEmChunk * S + 1;
+    constexpr int S = NS, P = NR, CH = em_chunk(S), RS = CH * S + 1;
     __shared__ float noise_s[kEmPaths * RS], traj_s[kEmPaths * RS];
     const int lane = threadIdx.x, b0 = blockIdx.x * kEmPaths, b = b0 + lane;
     const int rows = min(kEmPaths, p.B - b0);
@@ -96,18 +108,18 @@ __global__ void __launch_bounds__(kEmPaths) em_fwd_kernel(EmParams p) {
     float x[S], th[P];
 #pragma unroll
     for (int i = 0; i < S; ++i) x[i] = valid ? p.x0[(int64_t)b * S + i] : 1.f;
-#pragma unroll
-    for (int k = 0; k < P; ++k) th[k] = valid ? p.theta[(int64_t)b * P + k] : 1.f;
+    em_load_theta<KIND, P>(th, p.theta, b, p.P, valid);
     if (valid)
 #pragma unroll
         for (int i = 0; i < S; ++i) p.traj[(int64_t)b * (p.T + 1) * S + i] = x[i];
-    for (int t0 = 0; t0 < p.T; t0 += kEmChunk) {
-        const int n = min(kEmChunk, p.T - t0);
+    for (int t0 = 0; t0 < p.T; t0 += CH) {
+        const int n = min(CH, p.T - t0);
         em_rows<true>(noise_s, RS, const_cast<float *>(p.noise) + ((int64_t)b0 * p.T + t0) * S, (int64_t)p.T * S, n * S, rows, lane);
         __syncthreads();
         for (int k = 0; k < n; ++k) {
             float y[S];
-            em_step<KIND>(x, th, noise_s + lane * RS + k * S, p.dt, p.sqdt, y);
+            if constexpr (KIND == 4) crn_em_step<S, NR>(p.net, x, th, noise_s + lane * RS + k * S, p.dt, p.sqdt, y);
+            else em_step<KIND>(x, th, noise_s + lane * RS + k * S, p.dt, p.sqdt, y);
 #pragma unroll
             for (int i = 0; i < S; ++i) {
                 x[i] = ((p.pos_mask >> i) & 1u) ? floor_nan(y[i]) : y[i];
@@ -120,9 +132,9 @@ __global__ void __launch_bounds__(kEmPaths) em_fwd_kernel(EmParams p) {
     }
 }
 
-template <int KIND>
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
 __global__ void __launch_bounds__(kEmPaths) em_bwd_kernel(EmParams p) {
-    constexpr int S = EmDims<KIND>::S, P = EmDims<KIND>::P, RS = (kEmChunk + 1) * S + 1;
+    constexpr int S = NS, P = NR, CH = em_chunk(S), RS = (CH + 1) * S + 1;
     __shared__ float noise_s[kEmPaths * RS], traj_s[kEmPaths * RS], g_s[kEmPaths * RS];
     const int lane = threadIdx.x, b0 = blockIdx.x * kEmPaths, b = b0 + lane;
     const int rows = min(kEmPaths, p.B - b0);
@@ -130,11 +142,12 @@ __global__ void __launch_bounds__(kEmPaths) em_bwd_kernel(EmParams p) {
     float a[S], th[P], gth[P];
 #pragma unroll
     for (int i = 0; i < S; ++i) a[i] = 0.f;
+    em_load_theta<KIND, P>(th, p.theta, b, p.P, valid);
 #pragma unroll
-    for (int k = 0; k < P; ++k) { th[k] = valid ? p.theta[(int64_t)b * P + k] : 1.f; gth[k] = 0.f; }
-    const int nchunks = (p.T + kEmChunk - 1) / kEmChunk;
+    for (int k = 0; k < P; ++k) gth[k] = 0.f;
+    const int nchunks = (p.T + CH - 1) / CH;
     for (int c = nchunks - 1; c >= 0; --c) {
-        const int t0 = c * kEmChunk, n = min(kEmChunk, p.T - t0);
+        const int t0 = c * CH, n = min(CH, p.T - t0);
         em_rows<true>(noise_s, RS, const_cast<float *>(p.noise) + ((int64_t)b0 * p.T + t0) * S, (int64_t)p.T * S, n * S, rows, lane);
         em_rows<true>(traj_s, RS, const_cast<float *>(p.traj_in) + ((int64_t)b0 * (p.T + 1) + t0) * S, (int64_t)(p.T + 1) * S,
                       (n + 1) * S, rows, lane);                                             // x_{t0} .. x_{t0+n}
@@ -149,7 +162,8 @@ __global__ void __launch_bounds__(kEmPaths) em_bwd_kernel(EmParams p) {
                 if (((p.pos_mask >> i) & 1u) && xs[S + i] == kEmFloor) a[i] = 0.f;          // clamped entry: no gradient
             }
             float ax[S];
-            em_step_bwd<KIND>(xs, th, noise_s + lane * RS + k * S, a, p.dt, p.sqdt, ax, gth);
+            if constexpr (KIND == 4) crn_em_step_bwd<S, NR>(p.net, xs, th, noise_s + lane * RS + k * S, a, p.dt, p.sqdt, ax, gth);
+            else em_step_bwd<KIND>(xs, th, noise_s + lane * RS + k * S, a, p.dt, p.sqdt, ax, gth);
 #pragma unroll
             for (int i = 0; i < S; ++i) a[i] = ax[i];
         }
@@ -158,8 +172,10 @@ __global__ void __launch_bounds__(kEmPaths) em_bwd_kernel(EmParams p) {
     if (valid) {
 #pragma unroll
         for (int i = 0; i < S; ++i) p.g_x0[(int64_t)b * S + i] = a[i] + p.g_traj[(int64_t)b * (p.T + 1) * S + i];
+        const int np = KIND == 4 ? p.P : P;
 #pragma unroll
-        for (int k = 0; k < P; ++k) p.g_theta[(int64_t)b * P + k] = gth[k];
+        for (int k = 0; k < P; ++k)
+            if (k < np) p.g_theta[(int64_t)b * np + k] = gth[k];
     }
 }
 
@@ -217,6 +233,7 @@ struct FcParams {
     float *out;
     uint32_t pos_mask;
     float dt, sqdt;
+    CrnNet net;    // kind 4
 };
 
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
@@ -246,13 +263,13 @@ __device__ __forceinline__ void fc_normals(uint32_t blk, uint32_t i, uint32_t b,
     box_muller(w.z, w.w, z[2], z[3]);
 }
 
-// kinds 1, 2: thread = path (S = 1, 2 dims per thread); kind 3: thread = (path, dim), one dim per thread.  A block of 4 steps
+// kinds 1, 2, 4: thread = path (all S dims per thread); kind 3: thread = (path, dim), one dim per thread.  A block of 4 steps
 // is branch-free: the Philox / Box-Muller work of the NEXT block depends on no state, so it sits in the same basic block as the
 // 4-step serial chain and the scheduler interleaves the two.  Output rows are written after the block from the 4 kept states
 // (out_steps is the same for every thread: the write loop is uniform).  Steps that never come (out_steps above T) read NaN.
-template <int KIND>
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
 __global__ void __launch_bounds__(256) forecast_kernel(FcParams p) {
-    constexpr int S = EmDims<KIND>::S, P = EmDims<KIND>::P;
+    constexpr int S = NS, P = NR;
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int b, d0, rs;                          // path, first state dim of this thread, row stride of x_start / out
     if constexpr (KIND == 3) {
@@ -273,8 +290,7 @@ __global__ void __launch_bounds__(256) forecast_kernel(FcParams p) {
     if constexpr (KIND == 3) {
         th[0] = p.theta[(int64_t)b * p.P + d0]; th[1] = p.theta[(int64_t)b * p.P + p.S + d0];
     } else {
-#pragma unroll
-        for (int k = 0; k < P; ++k) th[k] = p.theta[(int64_t)b * P + k];
+        em_load_theta<KIND, P>(th, p.theta, b, p.P, true);
     }
     float *o = p.out + (int64_t)b * p.K * rs + d0;
     int k = 0, next = p.steps[0];
@@ -295,13 +311,23 @@ __global__ void __launch_bounds__(256) forecast_kernel(FcParams p) {
             float e[S], y[S];
 #pragma unroll
             for (int i = 0; i < S; ++i) e[i] = z[i][j];
-            em_step<KIND>(x, th, e, p.dt, p.sqdt, y);
+            if constexpr (KIND == 4) crn_em_step<S, NR>(p.net, x, th, e, p.dt, p.sqdt, y);
+            else em_step<KIND>(x, th, e, p.dt, p.sqdt, y);
 #pragma unroll
             for (int i = 0; i < S; ++i) xs[j][i] = x[i] = pos[i] ? floor_nan(y[i]) : y[i];
+            if constexpr (KIND == 4) {
+                // kind 4 writes its rows as the states are made: at S = 8 the [4][S] staging would push the kernel into scratch
+                const int t = 4 * blk + j + 1;
+                while (k < p.K && next <= t && t <= p.T) {
+#pragma unroll
+                    for (int i = 0; i < S; ++i) o[(int64_t)k * rs + i] = x[i];
+                    if (++k < p.K) next = p.steps[k];
+                }
+            }
         }
         // steps past T in the last block are computed and never written: rows are written for out_steps <= t1 only
         const int t1 = min(4 * blk + 4, p.T);
-        while (k < p.K && next <= t1) {
+        while (KIND != 4 && k < p.K && next <= t1) {
             const int j = max(next - 4 * blk - 1, 0);
 #pragma unroll
             for (int i = 0; i < S; ++i)
@@ -326,6 +352,7 @@ struct CoefParams {
     int B, T, S, P;
     const float *x, *theta, *g_drift, *g_diff;
     float *drift, *diff, *g_x, *g_theta;
+    CrnNet net;    // kind 4
 };
 
 // coef_fwd<KIND> (vsde_sde_coef.h) and its vector-Jacobian product
@@ -355,18 +382,18 @@ __device__ __forceinline__ void coef_bwd(const float *x, const float *th, const 
 }
 
 // thread = grid point (b, t)
-template <int KIND>
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
 __global__ void __launch_bounds__(256) coef_fwd_kernel(CoefParams p) {
-    constexpr int S = EmDims<KIND>::S, P = EmDims<KIND>::P;
+    constexpr int S = NS, P = NR;
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= (int64_t)p.B * p.T) return;
     const int b = (int)(q / p.T), t = (int)(q % p.T);
     float x[S], th[P], f[S], G[S * S];
 #pragma unroll
     for (int i = 0; i < S; ++i) x[i] = p.x[((int64_t)b * (p.T + 1) + t) * S + i];
-#pragma unroll
-    for (int i = 0; i < P; ++i) th[i] = p.theta[(int64_t)b * P + i];
-    coef_fwd<KIND>(x, th, f, G);
+    em_load_theta<KIND, P>(th, p.theta, b, p.P, true);
+    if constexpr (KIND == 4) crn_coef<S, NR>(p.net, x, th, f, G);
+    else coef_fwd<KIND>(x, th, f, G);
 #pragma unroll
     for (int i = 0; i < S; ++i) p.drift[q * S + i] = f[i];
 #pragma unroll
@@ -374,14 +401,15 @@ __global__ void __launch_bounds__(256) coef_fwd_kernel(CoefParams p) {
 }
 
 // workgroup = path: threads walk the time steps, the theta gradient is reduced through LDS in a fixed tree
-template <int KIND>
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
 __global__ void __launch_bounds__(256) coef_bwd_kernel(CoefParams p) {
-    constexpr int S = EmDims<KIND>::S, P = EmDims<KIND>::P;
+    constexpr int S = NS, P = NR;
     __shared__ float red[256][P + 1];
     const int b = blockIdx.x, tid = threadIdx.x;
     float th[P], gth[P];
+    em_load_theta<KIND, P>(th, p.theta, b, p.P, true);
 #pragma unroll
-    for (int i = 0; i < P; ++i) { th[i] = p.theta[(int64_t)b * P + i]; gth[i] = 0.f; }
+    for (int i = 0; i < P; ++i) gth[i] = 0.f;
     for (int t = tid; t <= p.T; t += 256) {
         float gx[S];
         if (t < p.T) {
@@ -391,7 +419,8 @@ __global__ void __launch_bounds__(256) coef_bwd_kernel(CoefParams p) {
             for (int i = 0; i < S; ++i) { x[i] = p.x[((int64_t)b * (p.T + 1) + t) * S + i]; gf[i] = p.g_drift[q * S + i]; }
 #pragma unroll
             for (int i = 0; i < S * S; ++i) gG[i] = p.g_diff[q * S * S + i];
-            coef_bwd<KIND>(x, th, gf, gG, gx, gth);
+            if constexpr (KIND == 4) crn_coef_bwd<S, NR>(p.net, x, th, gf, gG, gx, gth);
+            else coef_bwd<KIND>(x, th, gf, gG, gx, gth);
         } else {
 #pragma unroll
             for (int i = 0; i < S; ++i) gx[i] = 0.f;
@@ -408,7 +437,8 @@ __global__ void __launch_bounds__(256) coef_bwd_kernel(CoefParams p) {
             for (int i = 0; i < P; ++i) red[tid][i] += red[tid + w][i];
         __syncthreads();
     }
-    if (tid < P) p.g_theta[(int64_t)b * P + tid] = red[0][tid];
+    const int np = KIND == 4 ? p.P : P;
+    if (tid < np) p.g_theta[(int64_t)b * np + tid] = red[0][tid];
 }
 
 // kind 3 (f_i = -a_i x_i, G = diag(softplus(b_i) + 1e-3)): thread = (b, t, i) forward; workgroup = path backward with the threads
@@ -560,4 +590,97 @@ extern "C" int vsde_sde_coefficients_bwd(int kind, int B, int T, int S, int P, c
     else hipLaunchKernelGGL(coef_diag_bwd_kernel, dim3(B), dim3(256), 0, s, p);
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Kind 4: reaction networks (include/vsde_hip.h: vsde_crn_network).  The descriptor is checked and copied into the kernel
+// arguments here, before any HIP call.
+
+extern "C" int vsde_crn_euler_maruyama_fwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *x0,
+                                           const float *theta, const float *noise, double time_step,
+                                           const uint8_t *positive_mask_host, float *traj, void *stream) {
+    EmParams p = {};
+    int rc = crn_net(net, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad Euler-Maruyama dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(x0 && theta && noise && traj && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.x0 = x0; p.theta = theta; p.noise = noise; p.traj = traj;
+    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+    return crn_dispatch(S, P, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((em_fwd_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0,
+                           (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int vsde_crn_euler_maruyama_bwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *theta,
+                                           const float *noise, const float *traj, const float *g_traj, double time_step,
+                                           const uint8_t *positive_mask_host, float *g_x0, float *g_theta, void *stream) {
+    EmParams p = {};
+    int rc = crn_net(net, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad Euler-Maruyama dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(theta && noise && traj && g_traj && g_x0 && g_theta && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.theta = theta; p.noise = noise; p.traj_in = traj; p.g_traj = g_traj;
+    p.g_x0 = g_x0; p.g_theta = g_theta;
+    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+    return crn_dispatch(S, P, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((em_bwd_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0,
+                           (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int vsde_crn_forecast(const vsde_crn_network *net, int B, int T, int S, int P, int K, const float *x_start,
+                                 const float *theta, const int *out_steps, const uint32_t *key, double time_step,
+                                 const uint8_t *positive_mask_host, float *out, void *stream) {
+    FcParams p = {};
+    int rc = crn_net(net, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad forecast dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(K > 0, VSDE_E_BADARG, "bad forecast output count K=%d", K);
+    VSDE_CHECK_ARG(x_start && theta && out_steps && key && out && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.K = K; p.x0 = x_start; p.theta = theta; p.steps = out_steps; p.key = key; p.out = out;
+    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+    return crn_dispatch(S, P, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((forecast_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0,
+                           (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int vsde_crn_sde_coefficients_fwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *x,
+                                             const float *theta, float *drift, float *diffusion, void *stream) {
+    CoefParams p = {};
+    int rc = crn_net(net, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad coefficient dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(x && theta && drift && diffusion, VSDE_E_BADARG, "NULL argument");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = theta; p.drift = drift; p.diff = diffusion;
+    return crn_dispatch(S, P, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((coef_fwd_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3((unsigned)(((int64_t)B * T + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int vsde_crn_sde_coefficients_bwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *x,
+                                             const float *theta, const float *g_drift, const float *g_diffusion, float *g_x,
+                                             float *g_theta, void *stream) {
+    CoefParams p = {};
+    int rc = crn_net(net, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad coefficient dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(x && theta && g_drift && g_diffusion && g_x && g_theta, VSDE_E_BADARG, "NULL argument");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = theta; p.g_drift = g_drift; p.g_diff = g_diffusion;
+    p.g_x = g_x; p.g_theta = g_theta;
+    return crn_dispatch(S, P, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((coef_bwd_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3(B), dim3(256), 0, (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
 }

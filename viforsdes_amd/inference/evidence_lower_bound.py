@@ -16,7 +16,7 @@ from torch.autograd.function import once_differentiable
 
 from ..core.observations import ObservationLikelihood, Observations, grid_index
 from ..core.priors import Prior
-from ..core.sde import SDE, builtin_sde_kind
+from ..core.sde import SDE, builtin_sde_route
 from ..kernels.backend import get_backend
 from ..models.sde_parameter_posterior import SDEParameterPosterior
 from .types import DiffusionPathSample, EvidenceLowerBoundComponents, EvidenceLowerBoundResult
@@ -50,31 +50,31 @@ class _BuiltinCoefficients(torch.autograd.Function):
     (csrc/vsde_sde.hip) instead of the ~100 tiny kernels the Python callables and their autograd graph expand to."""
 
     @staticmethod
-    def forward(ctx, x, theta, kind):
+    def forward(ctx, x, theta, kind, network):
         from .. import _hip
         xc, tc = x.detach().float().contiguous(), theta.detach().float().contiguous()
         ctx.save_for_backward(xc, tc)
-        ctx.meta = (kind, x.dtype, theta.dtype)
-        return _hip.sde_coefficients_fwd(kind, xc, tc)
+        ctx.meta = (kind, network, x.dtype, theta.dtype)
+        return _hip.sde_coefficients_fwd(kind, xc, tc, network=network)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_drift, g_diffusion):
         from .. import _hip
-        kind, xdtype, tdtype = ctx.meta
+        kind, network, xdtype, tdtype = ctx.meta
         g_x, g_theta = _hip.sde_coefficients_bwd(kind, *ctx.saved_tensors, g_drift.float().contiguous(),
-                                                 g_diffusion.float().contiguous())
-        return g_x.to(xdtype), g_theta.to(tdtype), None
+                                                 g_diffusion.float().contiguous(), network=network)
+        return g_x.to(xdtype), g_theta.to(tdtype), None, None
 
 
 def sde_coefficients(sde: SDE, x: Tensor, sde_parameters: Tensor) -> tuple[Tensor, Tensor]:
     """Drift ``[B,T,S]`` and diffusion ``[B,T,S,S]`` on the first T grid points of ``x [B,T+1,S]`` (reference lines 37-40)."""
     B, n_steps, S = x.shape[0], x.shape[1] - 1, x.shape[2]
-    kind = builtin_sde_kind(sde)
+    kind, network = builtin_sde_route(sde)
     if kind is not None and HIP_COEFFICIENTS and x.is_cuda and x.dtype == torch.float32:
         from .. import _hip
         if kind in _hip.SDE_KINDS:
-            return _BuiltinCoefficients.apply(x, sde_parameters, kind)
+            return _BuiltinCoefficients.apply(x, sde_parameters, kind, network)
     x_flat = x[:, :-1].reshape(B * n_steps, S)
     theta_flat = sde_parameters.unsqueeze(1).expand(B, n_steps, -1).reshape(B * n_steps, -1)
     return (sde.drift(x_flat, theta_flat).reshape(B, n_steps, S),
