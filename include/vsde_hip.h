@@ -515,6 +515,51 @@ int vsde_crn_log_weights(const vsde_crn_network *net, int B, int T, int S, int K
                          const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host,
                          const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
 
+/* Rate laws of a reaction network (ReactionNetworkSDE(rate_laws=..., rate_constants=...)).  Reaction j follows law[j]:
+ *   VSDE_CRN_LAW_MASS_ACTION      h_j = k_j prod_i x_i^r_ji                     (modifier / hill_n ignored)
+ *   VSDE_CRN_LAW_HILL_ACTIVATION  h_j = k_j u^n / (K_j^n + u^n)
+ *   VSDE_CRN_LAW_HILL_REPRESSION  h_j = k_j K_j^n / (K_j^n + u^n)
+ * with u = max(x_s, 0) of the modifier species s = modifier[j] (torch.clamp semantics: NaN propagates, the gradient reaches x_s
+ * where x_s >= 0) and n = hill_n[j] in 1..4; powers by repeated multiplication.  The reactant row of a rate-law reaction sets
+ * its net change only.  Drift, covariance and diffusion are built from the h_j as for vsde_crn_network.  The vsde_crn_kinetic_*
+ * entry points take, in place of theta, the effective constants rates[B][2R] = (k_0 .. k_{R-1}, K_0 .. K_{R-1}) (so P = 2R;
+ * K_j is ignored for mass-action reactions), and the network and rate-law descriptors (HOST memory, copied into the kernel
+ * arguments: capturable).  They return VSDE_E_BADARG before any HIP call for a bad network descriptor, a law code outside
+ * 0..2, a modifier outside 0..S-1 or a Hill coefficient outside 1..4 on a rate-law reaction, or P != 2R.  Entries of rows
+ * >= R are ignored. */
+#define VSDE_CRN_LAW_MASS_ACTION 0
+#define VSDE_CRN_LAW_HILL_ACTIVATION 1
+#define VSDE_CRN_LAW_HILL_REPRESSION 2
+#define VSDE_CRN_MAX_HILL 4
+typedef struct vsde_crn_kinetics {
+    int8_t law[VSDE_CRN_MAX_REACTIONS];       /* VSDE_CRN_LAW_*                        */
+    int8_t modifier[VSDE_CRN_MAX_REACTIONS];  /* modifier species s_j of a rate law     */
+    int8_t hill_n[VSDE_CRN_MAX_REACTIONS];    /* Hill coefficient n_j of a rate law     */
+} vsde_crn_kinetics;
+int vsde_crn_kinetic_sde_coefficients_fwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int P,
+                                          const float *x, const float *rates, float *drift, float *diffusion, void *stream);
+int vsde_crn_kinetic_sde_coefficients_bwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int P,
+                                          const float *x, const float *rates, const float *g_drift, const float *g_diffusion,
+                                          float *g_x, float *g_rates, void *stream);
+int vsde_crn_kinetic_euler_maruyama_fwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int P,
+                                        const float *x0, const float *rates, const float *noise, double time_step,
+                                        const uint8_t *positive_mask_host, float *traj, void *stream);
+int vsde_crn_kinetic_euler_maruyama_bwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int P,
+                                        const float *rates, const float *noise, const float *traj, const float *g_traj,
+                                        double time_step, const uint8_t *positive_mask_host, float *g_x0, float *g_rates,
+                                        void *stream);
+int vsde_crn_kinetic_forecast(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int P, int K,
+                              const float *x_start, const float *rates, const int *out_steps, const uint32_t *key,
+                              double time_step, const uint8_t *positive_mask_host, float *out, void *stream);
+/* P here is the width of theta [B][P] (the prior / posterior terms); R_eff = 2R is the width of rates [B][2R] (the drift and
+ * diffusion). */
+int vsde_crn_kinetic_log_weights(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K, int O,
+                                 int P, int R_eff, const float *z, const float *means, const float *chol, const float *theta,
+                                 const float *rates, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                 double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean,
+                                 const float *post_log_std, const uint8_t *state_positive_mask_host,
+                                 const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

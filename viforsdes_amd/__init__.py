@@ -13,13 +13,13 @@ _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 from .config import AmpDtype, EncoderConfig, HeadConfig, PretrainConfig, TrainingConfig, YamlConfig
 from .core.observations import GaussianObservationLikelihood, ObservationLikelihood, Observations
 from .core.priors import Prior, PriorType
-from .core.reaction_network import ReactionNetworkSDE
+from .core.reaction_network import Hill, MichaelisMenten, ReactionNetworkSDE
 from .core.sde import SDE, FunctionalSDE, make_sde
 from .infer import InferenceConfig, infer
 from .posterior.variational_posterior import EvidenceEstimate, PosteriorPredictive, VariationalPosterior
 
 __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "TrainingConfig", "YamlConfig",
            "GaussianObservationLikelihood", "ObservationLikelihood", "Observations", "Prior", "PriorType", "SDE",
-           "FunctionalSDE", "ReactionNetworkSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior",
+           "FunctionalSDE", "Hill", "MichaelisMenten", "ReactionNetworkSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior",
            "EvidenceEstimate", "PosteriorPredictive"]
 __version__ = "0.1.0"

@@ -63,7 +63,9 @@ EXPORTS = (
     "vsde_attention_bwd_fused_bf16",
     "vsde_euler_maruyama_fwd", "vsde_euler_maruyama_bwd", "vsde_forecast", "vsde_sde_coefficients_fwd", "vsde_sde_coefficients_bwd",
     "vsde_crn_sde_coefficients_fwd", "vsde_crn_sde_coefficients_bwd", "vsde_crn_euler_maruyama_fwd", "vsde_crn_euler_maruyama_bwd",
-    "vsde_crn_forecast", "vsde_crn_log_weights", "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
+    "vsde_crn_forecast", "vsde_crn_log_weights", "vsde_crn_kinetic_sde_coefficients_fwd", "vsde_crn_kinetic_sde_coefficients_bwd",
+    "vsde_crn_kinetic_euler_maruyama_fwd", "vsde_crn_kinetic_euler_maruyama_bwd", "vsde_crn_kinetic_forecast",
+    "vsde_crn_kinetic_log_weights", "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
 )
@@ -301,7 +303,8 @@ def elbo_path_terms_bwd(z, x, means, chol, drift, diffusion, positive_dims, time
 
 
 SDE_KINDS = {"ornstein_uhlenbeck": 1, "lotka_volterra": 2, "linear_diagonal": 3, "reaction_network": 4}
-CRN_MAX_SPECIES, CRN_MAX_REACTIONS, CRN_MAX_ORDER = 8, 16, 3
+CRN_MAX_SPECIES, CRN_MAX_REACTIONS, CRN_MAX_ORDER, CRN_MAX_HILL = 8, 16, 3, 4
+CRN_LAW_MASS_ACTION, CRN_LAW_HILL_ACTIVATION, CRN_LAW_HILL_REPRESSION = 0, 1, 2
 
 
 class CrnNetwork(ctypes.Structure):
@@ -330,10 +333,44 @@ def crn_network(order, change) -> CrnNetwork:
     return net
 
 
+class CrnKinetics(ctypes.Structure):
+    """``vsde_crn_kinetics`` (include/vsde_hip.h): per reaction the law code (CRN_LAW_*), the modifier species and the Hill
+    coefficient of its rate law; host memory, copied into the kernel arguments at launch."""
+    _fields_ = [("law", ctypes.c_int8 * CRN_MAX_REACTIONS), ("modifier", ctypes.c_int8 * CRN_MAX_REACTIONS),
+                ("hill_n", ctypes.c_int8 * CRN_MAX_REACTIONS)]
+
+
+def crn_kinetics(laws) -> CrnKinetics:
+    """The rate-law descriptor of ``laws``: per reaction None (mass action) or ``(law code, modifier species, n)``."""
+    if not 1 <= len(laws) <= CRN_MAX_REACTIONS:
+        raise ValueError(f"rate-law descriptor: {len(laws)} reactions outside 1..{CRN_MAX_REACTIONS}")
+    kin = CrnKinetics()
+    for j, law in enumerate(laws):
+        code, s, n = (CRN_LAW_MASS_ACTION, 0, 1) if law is None else law
+        if code not in (CRN_LAW_MASS_ACTION, CRN_LAW_HILL_ACTIVATION, CRN_LAW_HILL_REPRESSION) or not (
+                0 <= s < CRN_MAX_SPECIES and 1 <= n <= CRN_MAX_HILL):
+            raise ValueError(f"rate-law descriptor: reaction {j}: law {code}, modifier {s}, n {n} outside 0..2 / "
+                             f"0..{CRN_MAX_SPECIES - 1} / 1..{CRN_MAX_HILL}")
+        kin.law[j], kin.modifier[j], kin.hill_n[j] = code, s, n
+    return kin
+
+
+class CrnKineticRoute:
+    """The kernel route of a reaction network with rate laws, shared or fixed constants (ReactionNetworkSDE.kernel_descriptor):
+    the network and rate-law descriptors, dispatched to the ``vsde_crn_kinetic_*`` entry points, and ``kernel_parameters``,
+    the network's differentiable map from theta [.., P] to the effective constants [.., 2R] those entry points take."""
+
+    def __init__(self, network: CrnNetwork, kinetics: CrnKinetics, kernel_parameters) -> None:
+        self.network, self.kinetics, self.kernel_parameters = network, kinetics, kernel_parameters
+
+
 def _sde_entry(lib, name: str, kind: str, network):
-    """(entry point, first argument) of a built-in SDE: ``vsde_<name>(kind, ...)``, or for a reaction network the mirrored
-    ``vsde_crn_<name>(&descriptor, ...)``."""
+    """(entry point, leading arguments) of a built-in SDE: ``vsde_<name>(kind, ...)``, or for a reaction network the mirrored
+    ``vsde_crn_<name>(&descriptor, ...)`` (``vsde_crn_kinetic_<name>(&descriptor, &rate laws, ...)`` for a CrnKineticRoute,
+    whose theta are the effective constants [B, 2R])."""
     if kind == "reaction_network":
+        if isinstance(network, CrnKineticRoute):
+            return getattr(lib, "vsde_crn_kinetic_" + name), ctypes.byref(network.network), ctypes.byref(network.kinetics)
         if not isinstance(network, CrnNetwork):
             raise ValueError("the reaction-network kernels need the network's descriptor (ReactionNetworkSDE.network_descriptor())")
         return getattr(lib, "vsde_crn_" + name), ctypes.byref(network)
@@ -438,12 +475,13 @@ def elbo_tail_bwd(x_obs, obs_values, obs_matrix, variance: float, theta, prior_t
 
 def log_weights(kind: str | None, z, means, chol, drift, diffusion, theta, obs_rows, obs_values, obs_matrix, variance: float,
                 prior_type: int, prior_mean: float, prior_std: float, post_mean, post_log_std, state_positive_dims,
-                theta_positive_dims, time_step: float, network=None):
+                theta_positive_dims, time_step: float, network=None, rates=None):
     """Per-sample importance log-weights [B] (see include/vsde_hip.h: vsde_log_weights).  ``kind`` in SDE_KINDS evaluates the
     built-in drift / diffusion in the kernel (``drift`` / ``diffusion`` None; a reaction network also needs its ``network``
-    descriptor: vsde_crn_log_weights); ``kind`` None reads the given tensors."""
+    descriptor: vsde_crn_log_weights, and for a CrnKineticRoute the effective constants ``rates`` [B, 2R] of the drift /
+    diffusion: vsde_crn_kinetic_log_weights); ``kind`` None reads the given tensors."""
     lib = load()
-    dev = _require_hip(z, means, chol, drift, diffusion, theta, obs_rows, obs_values, post_mean, post_log_std)
+    dev = _require_hip(z, means, chol, drift, diffusion, theta, rates, obs_rows, obs_values, post_mean, post_log_std)
     z, means, chol, theta, obs_values, post_mean, post_log_std = (
         _f32c(t) for t in (z, means, chol, theta, obs_values, post_mean, post_log_std))
     drift, diffusion, obs_matrix = (None if t is None else _f32c(t) for t in (drift, diffusion, obs_matrix))
@@ -464,7 +502,14 @@ def log_weights(kind: str | None, z, means, chol, drift, diffusion, theta, obs_r
             ctypes.c_double(time_step))
     with torch.cuda.device(dev):
         out = torch.empty(B, device=dev, dtype=torch.float32)
-        if kind == "reaction_network":
+        if kind == "reaction_network" and isinstance(network, CrnKineticRoute):
+            if rates is None or rates.ndim != 2 or rates.shape[0] != B:
+                raise ValueError("log_weights: a reaction network with rate laws needs its effective constants rates [B, 2R]")
+            rates = _f32c(rates)
+            fn, net, kin = _sde_entry(lib, "log_weights", kind, network)
+            _call(fn, net, kin, *dims[:6], ctypes.c_int(rates.shape[1]), *dims[6:], _ptr(theta), _ptr(rates), *tail[1:],
+                  _ptr(out), _stream(dev))
+        elif kind == "reaction_network":
             fn, net = _sde_entry(lib, "log_weights", kind, network)
             _call(fn, net, *dims, *tail, _ptr(out), _stream(dev))
         else:

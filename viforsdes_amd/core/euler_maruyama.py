@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from .sde import SDE, builtin_sde_route
+from .sde import SDE, builtin_sde_route, kernel_theta
 
 
 def euler_maruyama(sde: SDE, x0: Tensor, theta: Tensor, time_horizon: float, dt: float,
@@ -32,7 +32,7 @@ def euler_maruyama(sde: SDE, x0: Tensor, theta: Tensor, time_horizon: float, dt:
     if kind is not None and x0.is_cuda and x0.dtype == torch.float32 and HIP_SIMULATOR:
         from .. import _hip
         if kind in _hip.SDE_KINDS and noise.shape == (batch, n_steps, state_dim):
-            return _BuiltinEulerMaruyama.apply(x0, theta, noise, kind, float(dt), tuple(pos), network)
+            return _BuiltinEulerMaruyama.apply(x0, kernel_theta(network, theta), noise, kind, float(dt), tuple(pos), network)
     root_dt = dt ** 0.5
     states = [x0]
     x = x0

@@ -13,7 +13,7 @@ import torch
 from torch import Tensor
 
 from .euler_maruyama import euler_maruyama
-from .sde import SDE, builtin_sde_route
+from .sde import SDE, builtin_sde_route, kernel_theta
 
 
 def forecast_states(sde: SDE, x_start: Tensor, theta: Tensor, n_steps: int, out_steps, time_step: float,
@@ -46,6 +46,7 @@ def forecast_states(sde: SDE, x_start: Tensor, theta: Tensor, n_steps: int, out_
     if kind is not None and x_start.is_cuda and x_start.dtype == torch.float32:
         from .. import _hip
         key = torch.randint(-2 ** 31, 2 ** 31, (2,), device=dev, dtype=torch.int32)
-        return _hip.forecast(kind, x_start, theta, n_steps, steps, key, float(time_step), tuple(positive_dims), network=network)
+        return _hip.forecast(kind, x_start, kernel_theta(network, theta), n_steps, steps, key, float(time_step),
+                             tuple(positive_dims), network=network)
     traj = euler_maruyama(sde, x_start, theta, n_steps * time_step, time_step, positive_dims)
     return traj[:, steps.long()]

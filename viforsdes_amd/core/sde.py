@@ -67,7 +67,15 @@ def builtin_sde_kind(sde: object) -> str | None:
 
 def builtin_sde_route(sde: object) -> tuple[str | None, object]:
     """``(kind, network)``: the HIP library's name for ``sde`` (``builtin_sde_kind``) and, for a reaction network, its C-ABI
-    descriptor (``_hip.CrnNetwork``; None for the other kinds).  Every GPU route -- ELBO coefficients, simulator, forecast,
-    log-weights -- picks its kernels from this pair."""
+    descriptor (``_hip.CrnNetwork``, or ``_hip.CrnKineticRoute`` for a network with rate laws, shared or fixed constants; None
+    for the other kinds).  Every GPU route -- ELBO coefficients, simulator, forecast, log-weights -- picks its kernels from this
+    pair and hands them ``kernel_theta(network, theta)``."""
     kind = builtin_sde_kind(sde)
-    return kind, (sde.network_descriptor() if kind == "reaction_network" else None)
+    return kind, (sde.kernel_descriptor() if kind == "reaction_network" else None)
+
+
+def kernel_theta(network: object, theta: Tensor) -> Tensor:
+    """theta as the kernels of ``network`` (the second item of ``builtin_sde_route``) take it: a ``CrnKineticRoute``'s
+    effective constants ``[.., 2R]`` (its network's differentiable ``kernel_parameters``), else theta itself."""
+    kernel_parameters = getattr(network, "kernel_parameters", None)
+    return theta if kernel_parameters is None else kernel_parameters(theta)

@@ -362,6 +362,7 @@ struct LogWeightParams {
     float dt, sqdt;
     float *log_w;              // [B]
     CrnNet net;                // kind 4
+    const float *rates;        // kind 4 with rate laws: the effective constants [B][2R] of the drift / diffusion
 };
 
 // the state of path b at its observed grid points: softplus(z) on the positive dims
@@ -375,13 +376,17 @@ template <int S> struct XObsLatent {
     }
 };
 
-template <int KIND, int S, int NR = EmDims<KIND>::P>
+template <int KIND, int S, int NR = EmDims<KIND>::P, bool KIN = false>
 __global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p) {
-    constexpr int PK = KIND == 3 ? 2 * S : KIND == 4 ? NR : 3;
+    constexpr int PK = KIND == 3 ? 2 * S : KIND == 4 ? (KIN ? 2 * NR : NR) : 3;
     const int b = blockIdx.x;
     float th[PK];
+    if constexpr (KIN) {
+        crn_load_rates<NR>(th, p.rates, b, p.net.R, true);
+    } else {
 #pragma unroll
-    for (int i = 0; i < PK; ++i) th[i] = (KIND == 0 || (KIND == 4 && i >= p.tail.P)) ? 0.f : p.tail.theta[(int64_t)b * p.tail.P + i];
+        for (int i = 0; i < PK; ++i) th[i] = (KIND == 0 || (KIND == 4 && i >= p.tail.P)) ? 0.f : p.tail.theta[(int64_t)b * p.tail.P + i];
+    }
     float acc = 0.f;
     for (int t = threadIdx.x; t < p.T; t += blockDim.x) {
         const int64_t o1 = ((int64_t)b * (p.T + 1) + t) * S, o2 = ((int64_t)b * p.T + t) * S;
@@ -408,7 +413,7 @@ __global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p) {
             sde = -0.5f * ((float)S * kLog2Pi + quad) - logdet;
         } else {
             float f[S], G[S * S];
-            if constexpr (KIND == 4) crn_coef<S, NR>(p.net, x0, th, f, G);
+            if constexpr (KIND == 4) crn_coef<S, NR, KIN>(p.net, x0, th, f, G);
             else coef_fwd<KIND>(x0, th, f, G);
             sde = tri_logpdf<S>(x1, x0, f, G, p.dt, p.sqdt, w);
         }
@@ -432,8 +437,9 @@ __global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p) {
     }
 }
 
-template <int KIND, int S, int NR = EmDims<KIND>::P> static int launch_log_weights(const LogWeightParams &p, hipStream_t s) {
-    hipLaunchKernelGGL((log_weight_kernel<KIND, S, NR>), dim3(p.tail.B), dim3(256), 0, s, p);
+template <int KIND, int S, int NR = EmDims<KIND>::P, bool KIN = false>
+static int launch_log_weights(const LogWeightParams &p, hipStream_t s) {
+    hipLaunchKernelGGL((log_weight_kernel<KIND, S, NR, KIN>), dim3(p.tail.B), dim3(256), 0, s, p);
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -633,5 +639,30 @@ extern "C" int vsde_crn_log_weights(const vsde_crn_network *net, int B, int T, i
     p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
     return crn_dispatch(S, P, [&](auto ns, auto nr) {
         return launch_log_weights<4, decltype(ns)::value, decltype(nr)::value>(p, (hipStream_t)stream);
+    });
+}
+
+extern "C" int vsde_crn_kinetic_log_weights(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K,
+                                            int O, int P, int R_eff, const float *z, const float *means, const float *chol,
+                                            const float *theta, const float *rates, const int *obs_rows, const float *obs_values,
+                                            const float *obs_matrix, double variance, int prior_type, double prior_mean,
+                                            double prior_std, const float *post_mean, const float *post_log_std,
+                                            const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host,
+                                            double time_step, float *log_w, void *stream) {
+    LogWeightParams p = {};
+    int rc = crn_net(net, S, R_eff, p.net, true);
+    if (rc) return rc;
+    rc = crn_kinetics(kin, S, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0 && K >= 0, VSDE_E_BADARG, "bad log-weight dims B=%d T=%d S=%d K=%d", B, T, S, K);
+    VSDE_CHECK_ARG(z && means && chol && rates && log_w && (K == 0 || obs_rows) && time_step > 0, VSDE_E_BADARG,
+                   "NULL argument / bad time_step");
+    rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
+                   post_mean, post_log_std, theta_positive_mask_host, z, z, z);
+    if (rc) return rc;
+    p.T = T; p.z = z; p.means = means; p.chol = chol; p.obs_rows = obs_rows; p.rates = rates;
+    p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
+    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
+        return launch_log_weights<4, decltype(ns)::value, decltype(nr)::value, true>(p, (hipStream_t)stream);
     });
 }

@@ -98,9 +98,9 @@ __device__ __forceinline__ void em_load_theta(float *th, const float *theta, int
 }
 
 // kinds 1, 2, 4: thread = path
-template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false>
 __global__ void __launch_bounds__(kEmPaths) em_fwd_kernel(EmParams p) {
-    constexpr int S = NS, P = NR, CH = em_chunk(S), RS = CH * S + 1;
+    constexpr int S = NS, P = KIN ? 2 * NR : NR, CH = em_chunk(S), RS = CH * S + 1;
     __shared__ float noise_s[kEmPaths * RS], traj_s[kEmPaths * RS];
     const int lane = threadIdx.x, b0 = blockIdx.x * kEmPaths, b = b0 + lane;
     const int rows = min(kEmPaths, p.B - b0);
@@ -108,7 +108,8 @@ __global__ void __launch_bounds__(kEmPaths) em_fwd_kernel(EmParams p) {
     float x[S], th[P];
 #pragma unroll
     for (int i = 0; i < S; ++i) x[i] = valid ? p.x0[(int64_t)b * S + i] : 1.f;
-    em_load_theta<KIND, P>(th, p.theta, b, p.P, valid);
+    if constexpr (KIN) crn_load_rates<NR>(th, p.theta, b, p.net.R, valid);
+    else em_load_theta<KIND, P>(th, p.theta, b, p.P, valid);
     if (valid)
 #pragma unroll
         for (int i = 0; i < S; ++i) p.traj[(int64_t)b * (p.T + 1) * S + i] = x[i];
@@ -118,7 +119,7 @@ __global__ void __launch_bounds__(kEmPaths) em_fwd_kernel(EmParams p) {
         __syncthreads();
         for (int k = 0; k < n; ++k) {
             float y[S];
-            if constexpr (KIND == 4) crn_em_step<S, NR>(p.net, x, th, noise_s + lane * RS + k * S, p.dt, p.sqdt, y);
+            if constexpr (KIND == 4) crn_em_step<S, NR, KIN>(p.net, x, th, noise_s + lane * RS + k * S, p.dt, p.sqdt, y);
             else em_step<KIND>(x, th, noise_s + lane * RS + k * S, p.dt, p.sqdt, y);
 #pragma unroll
             for (int i = 0; i < S; ++i) {
@@ -132,9 +133,9 @@ __global__ void __launch_bounds__(kEmPaths) em_fwd_kernel(EmParams p) {
     }
 }
 
-template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false>
 __global__ void __launch_bounds__(kEmPaths) em_bwd_kernel(EmParams p) {
-    constexpr int S = NS, P = NR, CH = em_chunk(S), RS = (CH + 1) * S + 1;
+    constexpr int S = NS, P = KIN ? 2 * NR : NR, CH = em_chunk(S), RS = (CH + 1) * S + 1;
     __shared__ float noise_s[kEmPaths * RS], traj_s[kEmPaths * RS], g_s[kEmPaths * RS];
     const int lane = threadIdx.x, b0 = blockIdx.x * kEmPaths, b = b0 + lane;
     const int rows = min(kEmPaths, p.B - b0);
@@ -142,7 +143,8 @@ __global__ void __launch_bounds__(kEmPaths) em_bwd_kernel(EmParams p) {
     float a[S], th[P], gth[P];
 #pragma unroll
     for (int i = 0; i < S; ++i) a[i] = 0.f;
-    em_load_theta<KIND, P>(th, p.theta, b, p.P, valid);
+    if constexpr (KIN) crn_load_rates<NR>(th, p.theta, b, p.net.R, valid);
+    else em_load_theta<KIND, P>(th, p.theta, b, p.P, valid);
 #pragma unroll
     for (int k = 0; k < P; ++k) gth[k] = 0.f;
     const int nchunks = (p.T + CH - 1) / CH;
@@ -162,7 +164,7 @@ __global__ void __launch_bounds__(kEmPaths) em_bwd_kernel(EmParams p) {
                 if (((p.pos_mask >> i) & 1u) && xs[S + i] == kEmFloor) a[i] = 0.f;          // clamped entry: no gradient
             }
             float ax[S];
-            if constexpr (KIND == 4) crn_em_step_bwd<S, NR>(p.net, xs, th, noise_s + lane * RS + k * S, a, p.dt, p.sqdt, ax, gth);
+            if constexpr (KIND == 4) crn_em_step_bwd<S, NR, KIN>(p.net, xs, th, noise_s + lane * RS + k * S, a, p.dt, p.sqdt, ax, gth);
             else em_step_bwd<KIND>(xs, th, noise_s + lane * RS + k * S, a, p.dt, p.sqdt, ax, gth);
 #pragma unroll
             for (int i = 0; i < S; ++i) a[i] = ax[i];
@@ -172,10 +174,14 @@ __global__ void __launch_bounds__(kEmPaths) em_bwd_kernel(EmParams p) {
     if (valid) {
 #pragma unroll
         for (int i = 0; i < S; ++i) p.g_x0[(int64_t)b * S + i] = a[i] + p.g_traj[(int64_t)b * (p.T + 1) * S + i];
-        const int np = KIND == 4 ? p.P : P;
+        if constexpr (KIN) {
+            crn_store_rates<NR>(p.g_theta, gth, b, p.net.R);
+        } else {
+            const int np = KIND == 4 ? p.P : P;
 #pragma unroll
-        for (int k = 0; k < P; ++k)
-            if (k < np) p.g_theta[(int64_t)b * np + k] = gth[k];
+            for (int k = 0; k < P; ++k)
+                if (k < np) p.g_theta[(int64_t)b * np + k] = gth[k];
+        }
     }
 }
 
@@ -267,9 +273,9 @@ __device__ __forceinline__ void fc_normals(uint32_t blk, uint32_t i, uint32_t b,
 // is branch-free: the Philox / Box-Muller work of the NEXT block depends on no state, so it sits in the same basic block as the
 // 4-step serial chain and the scheduler interleaves the two.  Output rows are written after the block from the 4 kept states
 // (out_steps is the same for every thread: the write loop is uniform).  Steps that never come (out_steps above T) read NaN.
-template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false>
 __global__ void __launch_bounds__(256) forecast_kernel(FcParams p) {
-    constexpr int S = NS, P = NR;
+    constexpr int S = NS, P = KIN ? 2 * NR : NR;
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int b, d0, rs;                          // path, first state dim of this thread, row stride of x_start / out
     if constexpr (KIND == 3) {
@@ -289,6 +295,8 @@ __global__ void __launch_bounds__(256) forecast_kernel(FcParams p) {
     }
     if constexpr (KIND == 3) {
         th[0] = p.theta[(int64_t)b * p.P + d0]; th[1] = p.theta[(int64_t)b * p.P + p.S + d0];
+    } else if constexpr (KIN) {
+        crn_load_rates<NR>(th, p.theta, b, p.net.R, true);
     } else {
         em_load_theta<KIND, P>(th, p.theta, b, p.P, true);
     }
@@ -311,7 +319,7 @@ __global__ void __launch_bounds__(256) forecast_kernel(FcParams p) {
             float e[S], y[S];
 #pragma unroll
             for (int i = 0; i < S; ++i) e[i] = z[i][j];
-            if constexpr (KIND == 4) crn_em_step<S, NR>(p.net, x, th, e, p.dt, p.sqdt, y);
+            if constexpr (KIND == 4) crn_em_step<S, NR, KIN>(p.net, x, th, e, p.dt, p.sqdt, y);
             else em_step<KIND>(x, th, e, p.dt, p.sqdt, y);
 #pragma unroll
             for (int i = 0; i < S; ++i) xs[j][i] = x[i] = pos[i] ? floor_nan(y[i]) : y[i];
@@ -382,17 +390,18 @@ __device__ __forceinline__ void coef_bwd(const float *x, const float *th, const 
 }
 
 // thread = grid point (b, t)
-template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false>
 __global__ void __launch_bounds__(256) coef_fwd_kernel(CoefParams p) {
-    constexpr int S = NS, P = NR;
+    constexpr int S = NS, P = KIN ? 2 * NR : NR;
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= (int64_t)p.B * p.T) return;
     const int b = (int)(q / p.T), t = (int)(q % p.T);
     float x[S], th[P], f[S], G[S * S];
 #pragma unroll
     for (int i = 0; i < S; ++i) x[i] = p.x[((int64_t)b * (p.T + 1) + t) * S + i];
-    em_load_theta<KIND, P>(th, p.theta, b, p.P, true);
-    if constexpr (KIND == 4) crn_coef<S, NR>(p.net, x, th, f, G);
+    if constexpr (KIN) crn_load_rates<NR>(th, p.theta, b, p.net.R, true);
+    else em_load_theta<KIND, P>(th, p.theta, b, p.P, true);
+    if constexpr (KIND == 4) crn_coef<S, NR, KIN>(p.net, x, th, f, G);
     else coef_fwd<KIND>(x, th, f, G);
 #pragma unroll
     for (int i = 0; i < S; ++i) p.drift[q * S + i] = f[i];
@@ -401,13 +410,14 @@ __global__ void __launch_bounds__(256) coef_fwd_kernel(CoefParams p) {
 }
 
 // workgroup = path: threads walk the time steps, the theta gradient is reduced through LDS in a fixed tree
-template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P>
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false>
 __global__ void __launch_bounds__(256) coef_bwd_kernel(CoefParams p) {
-    constexpr int S = NS, P = NR;
+    constexpr int S = NS, P = KIN ? 2 * NR : NR;
     __shared__ float red[256][P + 1];
     const int b = blockIdx.x, tid = threadIdx.x;
     float th[P], gth[P];
-    em_load_theta<KIND, P>(th, p.theta, b, p.P, true);
+    if constexpr (KIN) crn_load_rates<NR>(th, p.theta, b, p.net.R, true);
+    else em_load_theta<KIND, P>(th, p.theta, b, p.P, true);
 #pragma unroll
     for (int i = 0; i < P; ++i) gth[i] = 0.f;
     for (int t = tid; t <= p.T; t += 256) {
@@ -419,7 +429,7 @@ __global__ void __launch_bounds__(256) coef_bwd_kernel(CoefParams p) {
             for (int i = 0; i < S; ++i) { x[i] = p.x[((int64_t)b * (p.T + 1) + t) * S + i]; gf[i] = p.g_drift[q * S + i]; }
 #pragma unroll
             for (int i = 0; i < S * S; ++i) gG[i] = p.g_diff[q * S * S + i];
-            if constexpr (KIND == 4) crn_coef_bwd<S, NR>(p.net, x, th, gf, gG, gx, gth);
+            if constexpr (KIND == 4) crn_coef_bwd<S, NR, KIN>(p.net, x, th, gf, gG, gx, gth);
             else coef_bwd<KIND>(x, th, gf, gG, gx, gth);
         } else {
 #pragma unroll
@@ -437,8 +447,13 @@ __global__ void __launch_bounds__(256) coef_bwd_kernel(CoefParams p) {
             for (int i = 0; i < P; ++i) red[tid][i] += red[tid + w][i];
         __syncthreads();
     }
-    const int np = KIND == 4 ? p.P : P;
-    if (tid < np) p.g_theta[(int64_t)b * np + tid] = red[0][tid];
+    if constexpr (KIN) {
+        const int R = p.net.R;          // red[0] holds (k_0 .. k_{NR-1}, K_0 .. K_{NR-1}); g_theta [B][2R]
+        if (tid < 2 * R) p.g_theta[(int64_t)b * 2 * R + tid] = red[0][tid < R ? tid : NR + tid - R];
+    } else {
+        const int np = KIND == 4 ? p.P : P;
+        if (tid < np) p.g_theta[(int64_t)b * np + tid] = red[0][tid];
+    }
 }
 
 // kind 3 (f_i = -a_i x_i, G = diag(softplus(b_i) + 1e-3)): thread = (b, t, i) forward; workgroup = path backward with the threads
@@ -680,6 +695,110 @@ extern "C" int vsde_crn_sde_coefficients_bwd(const vsde_crn_network *net, int B,
     p.g_x = g_x; p.g_theta = g_theta;
     return crn_dispatch(S, P, [&](auto ns, auto nr) {
         hipLaunchKernelGGL((coef_bwd_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3(B), dim3(256), 0, (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Kind 4 with rate laws (include/vsde_hip.h: vsde_crn_kinetics): the KIN instantiations, theta = the effective constants
+// rates [B][2R].  Both descriptors are checked and copied into the kernel arguments here, before any HIP call.
+
+static int crn_kinetic_net(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int S, int P, CrnNet &n) {
+    const int rc = crn_net(net, S, P, n, true);
+    return rc ? rc : crn_kinetics(kin, S, n);
+}
+
+extern "C" int vsde_crn_kinetic_euler_maruyama_fwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S,
+                                                   int P, const float *x0, const float *rates, const float *noise,
+                                                   double time_step, const uint8_t *positive_mask_host, float *traj,
+                                                   void *stream) {
+    EmParams p = {};
+    int rc = crn_kinetic_net(net, kin, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad Euler-Maruyama dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(x0 && rates && noise && traj && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.x0 = x0; p.theta = rates; p.noise = noise; p.traj = traj;
+    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((em_fwd_kernel<4, decltype(ns)::value, decltype(nr)::value, true>), dim3((B + kEmPaths - 1) / kEmPaths),
+                           dim3(kEmPaths), 0, (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int vsde_crn_kinetic_euler_maruyama_bwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S,
+                                                   int P, const float *rates, const float *noise, const float *traj,
+                                                   const float *g_traj, double time_step, const uint8_t *positive_mask_host,
+                                                   float *g_x0, float *g_rates, void *stream) {
+    EmParams p = {};
+    int rc = crn_kinetic_net(net, kin, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad Euler-Maruyama dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(rates && noise && traj && g_traj && g_x0 && g_rates && time_step > 0, VSDE_E_BADARG,
+                   "NULL argument / bad time_step");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.theta = rates; p.noise = noise; p.traj_in = traj; p.g_traj = g_traj;
+    p.g_x0 = g_x0; p.g_theta = g_rates;
+    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((em_bwd_kernel<4, decltype(ns)::value, decltype(nr)::value, true>), dim3((B + kEmPaths - 1) / kEmPaths),
+                           dim3(kEmPaths), 0, (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int vsde_crn_kinetic_forecast(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int P,
+                                         int K, const float *x_start, const float *rates, const int *out_steps,
+                                         const uint32_t *key, double time_step, const uint8_t *positive_mask_host, float *out,
+                                         void *stream) {
+    FcParams p = {};
+    int rc = crn_kinetic_net(net, kin, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad forecast dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(K > 0, VSDE_E_BADARG, "bad forecast output count K=%d", K);
+    VSDE_CHECK_ARG(x_start && rates && out_steps && key && out && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.K = K; p.x0 = x_start; p.theta = rates; p.steps = out_steps; p.key = key; p.out = out;
+    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((forecast_kernel<4, decltype(ns)::value, decltype(nr)::value, true>), dim3((B + kEmPaths - 1) / kEmPaths),
+                           dim3(kEmPaths), 0, (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int vsde_crn_kinetic_sde_coefficients_fwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T,
+                                                     int S, int P, const float *x, const float *rates, float *drift,
+                                                     float *diffusion, void *stream) {
+    CoefParams p = {};
+    int rc = crn_kinetic_net(net, kin, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad coefficient dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(x && rates && drift && diffusion, VSDE_E_BADARG, "NULL argument");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = rates; p.drift = drift; p.diff = diffusion;
+    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((coef_fwd_kernel<4, decltype(ns)::value, decltype(nr)::value, true>),
+                           dim3((unsigned)(((int64_t)B * T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int vsde_crn_kinetic_sde_coefficients_bwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T,
+                                                     int S, int P, const float *x, const float *rates, const float *g_drift,
+                                                     const float *g_diffusion, float *g_x, float *g_rates, void *stream) {
+    CoefParams p = {};
+    int rc = crn_kinetic_net(net, kin, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad coefficient dims B=%d T=%d", B, T);
+    VSDE_CHECK_ARG(x && rates && g_drift && g_diffusion && g_x && g_rates, VSDE_E_BADARG, "NULL argument");
+    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = rates; p.g_drift = g_drift; p.g_diff = g_diffusion;
+    p.g_x = g_x; p.g_theta = g_rates;
+    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
+        hipLaunchKernelGGL((coef_bwd_kernel<4, decltype(ns)::value, decltype(nr)::value, true>), dim3(B), dim3(256), 0,
+                           (hipStream_t)stream, p);
         VSDE_CHECK_HIP(hipGetLastError());
         return 0;
     });

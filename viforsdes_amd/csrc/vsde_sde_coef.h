@@ -3,7 +3,8 @@
 //   kind 1  Ornstein-Uhlenbeck  (examples/ornstein_uhlenbeck.py:18-30)   f = kappa (mu - x),   G = sigma
 //   kind 2  Lotka-Volterra      (examples/lotka_volterra.py:18-46)       analytic 2x2 Cholesky factor, three clamp(min=1e-6)
 //   kind 3  linear / diagonal   (BASELINE config 5)                       f = -a x, G = diag(softplus(b) + 1e-3)
-//   kind 4  reaction network    (core/reaction_network.py)                mass action, floored Cholesky factor of sum_j h_j nu_j nu_j^T
+//   kind 4  reaction network    (core/reaction_network.py)                mass action or Hill rate laws, floored Cholesky factor of
+//                                                                         sum_j h_j nu_j nu_j^T
 #pragma once
 #include <type_traits>
 
@@ -52,10 +53,13 @@ struct CrnNet {
     int R;
     int8_t order[kCrnMaxR][kCrnMaxS];   // reactant orders, 0..3
     float change[kCrnMaxR][kCrnMaxS];   // net change as float: FMA operands straight from the kernel arguments
+    // rate laws (vsde_crn_kinetics): read only by the KIN instantiations, zero for the mass-action entry points
+    int8_t law[kCrnMaxR], mod[kCrnMaxR], hill_n[kCrnMaxR];
 };
 
-// validate a C-ABI descriptor (host memory) against the call's S / P and convert it into the kernel-argument form
-static inline int crn_net(const vsde_crn_network *d, int S, int P, CrnNet &n) {
+// validate a C-ABI descriptor (host memory) against the call's S / P and convert it into the kernel-argument form; P is R, or 2R
+// for the rate-law entry points (kinetic: theta is the effective constants (k_0 .. k_{R-1}, K_0 .. K_{R-1}))
+static inline int crn_net(const vsde_crn_network *d, int S, int P, CrnNet &n, bool kinetic = false) {
     VSDE_CHECK_ARG(d, VSDE_E_BADARG, "NULL reaction-network descriptor");
     VSDE_CHECK_ARG(d->S >= 1 && d->S <= kCrnMaxS, VSDE_E_BADARG, "reaction network: %d species (1..%d supported)", d->S, kCrnMaxS);
     VSDE_CHECK_ARG(d->R >= 1 && d->R <= kCrnMaxR, VSDE_E_BADARG, "reaction network: %d reactions (1..%d supported)", d->R, kCrnMaxR);
@@ -64,8 +68,13 @@ static inline int crn_net(const vsde_crn_network *d, int S, int P, CrnNet &n) {
             VSDE_CHECK_ARG(d->order[j][i] >= 0 && d->order[j][i] <= VSDE_CRN_MAX_ORDER, VSDE_E_BADARG,
                            "reaction network: reaction %d has order %d in species %d (0..%d supported)", j, (int)d->order[j][i], i,
                            VSDE_CRN_MAX_ORDER);
-    VSDE_CHECK_ARG(S == d->S && P == d->R, VSDE_E_BADARG,
-                   "reaction network of %d species and %d reactions called with state_dim %d, sde_param_dim %d", d->S, d->R, S, P);
+    if (kinetic)
+        VSDE_CHECK_ARG(S == d->S && P == 2 * d->R, VSDE_E_BADARG,
+                       "reaction network of %d species and %d reactions called with state_dim %d and %d effective constants (2R = %d)",
+                       d->S, d->R, S, P, 2 * d->R);
+    else
+        VSDE_CHECK_ARG(S == d->S && P == d->R, VSDE_E_BADARG,
+                       "reaction network of %d species and %d reactions called with state_dim %d, sde_param_dim %d", d->S, d->R, S, P);
     n = CrnNet{};
     n.R = d->R;
     for (int j = 0; j < d->R; ++j)
@@ -73,12 +82,79 @@ static inline int crn_net(const vsde_crn_network *d, int S, int P, CrnNet &n) {
     return 0;
 }
 
+// validate a rate-law descriptor (host memory) against the network already in n (crn_net first) and copy it into n
+static inline int crn_kinetics(const vsde_crn_kinetics *k, int S, CrnNet &n) {
+    VSDE_CHECK_ARG(k, VSDE_E_BADARG, "NULL rate-law descriptor");
+    for (int j = 0; j < n.R; ++j) {
+        const int law = k->law[j];
+        VSDE_CHECK_ARG(law >= VSDE_CRN_LAW_MASS_ACTION && law <= VSDE_CRN_LAW_HILL_REPRESSION, VSDE_E_BADARG,
+                       "rate laws: reaction %d has law code %d (0..2 supported)", j, law);
+        if (law == VSDE_CRN_LAW_MASS_ACTION) continue;
+        VSDE_CHECK_ARG(k->modifier[j] >= 0 && k->modifier[j] < S, VSDE_E_BADARG,
+                       "rate laws: reaction %d has modifier species %d (0..%d for %d species)", j, (int)k->modifier[j], S - 1, S);
+        VSDE_CHECK_ARG(k->hill_n[j] >= 1 && k->hill_n[j] <= VSDE_CRN_MAX_HILL, VSDE_E_BADARG,
+                       "rate laws: reaction %d has Hill coefficient %d (1..%d supported)", j, (int)k->hill_n[j], VSDE_CRN_MAX_HILL);
+    }
+    for (int j = 0; j < n.R; ++j) {
+        const bool ma = k->law[j] == VSDE_CRN_LAW_MASS_ACTION;
+        n.law[j] = k->law[j]; n.mod[j] = ma ? 0 : k->modifier[j]; n.hill_n[j] = ma ? 1 : k->hill_n[j];
+    }
+    return 0;
+}
+
 // x^r by repeated multiplication (r uniform, 0..3) and its derivative r x^(r-1)
 __device__ __forceinline__ float crn_pow(float x, int r) { return r == 0 ? 1.f : r == 1 ? x : r == 2 ? x * x : x * x * x; }
 __device__ __forceinline__ float crn_dpow(float x, int r) { return r == 0 ? 0.f : r == 1 ? 1.f : r == 2 ? 2.f * x : 3.f * (x * x); }
 
+// a rate-law table entry as an opaque uniform value.  Read plainly, the entries of all NR reactions are loop-invariant in the time
+// loops, and the compiler hoists every comparison made with them (law, Hill coefficient, `i == s`: each a 64-lane mask, 2 SGPRs)
+// out of the loop: 100-800 SGPRs spilled to VGPR lanes, and scratch.  The empty asm makes each read a fresh value and the
+// (convergent, so never hoisted) readfirstlane returns it to an SGPR as a uniform value: the masks are remade next to their use,
+// a few instructions per reaction and step.
+__device__ __forceinline__ int crn_rl(int v) {
+    asm volatile("" : "+v"(v));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
+// v^e for a Hill coefficient e (uniform, 1..4) by repeated multiplication, ((v v) v) v: the spec's operation order
+__device__ __forceinline__ float crn_hpow(float v, int e) {
+    float r = v;
+#pragma unroll
+    for (int k = 1; k < VSDE_CRN_MAX_HILL; ++k)
+        if (k < e) r *= v;
+    return r;
+}
+
+// x[s] for a uniform run-time s: an unrolled select over the S registers (indexing the array by s would put it in scratch)
+template <int S> __device__ __forceinline__ float crn_pick(const float *x, int s) {
+    float v = 0.f;
+#pragma unroll
+    for (int i = 0; i < S; ++i)
+        if (i == s) v = x[i];
+    return v;
+}
+
+// propensity h_j; th [NR] = k (mass action only), or [2 NR] = (k, K) with KIN (rate laws: u = clamp(x_s, min=0), a = u^n,
+// c = K^n, g = a / (c + a) or c / (c + a), h = k g; `u` keeps NaN like torch.clamp)
+template <int S, int NR, bool KIN>
+__device__ __forceinline__ float crn_propensity(const CrnNet &n, int j, const float *x, const float *th) {
+    if constexpr (KIN) {
+        const int law = crn_rl(n.law[j]);
+        if (law != VSDE_CRN_LAW_MASS_ACTION) {
+            const int e = crn_rl(n.hill_n[j]);
+            const float xs = crn_pick<S>(x, crn_rl(n.mod[j])), u = xs < 0.f ? 0.f : xs;
+            const float a = crn_hpow(u, e), c = crn_hpow(th[NR + j], e);
+            return th[j] * ((law == VSDE_CRN_LAW_HILL_ACTIVATION ? a : c) / (c + a));
+        }
+    }
+    float m = 1.f;
+#pragma unroll
+    for (int i = 0; i < S; ++i) m *= crn_pow(x[i], n.order[j][i]);
+    return th[j] * m;
+}
+
 // drift f [S] and the lower triangle of Sigma = sum_j h_j nu_j nu_j^T in sig [S][S]
-template <int S, int NR>
+template <int S, int NR, bool KIN = false>
 __device__ __forceinline__ void crn_drift_cov(const CrnNet &n, const float *x, const float *th, float *f, float *sig) {
 #pragma unroll
     for (int i = 0; i < S; ++i) {
@@ -89,10 +165,7 @@ __device__ __forceinline__ void crn_drift_cov(const CrnNet &n, const float *x, c
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
         if (j < n.R) {
-            float m = 1.f;
-#pragma unroll
-            for (int i = 0; i < S; ++i) m *= crn_pow(x[i], n.order[j][i]);
-            const float h = th[j] * m;
+            const float h = crn_propensity<S, NR, KIN>(n, j, x, th);
 #pragma unroll
             for (int i = 0; i < S; ++i) {
                 const float hn = h * n.change[j][i];
@@ -126,20 +199,21 @@ template <int S> __device__ __forceinline__ void crn_chol(float *a, float *sd) {
     }
 }
 
-// drift f [S] and diffusion factor G [S][S] (row-major, lower triangular) of a network at state x; th [NR]
-template <int S, int NR>
+// drift f [S] and diffusion factor G [S][S] (row-major, lower triangular) of a network at state x; th [NR] ([2 NR] with KIN)
+template <int S, int NR, bool KIN = false>
 __device__ __forceinline__ void crn_coef(const CrnNet &n, const float *x, const float *th, float *f, float *G) {
     float sd[S];
-    crn_drift_cov<S, NR>(n, x, th, f, G);
+    crn_drift_cov<S, NR, KIN>(n, x, th, f, G);
     crn_chol<S>(G, sd);
 }
 
-// vector-Jacobian product of crn_coef: (gf [S], lower triangle of gG [S][S]) -> gx [S] (overwritten), gth [NR] (+=)
-template <int S, int NR>
+// vector-Jacobian product of crn_coef: (gf [S], lower triangle of gG [S][S]) -> gx [S] (overwritten), gth [NR] ([2 NR] with KIN)
+// (+=)
+template <int S, int NR, bool KIN = false>
 __device__ __forceinline__ void crn_coef_bwd(const CrnNet &n, const float *x, const float *th, const float *gf, const float *gG,
                                              float *gx, float *gth) {
     float f[S], L[S * S], sd[S], d[S * S];
-    crn_drift_cov<S, NR>(n, x, th, f, L);
+    crn_drift_cov<S, NR, KIN>(n, x, th, f, L);
     crn_chol<S>(L, sd);
 #pragma unroll
     for (int i = 0; i < S; ++i) {
@@ -166,7 +240,10 @@ __device__ __forceinline__ void crn_coef_bwd(const CrnNet &n, const float *x, co
 #pragma unroll
         for (int k = 0; k < j; ++k) d[j * S + k] -= 2.f * ds * L[j * S + k];
     }
-    // through Sigma and f to the propensities, then h_j = theta_j prod_i x_i^r_ji
+    // through Sigma and f to the propensities, then h_j = theta_j prod_i x_i^r_ji.  With KIN the rate-law reactions keep their
+    // dh_j for a second loop: one loop with both bodies is too large to unroll fully at S = 8, NR = 16 (its arrays would go to
+    // scratch)
+    float dhl[KIN ? NR : 1];
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
         if (j < n.R) {
@@ -177,6 +254,10 @@ __device__ __forceinline__ void crn_coef_bwd(const CrnNet &n, const float *x, co
 #pragma unroll
                 for (int k = 0; k <= i; ++k) acc += d[i * S + k] * n.change[j][k];
                 dh += acc * n.change[j][i];
+            }
+            if constexpr (KIN) {
+                dhl[j] = dh;
+                if (crn_rl(n.law[j]) != VSDE_CRN_LAW_MASS_ACTION) continue;
             }
             float pre[S], m = 1.f;
 #pragma unroll
@@ -191,14 +272,38 @@ __device__ __forceinline__ void crn_coef_bwd(const CrnNet &n, const float *x, co
             }
         }
     }
+    if constexpr (KIN) {
+        // g = num / (c + a), num = a (activation) or c (repression):  dg/du = +-n u^(n-1) c / (c+a)^2,  dg/dK = -+n K^(n-1) a /
+        // (c+a)^2; x_s gets dg/du only where x_s >= 0 (torch.clamp's rule)
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            if (j < n.R) {
+                const int law = crn_rl(n.law[j]);
+                if (law != VSDE_CRN_LAW_MASS_ACTION) {
+                    const int s = crn_rl(n.mod[j]), e = crn_rl(n.hill_n[j]);
+                    const bool act = law == VSDE_CRN_LAW_HILL_ACTIVATION;
+                    const float dh = dhl[j], xs = crn_pick<S>(x, s), u = xs < 0.f ? 0.f : xs, K = th[NR + j];
+                    const float a = crn_hpow(u, e), c = crn_hpow(K, e), den = c + a;
+                    gth[j] += dh * ((act ? a : c) / den);
+                    const float w = dh * th[j] / (den * den), fe = (float)e;
+                    const float gu = xs >= 0.f ? w * c * fe * crn_pow(u, e - 1) : 0.f;
+                    const float gk = w * a * fe * crn_pow(K, e - 1);
+#pragma unroll
+                    for (int i = 0; i < S; ++i)
+                        if (i == s) gx[i] += act ? gu : -gu;
+                    gth[NR + j] += act ? -gk : gk;
+                }
+            }
+        }
+    }
 }
 
 // y = x + f dt + (G e) sqrt(dt)
-template <int S, int NR>
+template <int S, int NR, bool KIN = false>
 __device__ __forceinline__ void crn_em_step(const CrnNet &n, const float *x, const float *th, const float *e, float dt, float sqdt,
                                             float *y) {
     float f[S], G[S * S];
-    crn_coef<S, NR>(n, x, th, f, G);
+    crn_coef<S, NR, KIN>(n, x, th, f, G);
 #pragma unroll
     for (int i = 0; i < S; ++i) {
         float acc = 0.f;
@@ -209,7 +314,7 @@ __device__ __forceinline__ void crn_em_step(const CrnNet &n, const float *x, con
 }
 
 // reverse-mode derivative of crn_em_step: a = dL/dy (already masked by the clamp) -> ax = dL/dx, gth += dL/dtheta
-template <int S, int NR>
+template <int S, int NR, bool KIN = false>
 __device__ __forceinline__ void crn_em_step_bwd(const CrnNet &n, const float *x, const float *th, const float *e, const float *a,
                                                 float dt, float sqdt, float *ax, float *gth) {
     float gf[S], gG[S * S], gx[S];
@@ -219,9 +324,27 @@ __device__ __forceinline__ void crn_em_step_bwd(const CrnNet &n, const float *x,
 #pragma unroll
         for (int k = 0; k <= i; ++k) gG[i * S + k] = a[i] * e[k] * sqdt;
     }
-    crn_coef_bwd<S, NR>(n, x, th, gf, gG, gx, gth);
+    crn_coef_bwd<S, NR, KIN>(n, x, th, gf, gG, gx, gth);
 #pragma unroll
     for (int i = 0; i < S; ++i) ax[i] = a[i] + gx[i];
+}
+
+// the effective constants of path b, rates [B][2R] = (k_0 .. k_{R-1}, K_0 .. K_{R-1}), into th [2 NR] at compile-time
+// register offsets: th[j] = k_j, th[NR + j] = K_j (R at run time, the rest 1), and the gradient gth [2 NR] back into g [B][2R]
+template <int NR>
+__device__ __forceinline__ void crn_load_rates(float *th, const float *rates, int b, int R, bool valid) {
+    const float *r = rates + (int64_t)b * 2 * R;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        th[j] = (valid && j < R) ? r[j] : 1.f;
+        th[NR + j] = (valid && j < R) ? r[R + j] : 1.f;
+    }
+}
+template <int NR> __device__ __forceinline__ void crn_store_rates(float *g, const float *gth, int b, int R) {
+    float *o = g + (int64_t)b * 2 * R;
+#pragma unroll
+    for (int j = 0; j < NR; ++j)
+        if (j < R) { o[j] = gth[j]; o[R + j] = gth[NR + j]; }
 }
 
 // host: f(std::integral_constant<int, S>, std::integral_constant<int, NR>) for the run-time S in 1..kCrnMaxS and the reaction

@@ -11,7 +11,7 @@ from torch import Tensor
 
 from ..core.observations import ObservationLikelihood, Observations, grid_index
 from ..core.priors import Prior
-from ..core.sde import SDE, builtin_sde_route
+from ..core.sde import SDE, builtin_sde_route, kernel_theta
 from ..models.sde_parameter_posterior import SDEParameterPosterior
 from .evidence_lower_bound import _fused_tail_config, path_log_terms, sde_coefficients, tail_log_terms
 from .types import DiffusionPathSample
@@ -43,7 +43,8 @@ def importance_log_weights(sde: SDE, observations: Observations, observation_lik
         return _hip.log_weights(kind, z, sample.transition_means, sample.transition_cholesky, drift, diffusion, sde_parameters,
                                 obs_idx, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std,
                                 sde_parameter_posterior.mean, sde_parameter_posterior.log_std, sample.state_space.positive_dims,
-                                theta_pos, time_step, network=network)
+                                theta_pos, time_step, network=network,
+                                rates=None if kind is None else kernel_theta(network, sde_parameters))
     x = sample.x
     drift, diffusion = sde_coefficients(sde, x, sde_parameters)
     sde_lp, gen_lp, jac = path_log_terms(sample, drift, diffusion, time_step)

@@ -16,7 +16,7 @@ from torch.autograd.function import once_differentiable
 
 from ..core.observations import ObservationLikelihood, Observations, grid_index
 from ..core.priors import Prior
-from ..core.sde import SDE, builtin_sde_route
+from ..core.sde import SDE, builtin_sde_route, kernel_theta
 from ..kernels.backend import get_backend
 from ..models.sde_parameter_posterior import SDEParameterPosterior
 from .types import DiffusionPathSample, EvidenceLowerBoundComponents, EvidenceLowerBoundResult
@@ -74,7 +74,7 @@ def sde_coefficients(sde: SDE, x: Tensor, sde_parameters: Tensor) -> tuple[Tenso
     if kind is not None and HIP_COEFFICIENTS and x.is_cuda and x.dtype == torch.float32:
         from .. import _hip
         if kind in _hip.SDE_KINDS:
-            return _BuiltinCoefficients.apply(x, sde_parameters, kind, network)
+            return _BuiltinCoefficients.apply(x, kernel_theta(network, sde_parameters), kind, network)
     x_flat = x[:, :-1].reshape(B * n_steps, S)
     theta_flat = sde_parameters.unsqueeze(1).expand(B, n_steps, -1).reshape(B * n_steps, -1)
     return (sde.drift(x_flat, theta_flat).reshape(B, n_steps, S),
