@@ -560,6 +560,41 @@ int vsde_crn_kinetic_log_weights(const vsde_crn_network *net, const vsde_crn_kin
                                  const float *post_log_std, const uint8_t *state_positive_mask_host,
                                  const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
 
+/* Bootstrap particle filter: log p^(y | theta_m) of the Euler-Maruyama-discretised built-in SDE with the Gaussian observation
+ * term of vsde_elbo_tail_fwd, for M parameter vectors at once (viforsdes_amd/inference/particle_filter.py is the specification).
+ * One workgroup per theta, one thread per particle: N particles, a multiple of 64 up to 1024 (reaction networks of 5..8 species:
+ * up to 512); S <= 16 (kinds 1, 2 and networks: their own S), O <= 16, M N < 2^32.  x0[M][S] start states (every particle of filter
+ * m starts there), theta[M][P], obs_rows[K] (device int32, non-decreasing grid rows; the run has obs_rows[K-1] steps, several
+ * observations may share a row), obs_values[K][O], obs_matrix[O][S] or NULL (identity, O == S), key: 2 words in DEVICE memory.
+ *   Between observations: the step and 1e-6 clamp of vsde_euler_maruyama_fwd.  Noise: the stream of vsde_forecast; the normal of
+ * filter m, particle slot j, GLOBAL grid step t, dim i is that of path b = m N + j (counter word 3 = 0): a slot keeps its stream
+ * across resampling.
+ *   At observation k: lw_j = sum_o -(y_ko - (H x_j)_o)^2 / (2 variance) - log(2 pi variance) / 2, NaN counts as -inf;
+ * increments[m][k] = max lw + log sum_j exp(lw_j - max) - log N; ess[m][k] = (sum w)^2 / sum w^2 with w_j = exp(lw_j - max);
+ * filtered_mean / filtered_std [m][k][S]: weighted mean and standard deviation of the particles BEFORE resampling;
+ * particles [m][k][N][S] (those states) and ancestors [m][k][N] are optional (NULL = not written).  Then systematic resampling, at
+ * every observation: inclusive cumulative sums C_j of w in particle order (made non-decreasing by a running maximum: a tree of fp32
+ * sums is not), u = ((w0 >> 8) + 0.5) 2^-24 in (0, 1] with w0 the first word of philox4x32_10(counter {k, 0, m, 1}, key),
+ * tau_j = (j + u) / N C_{N-1}, ancestor_j = min(#{i : C_i <= tau_j}, N - 1); particle j continues from the state of ancestor_j.
+ * If no weight is positive: increment -inf, ess 0, mean / std NaN, ancestors the identity, the particles stay as they are.
+ * log_likelihood[m] = sum_k increments[m][k].  VSDE_E_BADARG before any HIP call for N not a multiple of 64 or above the limit, S
+ * or O above 16, K < 1, O != S without obs_matrix, or a bad network / rate-law descriptor.  The vsde_crn_* forms take the
+ * descriptors as the other vsde_crn_* entry points do (rates[M][2R] in place of theta for the rate-law form).  Forward only. */
+int vsde_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta, const int *obs_rows,
+                         const float *obs_values, const float *obs_matrix, double variance, const uint32_t *key, double time_step,
+                         const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
+                         float *filtered_mean, float *filtered_std, float *particles, int *ancestors, void *stream);
+int vsde_crn_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
+                             const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                             double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                             float *log_likelihood, float *increments, float *ess, float *filtered_mean, float *filtered_std,
+                             float *particles, int *ancestors, void *stream);
+int vsde_crn_kinetic_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P, int K,
+                                     int O, const float *x0, const float *rates, const int *obs_rows, const float *obs_values,
+                                     const float *obs_matrix, double variance, const uint32_t *key, double time_step,
+                                     const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
+                                     float *filtered_mean, float *filtered_std, float *particles, int *ancestors, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

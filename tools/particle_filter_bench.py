@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""Measures the particle-filter kernel (csrc/vsde_filter.hip: vsde_particle_filter) against the torch route of
+``particle_filter`` on the same GPU, at sizes a user would run: M thetas x N particles, the Lotka-Volterra example grid (400 Euler
+steps, 5 observations) and the SIR network (200 steps, 5 observations).  Prints one JSON line.
+
+Time per call: device events around ``--reps`` calls after ``--warmup``, twice (the pair shows the spread; 200 calls make a window
+of a few tenths of a second); the torch route is tens of thousands of small launches and seconds per call: ``--torch-reps`` of
+them.  Bytes: what the kernel route has to move (theta, start states, observations in; log-likelihood, increments, ESS and moments
+out: O(M K S)) against the [M N, S]-sized tensors the torch route reads and writes per Euler step.
+There is no earlier version of the feature to compare with: the torch route on the same device is the baseline.
+
+    python tools/particle_filter_bench.py [--m 1024] [--n 1024] [--reps 200] [--torch-reps 2]"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from viforsdes_amd import GaussianObservationLikelihood, Observations, ReactionNetworkSDE, particle_filter  # noqa: E402
+from viforsdes_amd.inference import particle_filter as pf  # noqa: E402
+
+DEV = torch.device("cuda:0")
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def compare(sde, obs, like, theta, dt, N, pos, a):
+    obs, theta = obs.to(DEV), theta.to(DEV)
+    key = torch.tensor([12345, 678], dtype=torch.int32, device=DEV)
+    run = lambda: particle_filter(sde, obs, like, theta, dt, n_particles=N, positive_dims=pos, key=key)
+    M, P = theta.shape
+    S, (K, O) = sde.state_dim, obs.values.shape
+    T = int(torch.round(obs.times[-1] / dt))
+    pf.HIP_FILTER = True
+    tk = timed(run, a.warmup, a.reps)
+    tk2 = timed(run, 0, a.reps)
+    res_k = run()
+    pf.HIP_FILTER = False
+    try:
+        tt = timed(run, 1, a.torch_reps)
+        res_t = run()
+    finally:
+        pf.HIP_FILTER = True
+    lk, lt = res_k.log_likelihood.double(), res_t.log_likelihood.double()
+    ok = torch.isfinite(lk) & torch.isfinite(lt)
+    kernel_bytes = 4 * (M * (P + S) + K * (O + 1) + M * (1 + 2 * K + 2 * K * S))
+    torch_bytes = 4 * M * N * S * 3 * T          # at the very least: state read, noise read, state written, per step
+    return {"M": M, "N": N, "steps": T, "observations": K, "kernel_ms": round(min(tk, tk2), 4), "kernel_ms_runs": [round(tk, 4), round(tk2, 4)],
+            "torch_ms": round(tt, 2), "ratio": round(tt / min(tk, tk2), 1),
+            "particle_steps_per_s": round(M * N * T / (min(tk, tk2) * 1e-3), 0),
+            "kernel_bytes": kernel_bytes, "torch_bytes_at_least": torch_bytes,
+            "mean_log_likelihood": [round(float(lk[ok].mean()), 4), round(float(lt[ok].mean()), 4)],
+            "finite_fraction": [float(torch.isfinite(lk).float().mean()), float(torch.isfinite(lt).float().mean())],
+            "min_particle_ess": round(float(res_k.effective_sample_size.min()), 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--m", type=int, default=1024)
+    ap.add_argument("--n", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--torch-reps", type=int, default=2)
+    a = ap.parse_args()
+    from viforsdes_amd.examples.sdes import lv_problem
+    g = torch.Generator().manual_seed(0)
+    lv, lv_obs, lv_like, _, _, lv_dt, lv_pos, _ = lv_problem()
+    lv_th = torch.tensor([0.5, 0.0025, 0.3]) * (1.0 + 0.1 * torch.rand(a.m, 3, generator=g))
+    sir = ReactionNetworkSDE(reactants=[[1, 1], [0, 1]], products=[[0, 2], [0, 0]], species=["S", "I"],
+                             reactions=["infection", "removal"])
+    sir_obs = Observations(times=torch.tensor([0.0, 5.0, 10.0, 15.0, 20.0]),
+                           values=torch.tensor([[95.0, 5.0], [85.0, 8.0], [72.0, 11.0], [60.0, 12.0], [50.0, 11.0]]))
+    sir_th = torch.tensor([0.004, 0.15]) * (1.0 + 0.1 * torch.rand(a.m, 2, generator=g))
+    rec = {"tool": "particle_filter_bench", "device": torch.cuda.get_device_name(DEV),
+           "lv": compare(lv, lv_obs, lv_like, lv_th, lv_dt, a.n, lv_pos, a),
+           "sir": compare(sir, sir_obs, GaussianObservationLikelihood(variance=1.0), sir_th, 0.1, a.n, [0, 1], a)}
+    print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()

@@ -16,10 +16,11 @@ from .core.priors import Prior, PriorType
 from .core.reaction_network import Hill, MichaelisMenten, ReactionNetworkSDE
 from .core.sde import SDE, FunctionalSDE, make_sde
 from .infer import InferenceConfig, infer
-from .posterior.variational_posterior import EvidenceEstimate, PosteriorPredictive, VariationalPosterior
+from .inference.particle_filter import ParticleFilterResult, particle_filter
+from .posterior.variational_posterior import EvidenceEstimate, ParameterReweighting, PosteriorPredictive, VariationalPosterior
 
 __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "TrainingConfig", "YamlConfig",
            "GaussianObservationLikelihood", "ObservationLikelihood", "Observations", "Prior", "PriorType", "SDE",
            "FunctionalSDE", "Hill", "MichaelisMenten", "ReactionNetworkSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior",
-           "EvidenceEstimate", "PosteriorPredictive"]
+           "EvidenceEstimate", "PosteriorPredictive", "ParameterReweighting", "ParticleFilterResult", "particle_filter"]
 __version__ = "0.1.0"

@@ -65,7 +65,8 @@ EXPORTS = (
     "vsde_crn_sde_coefficients_fwd", "vsde_crn_sde_coefficients_bwd", "vsde_crn_euler_maruyama_fwd", "vsde_crn_euler_maruyama_bwd",
     "vsde_crn_forecast", "vsde_crn_log_weights", "vsde_crn_kinetic_sde_coefficients_fwd", "vsde_crn_kinetic_sde_coefficients_bwd",
     "vsde_crn_kinetic_euler_maruyama_fwd", "vsde_crn_kinetic_euler_maruyama_bwd", "vsde_crn_kinetic_forecast",
-    "vsde_crn_kinetic_log_weights", "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
+    "vsde_crn_kinetic_log_weights", "vsde_particle_filter", "vsde_crn_particle_filter", "vsde_crn_kinetic_particle_filter",
+    "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
 )
@@ -427,6 +428,53 @@ def forecast(kind: str, x_start, theta, n_steps: int, out_steps, key, time_step:
               ctypes.c_int(theta.shape[1]), ctypes.c_int(K), _ptr(x_start), _ptr(theta), _ptr(out_steps), _ptr(key),
               ctypes.c_double(time_step), _mask_bytes(positive_dims, S), _ptr(out), _stream(dev))
     return out
+
+
+PF_MAX_STATE, PF_MAX_OBS, PF_MAX_PARTICLES = 16, 16, 1024
+
+
+def particle_filter_max_particles(kind: str, state_dim: int) -> int:
+    """The largest ``n_particles`` (a multiple of 64) the filter kernel of a built-in SDE takes (csrc/vsde_filter.hip: pf_max_n):
+    1024, and 512 for a reaction network of 5..8 species (its step needs more than the 128 registers of a 1024-thread workgroup)."""
+    return PF_MAX_PARTICLES // 2 if kind == "reaction_network" and state_dim > 4 else PF_MAX_PARTICLES
+
+
+def particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, key, time_step: float,
+                    n_particles: int, positive_dims=(), network=None, return_particles: bool = False):
+    """Bootstrap particle filters of a built-in model SDE (``kind`` in SDE_KINDS), one per row of theta [M, P] (the effective
+    constants [M, 2R] for a CrnKineticRoute) from the start states x0 [M, S], against obs_values [K, O] at the grid rows obs_rows
+    (int32 device tensor [K]) with a Gaussian observation term (obs_matrix [O, S] or None); noise and resampling uniforms come from
+    the Philox stream of ``key`` (2 int32 words on the device).  See include/vsde_hip.h: vsde_particle_filter.  Returns
+    (log_likelihood [M], increments [M, K], effective_sample_size [M, K], filtered_mean [M, K, S], filtered_std [M, K, S],
+    particles [M, K, N, S] or None, ancestors [M, K, N] int32 or None)."""
+    lib = load()
+    dev = _require_hip(x0, theta, obs_rows, obs_values, obs_matrix, key)
+    x0, theta, obs_values = _f32c(x0), _f32c(theta), _f32c(obs_values)
+    obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
+    if obs_rows.dtype != torch.int32 or obs_rows.ndim != 1 or key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2:
+        raise ValueError("particle_filter: obs_rows must be an int32 [K] tensor and key two int32 words")
+    obs_rows, key = obs_rows.contiguous(), key.contiguous()
+    if x0.ndim != 2 or theta.ndim != 2 or theta.shape[0] != x0.shape[0] or obs_values.ndim != 2 \
+            or obs_values.shape[0] != obs_rows.shape[0]:
+        raise ValueError(f"particle_filter: x0 [M, S], theta [M, P], obs_values [K, O], obs_rows [K] expected, got "
+                         f"{tuple(x0.shape)}, {tuple(theta.shape)}, {tuple(obs_values.shape)}, {tuple(obs_rows.shape)}")
+    M, S = x0.shape
+    K, O = obs_values.shape
+    N = int(n_particles)
+    if obs_matrix is not None and tuple(obs_matrix.shape) != (O, S):
+        raise ValueError(f"particle_filter: obs_matrix must be [{O}, {S}], got {tuple(obs_matrix.shape)}")
+    with torch.cuda.device(dev):
+        f32 = dict(device=dev, dtype=torch.float32)
+        loglik, incr, ess = torch.empty(M, **f32), torch.empty(M, K, **f32), torch.empty(M, K, **f32)
+        mean, std = torch.empty(M, K, S, **f32), torch.empty(M, K, S, **f32)
+        keep = return_particles and 0 < N <= PF_MAX_PARTICLES   # a bad N is the entry point's to refuse: allocate nothing for it
+        particles = torch.empty(M, K, N, S, **f32) if keep else None
+        ancestors = torch.empty(M, K, N, device=dev, dtype=torch.int32) if keep else None
+        _call(*_sde_entry(lib, "particle_filter", kind, network), ctypes.c_int(M), ctypes.c_int(N), ctypes.c_int(S),
+              ctypes.c_int(theta.shape[1]), ctypes.c_int(K), ctypes.c_int(O), _ptr(x0), _ptr(theta), _ptr(obs_rows), _ptr(obs_values),
+              _ptr(obs_matrix), ctypes.c_double(variance), _ptr(key), ctypes.c_double(time_step), _mask_bytes(positive_dims, S),
+              _ptr(loglik), _ptr(incr), _ptr(ess), _ptr(mean), _ptr(std), _ptr(particles), _ptr(ancestors), _stream(dev))
+    return loglik, incr, ess, mean, std, particles, ancestors
 
 
 def _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean, post_log_std, theta_positive_dims):

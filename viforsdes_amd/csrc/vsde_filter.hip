@@ -1,0 +1,359 @@
+// Bootstrap particle filter of the built-in SDEs (gfx950): log p^(y | theta) of the Euler-Maruyama-discretised model with a
+// Gaussian observation term, for M parameter vectors at once (viforsdes_amd/inference/particle_filter.py is the specification).
+// One launch runs whole filters: a workgroup per theta, a thread per particle; the particle's state, theta and the running
+// log-likelihood stay in registers from the first Euler step to the last.  Neither noise nor trajectory is stored: the normals come
+// from the forecast kernel's Philox stream (vsde_sde_step.h: fc_normals) with path index b = m N + j.
+// At an observation: the log-weight in registers; max, sum w^2 and sum w x by wave butterflies and one LDS stage; an inclusive
+// scan of the weights (wave scan by cross-lane moves, wave totals through LDS); cumulative sums and particle states go to LDS
+// (row stride S | 1: the gather below is not a bank conflict), every thread finds its ancestor by binary search over the cumulative
+// sums (systematic resampling, one uniform per (filter, observation)) and reads that state row.
+// LDS (dynamic): N cumulative sums + N (S | 1) state floats + 16 x 18 reduction slots: 73 KiB at N = 1024, S = 16.
+#include "vsde_sde_step.h"
+
+namespace vsde {
+
+constexpr int kPfMaxN = 1024, kPfWaves = kPfMaxN / kWave, kPfMaxS = 16, kPfMaxO = 16;
+constexpr int kPfRed = kPfWaves * (kPfMaxS + 2);   // floats of the reduction stage
+
+// Particles per filter an instantiation is built for.  A 1024-thread workgroup leaves 128 VGPRs per lane; the reaction-network step
+// at 5..8 species (its S x S covariance and Cholesky factor in registers) needs more, so those instantiations are built for 512
+// threads (256 VGPRs) and refuse a larger N rather than spill.
+constexpr int pf_max_n(int kind, int S) { return kind == 4 && S > 4 ? kPfMaxN / 2 : kPfMaxN; }
+
+struct PfParams {
+    int M, N, S, P, K, O;
+    const float *x0, *theta, *obs_values, *obs_matrix;
+    const int *rows;
+    const uint32_t *key;
+    float *loglik, *incr, *ess, *mean, *std, *particles;
+    int *ancestors;
+    uint32_t pos_mask;
+    float dt, sqdt, inv_var, log_norm, log_n;
+    CrnNet net;    // kind 4
+};
+
+__device__ __forceinline__ float pf_wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// v[0 .. NV) summed over the workgroup, the result in every thread: butterfly per wave (every lane adds the same pairs, so the lanes
+// agree bitwise), wave totals through red [nwaves][NV], added in wave order
+template <int NV>
+__device__ __forceinline__ void pf_block_sum(float *v, float *red, int lane, int wave, int nwaves) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
+    if (lane == 0)
+#pragma unroll
+        for (int i = 0; i < NV; ++i) red[wave * NV + i] = v[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        float s = 0.f;
+        for (int w = 0; w < nwaves; ++w) s += red[w * NV + i];
+        v[i] = s;
+    }
+    __syncthreads();
+}
+
+// Euler-Maruyama steps t0 .. t1 - 1 (global grid steps, t1 > t0) of one particle, path index b of the noise stream
+template <int KIND, int NS, int NR, bool KIN, int P>
+__device__ __forceinline__ void pf_propagate(const PfParams &p, float *x, const float *th, int t0, int t1, uint32_t b, uint32_t k0,
+                                             uint32_t k1, int m) {
+    if constexpr (KIND == 3) {
+        // independent scalar SDEs: one dim at a time, so only 4 normals are alive (theta_i is uniform: scalar loads)
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            {
+                const float th2[2] = {p.theta[(int64_t)m * p.P + i], p.theta[(int64_t)m * p.P + NS + i]};
+                const bool pos = (p.pos_mask >> i) & 1u;
+                float xi = x[i];
+                for (int blk = t0 >> 2; blk <= (t1 - 1) >> 2; ++blk) {
+                    float z[4];
+                    fc_normals((uint32_t)blk, (uint32_t)i, b, k0, k1, z);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int t = 4 * blk + q;
+                        if (t >= t0 && t < t1) {
+                            float y;
+                            em_step<3>(&xi, th2, &z[q], p.dt, p.sqdt, &y);
+                            xi = pos ? floor_nan(y) : y;
+                        }
+                    }
+                }
+                x[i] = xi;
+            }
+        }
+    } else {
+        for (int blk = t0 >> 2; blk <= (t1 - 1) >> 2; ++blk) {
+            float z[NS][4];
+#pragma unroll
+            for (int i = 0; i < NS; ++i) fc_normals((uint32_t)blk, (uint32_t)i, b, k0, k1, z[i]);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int t = 4 * blk + q;
+                if (t >= t0 && t < t1) {
+                    float e[NS], y[NS];
+#pragma unroll
+                    for (int i = 0; i < NS; ++i) e[i] = z[i][q];
+                    if constexpr (KIND == 4) crn_em_step<NS, NR, KIN>(p.net, x, th, e, p.dt, p.sqdt, y);
+                    else em_step<KIND>(x, th, e, p.dt, p.sqdt, y);
+#pragma unroll
+                    for (int i = 0; i < NS; ++i) x[i] = ((p.pos_mask >> i) & 1u) ? floor_nan(y[i]) : y[i];
+                }
+            }
+        }
+    }
+}
+
+// workgroup = filter m (theta_m), thread = particle j.  NS: the state dim (kind 3: one instantiation per dim: a run-time dim under
+// `i < S` guards costs a hoisted 64-lane mask per guard and pushes the S = 16 kernel into scratch); NR: reaction bound
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false>
+__global__ void __launch_bounds__(pf_max_n(KIND, NS)) pf_kernel(PfParams p) {
+    constexpr int P = KIND == 3 ? 1 : KIN ? 2 * NR : NR;
+    extern __shared__ __attribute__((aligned(16))) float pf_lds[];
+    constexpr int S = NS, RS = S | 1;
+    const int N = p.N;
+    float *cum = pf_lds, *rows_s = cum + N, *red = rows_s + N * RS;
+    const int j = threadIdx.x, lane = j & (kWave - 1), wave = j >> 6, nwaves = N >> 6, m = blockIdx.x;
+    const uint32_t b = (uint32_t)m * (uint32_t)N + (uint32_t)j;
+    const uint32_t k0 = p.key[0], k1 = p.key[1];
+    float x[NS], th[P];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) x[i] = i < S ? p.x0[(int64_t)m * S + i] : 0.f;
+    if constexpr (KIND == 3) th[0] = 0.f;
+    else if constexpr (KIN) crn_load_rates<NR>(th, p.theta, m, p.net.R, true);
+    else em_load_theta<KIND, P>(th, p.theta, m, p.P, true);
+    float loglik = 0.f;
+    int row_prev = 0;
+    for (int k = 0; k < p.K; ++k) {
+        const int row = p.rows[k];
+        if (row > row_prev) {
+            pf_propagate<KIND, NS, NR, KIN, P>(p, x, th, row_prev, row, b, k0, k1, m);
+            row_prev = row;
+        }
+        // Gaussian log-weight (the observation term of the ELBO tail kernel); NaN counts as -inf
+        const float *yk = p.obs_values + (int64_t)k * p.O;
+        float lw = 0.f;
+        if (p.obs_matrix) {
+            for (int o = 0; o < p.O; ++o) {
+                float pred = 0.f;
+#pragma unroll
+                for (int i = 0; i < NS; ++i)
+                    if (i < S) pred += p.obs_matrix[o * S + i] * x[i];
+                const float r = yk[o] - pred;
+                lw += -0.5f * r * r * p.inv_var + p.log_norm;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NS; ++i)
+                if (i < S) {
+                    const float r = yk[i] - x[i];
+                    lw += -0.5f * r * r * p.inv_var + p.log_norm;
+                }
+        }
+        if (!(lw == lw)) lw = -__builtin_inff();
+        if (p.particles)
+#pragma unroll
+            for (int i = 0; i < NS; ++i)
+                if (i < S) p.particles[(((int64_t)m * p.K + k) * N + j) * S + i] = x[i];
+        float mx = pf_wave_max(lw);
+        if (lane == 0) red[wave] = mx;
+        __syncthreads();
+        mx = red[0];
+        for (int w = 1; w < nwaves; ++w) mx = fmaxf(mx, red[w]);
+        __syncthreads();
+        const int64_t mk = (int64_t)m * p.K + k;
+        if (mx == -__builtin_inff()) {
+            // no particle has a positive weight: log p^ = -inf, the particles stay as they are
+            loglik = mx;
+            if (j == 0) {
+                p.incr[mk] = mx; p.ess[mk] = 0.f;
+                for (int i = 0; i < S; ++i) p.mean[mk * S + i] = p.std[mk * S + i] = __builtin_nanf("");
+            }
+            if (p.ancestors) p.ancestors[mk * N + j] = j;
+            continue;
+        }
+        const float w = expf(lw - mx);
+        // inclusive scan of w: Hillis-Steele in the wave, then a running maximum (a tree of fp32 sums is not monotone where a weight
+        // is below the rounding of its neighbours' sum; the binary search and ancestors that do not decrease in j need it to be)
+        float c = w;
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) {
+            const float t = __shfl_up(c, off, 64);
+            if (lane >= off) c += t;
+        }
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) {
+            const float t = __shfl_up(c, off, 64);
+            if (lane >= off) c = fmaxf(c, t);
+        }
+        if (lane == kWave - 1) red[wave] = c;
+        __syncthreads();
+        float base = 0.f, total = 0.f;
+        for (int w2 = 0; w2 < nwaves; ++w2) {
+            if (w2 == wave) base = total;
+            total += red[w2];
+        }
+        __syncthreads();
+        c += base;
+        // sum w^2 and sum w x, then sum w (x - mean)^2 (two passes: no cancellation where the spread is far below the mean), four
+        // dims per reduction round so that a round's operands do not crowd the state out of the registers at S = 16
+        constexpr int CH = NS < 4 ? NS : 4;
+        float mean[NS], s2 = 0.f;
+#pragma unroll
+        for (int i0 = 0; i0 < NS; i0 += CH) {
+            if (i0 < S) {
+                float v[CH + 1];
+                v[0] = w * w;
+#pragma unroll
+                for (int i = 0; i < CH; ++i) v[1 + i] = (i0 + i < S && w > 0.f) ? w * x[i0 + i] : 0.f;
+                pf_block_sum<CH + 1>(v, red, lane, wave, nwaves);
+                s2 = v[0];
+#pragma unroll
+                for (int i = 0; i < CH; ++i) mean[i0 + i] = v[1 + i] / total;
+            }
+        }
+#pragma unroll
+        for (int i0 = 0; i0 < NS; i0 += CH) {
+            if (i0 < S) {
+                float d[CH];
+#pragma unroll
+                for (int i = 0; i < CH; ++i) {
+                    const float dx = x[i0 + i] - mean[i0 + i];
+                    d[i] = (i0 + i < S && w > 0.f) ? w * dx * dx : 0.f;
+                }
+                pf_block_sum<CH>(d, red, lane, wave, nwaves);
+                if (j == 0)
+#pragma unroll
+                    for (int i = 0; i < CH; ++i)
+                        if (i0 + i < S) { p.mean[mk * S + i0 + i] = mean[i0 + i]; p.std[mk * S + i0 + i] = sqrtf(d[i] / total); }
+            }
+        }
+        const float inc = mx + logf(total) - p.log_n;
+        loglik += inc;
+        if (j == 0) { p.incr[mk] = inc; p.ess[mk] = total * total / s2; }
+        // systematic resampling: ancestor_j = min(#{i : C_i <= (j + u) / N C_{N-1}}, N - 1)
+        cum[j] = c;
+#pragma unroll
+        for (int i = 0; i < NS; ++i)
+            if (i < S) rows_s[j * RS + i] = x[i];
+        __syncthreads();
+        const float u = philox_uniform(philox4x32_10(make_uint4((uint32_t)k, 0u, (uint32_t)m, 1u), k0, k1).x);
+        const float tau = ((float)j + u) / (float)N * total;
+        int lo = 0, hi = N;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (cum[mid] <= tau) lo = mid + 1;
+            else hi = mid;
+        }
+        const int anc = min(lo, N - 1);
+#pragma unroll
+        for (int i = 0; i < NS; ++i)
+            if (i < S) x[i] = rows_s[anc * RS + i];
+        if (p.ancestors) p.ancestors[mk * N + j] = anc;
+        __syncthreads();
+    }
+    if (j == 0) p.loglik[m] = loglik;
+}
+
+// argument checks shared by the three entry points (before any HIP call) and the parameter block
+static int pf_fill(PfParams &p, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta, const int *obs_rows,
+                   const float *obs_values, const float *obs_matrix, double variance, const uint32_t *key, double time_step,
+                   const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess, float *filtered_mean,
+                   float *filtered_std, float *particles, int *ancestors) {
+    VSDE_CHECK_ARG(M >= 1 && K >= 1, VSDE_E_BADARG, "bad particle-filter dims M=%d K=%d", M, K);
+    VSDE_CHECK_ARG(N >= kWave && N <= kPfMaxN && N % kWave == 0, VSDE_E_BADARG,
+                   "particle filter: %d particles (a multiple of %d up to %d supported)", N, kWave, kPfMaxN);
+    VSDE_CHECK_ARG((int64_t)M * N < ((int64_t)1 << 32), VSDE_E_BADARG, "particle filter: M N = %lld paths (below 2^32 supported)",
+                   (long long)M * N);
+    VSDE_CHECK_ARG(S >= 1 && S <= kPfMaxS, VSDE_E_BADARG, "particle filter: state_dim %d (1..%d supported)", S, kPfMaxS);
+    VSDE_CHECK_ARG(O >= 1 && O <= kPfMaxO, VSDE_E_BADARG, "particle filter: obs_dim %d (1..%d supported)", O, kPfMaxO);
+    VSDE_CHECK_ARG(obs_matrix || O == S, VSDE_E_BADARG, "without an observation matrix obs_dim must equal state_dim (%d vs %d)", O, S);
+    VSDE_CHECK_ARG(variance > 0 && time_step > 0, VSDE_E_BADARG, "bad variance / time_step");
+    VSDE_CHECK_ARG(x0 && theta && obs_rows && obs_values && key && log_likelihood && increments && ess && filtered_mean && filtered_std,
+                   VSDE_E_BADARG, "NULL argument");
+    p.M = M; p.N = N; p.S = S; p.P = P; p.K = K; p.O = O;
+    p.x0 = x0; p.theta = theta; p.obs_values = obs_values; p.obs_matrix = obs_matrix; p.rows = obs_rows; p.key = key;
+    p.loglik = log_likelihood; p.incr = increments; p.ess = ess; p.mean = filtered_mean; p.std = filtered_std;
+    p.particles = particles; p.ancestors = ancestors;
+    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+    p.inv_var = (float)(1.0 / variance); p.log_norm = (float)(-0.5 * log(2.0 * M_PI * variance)); p.log_n = (float)log((double)N);
+    return 0;
+}
+
+template <class Kern> static int pf_launch(Kern kern, const PfParams &p, void *stream, int max_n = kPfMaxN) {
+    VSDE_CHECK_ARG(p.N <= max_n, VSDE_E_BADARG, "particle filter: %d particles (up to %d supported at state_dim %d of this SDE)", p.N,
+                   max_n, p.S);
+    const size_t lds = ((size_t)p.N * ((p.S | 1) + 1) + kPfRed) * sizeof(float);
+    if (lds > 64 * 1024)
+        VSDE_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(p.M), dim3(p.N), lds, (hipStream_t)stream, p);
+    VSDE_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace vsde
+
+using namespace vsde;
+
+extern "C" int vsde_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
+                                    const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                                    const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                    float *log_likelihood, float *increments, float *ess, float *filtered_mean, float *filtered_std,
+                                    float *particles, int *ancestors, void *stream) {
+    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);
+    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim");
+    PfParams p = {};
+    int rc = pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step, positive_mask_host,
+                     log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
+    if (rc) return rc;
+    if (kind == 1) return pf_launch(pf_kernel<1>, p, stream);
+    if (kind == 2) return pf_launch(pf_kernel<2>, p, stream);
+    switch (S) {
+#define VSDE_PF_DIAG(n) case n: return pf_launch(pf_kernel<3, n>, p, stream)
+        VSDE_PF_DIAG(1); VSDE_PF_DIAG(2); VSDE_PF_DIAG(3); VSDE_PF_DIAG(4); VSDE_PF_DIAG(5); VSDE_PF_DIAG(6); VSDE_PF_DIAG(7); VSDE_PF_DIAG(8);
+        VSDE_PF_DIAG(9); VSDE_PF_DIAG(10); VSDE_PF_DIAG(11); VSDE_PF_DIAG(12); VSDE_PF_DIAG(13); VSDE_PF_DIAG(14); VSDE_PF_DIAG(15);
+        default: VSDE_PF_DIAG(16);
+#undef VSDE_PF_DIAG
+    }
+}
+
+extern "C" int vsde_crn_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
+                                        const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                        double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                        float *log_likelihood, float *increments, float *ess, float *filtered_mean,
+                                        float *filtered_std, float *particles, int *ancestors, void *stream) {
+    PfParams p = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n);
+    if (rc) return rc;
+    rc = pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step, positive_mask_host,
+                 log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
+    if (rc) return rc;
+    p.net = n;
+    return crn_dispatch(S, P, [&](auto ns, auto nr) { return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value>, p, stream, pf_max_n(4, decltype(ns)::value)); });
+}
+
+extern "C" int vsde_crn_kinetic_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P,
+                                                int K, int O, const float *x0, const float *rates, const int *obs_rows,
+                                                const float *obs_values, const float *obs_matrix, double variance,
+                                                const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                                float *log_likelihood, float *increments, float *ess, float *filtered_mean,
+                                                float *filtered_std, float *particles, int *ancestors, void *stream) {
+    PfParams p = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n, true);
+    if (!rc) rc = crn_kinetics(kin, S, n);
+    if (rc) return rc;
+    rc = pf_fill(p, M, N, S, P, K, O, x0, rates, obs_rows, obs_values, obs_matrix, variance, key, time_step, positive_mask_host,
+                 log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
+    if (rc) return rc;
+    p.net = n;
+    return crn_dispatch(S, n.R, [&](auto ns, auto nr) {
+        return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value, true>, p, stream, pf_max_n(4, decltype(ns)::value));
+    });
+}

@@ -1,0 +1,253 @@
+"""Bootstrap particle filter: an unbiased estimate of the marginal likelihood ``p(y | theta)`` of the Euler-Maruyama-discretised
+model, for a batch of parameter vectors at once.  It is the yardstick that does not depend on the variational paths: profile
+likelihoods, a pseudo-marginal sampler, and the theta-only check of a fit (``VariationalPosterior.reweight_parameters``).
+
+The torch code below is the specification and runs anywhere (any SDE, any likelihood, CPU or GPU).  Built-in SDEs with a
+``GaussianObservationLikelihood`` on the GPU in fp32 and ``n_particles`` a multiple of 64 up to 1024 (512 for a reaction network
+of 5..8 species) run as ONE kernel (csrc/vsde_filter.hip: a workgroup per theta, a thread per particle) that reproduces it; every
+other case falls back to the torch route silently, as ``forecast_states`` does.
+
+The algorithm, for filter ``m`` (parameters ``theta_m``, ``N`` particles, all started at ``initial_state``):
+
+* grid rows of the observations ``rows = round(times / time_step)`` (the rule of ``grid_index``); ``rows[K-1]`` Euler steps in all,
+  several observations may share a row;
+* between observations the step of ``euler_maruyama`` (``positive_dims`` clamped at 1e-6 after every step);
+* at observation ``k``: ``lw_j = log p(y_k | x_j)`` (NaN counts as -inf), ``increment_k = max lw + log sum_j exp(lw_j - max) -
+  log N``; then systematic resampling, at every observation: ``w_j = exp(lw_j - max)``, inclusive cumulative sums ``C_j`` in particle
+  order (made non-decreasing by a running maximum, which is the identity in exact arithmetic), one uniform ``u`` in (0, 1],
+  thresholds ``tau_j = (j + u) / N * C_{N-1}``, ``ancestor_j = min(#{i : C_i <= tau_j}, N - 1)``; particle ``j`` continues from the
+  state of ``ancestor_j``.  If no weight is positive the increment is -inf, the ESS 0, the filtered moments NaN and the particles
+  stay as they are (ancestors = identity);
+* randomness is the forecast kernel's stream (include/vsde_hip.h): the normal of filter m, particle slot j, GLOBAL grid step t,
+  dim i is the normal of path ``b = m N + j``, step t, dim i for the call's key; the resampling uniform of (m, k) is
+  ``((w0 >> 8) + 0.5) 2^-24`` with ``w0`` the first word of ``philox4x32_10({k, 0, m, 1}, key)``.  A slot keeps its own noise
+  stream across resampling.  Same key => same result."""
+from __future__ import annotations
+
+import math
+from collections.abc import Sequence
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from ..core.euler_maruyama import _floor_vector
+from ..core.observations import GaussianObservationLikelihood, ObservationLikelihood, Observations
+from ..core.sde import SDE, builtin_sde_route, kernel_theta
+
+HIP_FILTER = True   # set False to force the torch route (A/B tests)
+
+_M0, _M1, _W0, _W1, _MASK = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xFFFFFFFF
+
+
+@dataclass(frozen=True)
+class ParticleFilterResult:
+    """``log_likelihood [M]``: log p^(y | theta_m) given the start state; ``increments [M, K]``: log p^(y_k | y_<k, theta_m), whose sum
+    over k it is; ``effective_sample_size [M, K]``: (sum w)^2 / sum w^2 of the weights at observation k, in [0, N];
+    ``filtered_mean`` / ``filtered_std [M, K, S]``: weighted moments of the particles before resampling; ``particles [M, K, N, S]``
+    (those states) and ``ancestors [M, K, N]`` (int32), or None unless asked for."""
+    log_likelihood: Tensor
+    increments: Tensor
+    effective_sample_size: Tensor
+    filtered_mean: Tensor
+    filtered_std: Tensor
+    particles: Optional[Tensor] = None
+    ancestors: Optional[Tensor] = None
+
+
+def _mul_hi_lo(m: int, c: Tensor) -> tuple[Tensor, Tensor]:
+    """High and low 32-bit words of the 64-bit product m * c (m, c < 2^32) in int64 arithmetic that never overflows."""
+    ph, pl = m * (c >> 16), m * (c & 0xFFFF)
+    return (ph + (pl >> 16)) >> 16, (((ph & 0xFFFF) << 16) + (pl & _MASK)) & _MASK
+
+
+def philox4x32_10(c0: Tensor, c1: Tensor, c2: Tensor, c3: Tensor, k0: Tensor, k1: Tensor) -> list[Tensor]:
+    """The four output words (int64 tensors holding uint32 values) of Philox4x32-10 for counter (c0..c3) and key (k0, k1), all int64
+    tensors of uint32 values, broadcast together."""
+    c = list(torch.broadcast_tensors(c0, c1, c2, c3))
+    for _ in range(10):
+        hi0, lo0 = _mul_hi_lo(_M0, c[0])
+        hi1, lo1 = _mul_hi_lo(_M1, c[2])
+        c = [hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0]
+        k0, k1 = (k0 + _W0) & _MASK, (k1 + _W1) & _MASK
+    return c
+
+
+def _uniform(w: Tensor) -> Tensor:
+    """u = ((w >> 8) + 0.5) 2^-24 in (0, 1], formed in fp32 as the kernels form it."""
+    return ((w >> 8).to(torch.float32) + 0.5) * 2.0 ** -24
+
+
+def _key_words(key: Tensor) -> tuple[Tensor, Tensor]:
+    k = key.to(torch.int64) & _MASK
+    return k[0], k[1]
+
+
+def stream_normals(n_paths: int, block: int, state_dim: int, key: Tensor) -> Tensor:
+    """The stream's normals of grid steps ``4 block .. 4 block + 3`` for paths ``0 .. n_paths - 1``: float64 ``[n_paths, S, 4]``
+    (Box-Muller on the word pairs (w0, w1), (w2, w3); u in fp32, log / sqrt / cos / sin in float64)."""
+    dev = key.device
+    k0, k1 = _key_words(key)
+    b = torch.arange(n_paths, device=dev, dtype=torch.int64)[:, None]
+    i = torch.arange(state_dim, device=dev, dtype=torch.int64)[None, :]
+    blk = torch.full((1, 1), int(block), device=dev, dtype=torch.int64)
+    w = philox4x32_10(blk, i, b, torch.zeros_like(blk), k0, k1)
+    out = []
+    for wa, wb in ((w[0], w[1]), (w[2], w[3])):
+        r = torch.sqrt(-2.0 * torch.log(_uniform(wa).double()))
+        ang = 2.0 * math.pi * _uniform(wb).double()
+        out += [r * torch.cos(ang), r * torch.sin(ang)]
+    return torch.stack(out, dim=-1)
+
+
+def resampling_uniforms(n_filters: int, k: int, key: Tensor) -> Tensor:
+    """The uniform of (filter m, observation k) for m = 0 .. n_filters - 1: fp32 ``[n_filters]``."""
+    dev = key.device
+    k0, k1 = _key_words(key)
+    m = torch.arange(n_filters, device=dev, dtype=torch.int64)
+    kk = torch.full((1,), int(k), device=dev, dtype=torch.int64)
+    return _uniform(philox4x32_10(kk, torch.zeros_like(kk), m, torch.ones_like(kk), k0, k1)[0])
+
+
+def systematic_ancestors(weights: Tensor, u: Tensor) -> Tensor:
+    """Ancestors ``[M, N]`` (int64) of systematic resampling with the weights ``[M, N]`` (>= 0, not all zero in a row) and one
+    uniform ``u [M]`` per row: ``min(#{i : C_i <= (j + u) / N * C_{N-1}}, N - 1)``."""
+    N = weights.shape[1]
+    cum = torch.cummax(torch.cumsum(weights, dim=1), dim=1).values
+    j = torch.arange(N, device=weights.device, dtype=weights.dtype)
+    tau = (j[None, :] + u.to(weights.dtype)[:, None]) / N * cum[:, -1:]
+    return torch.searchsorted(cum.contiguous(), tau.contiguous(), right=True).clamp(max=N - 1)
+
+
+def _validate(sde, observations, theta, time_step, n_particles, initial_state):
+    if n_particles < 1:
+        raise ValueError(f"n_particles must be >= 1, got {n_particles}")
+    if time_step <= 0:
+        raise ValueError(f"time_step must be positive, got {time_step}")
+    if theta.ndim == 1:
+        theta = theta.unsqueeze(0)
+    S, P = int(sde.state_dim), int(sde.sde_param_dim)
+    if theta.ndim != 2 or theta.shape[0] < 1 or theta.shape[1] != P:
+        raise ValueError(f"theta [M, {P}] or [{P}] expected (sde_param_dim {P}), got {tuple(theta.shape)}")
+    M = theta.shape[0]
+    if M * n_particles >= 2 ** 32:
+        raise ValueError(f"M * n_particles = {M * n_particles} paths: the noise stream indexes fewer than 2^32")
+    if observations.values.shape[0] < 1:
+        raise ValueError("observations must not be empty")
+    if initial_state is None:
+        if observations.values.shape[1] != S:
+            raise ValueError(f"initial_state is required: the observations have dim {observations.values.shape[1]}, the state {S}")
+        initial_state = observations.values[0]
+    x0 = initial_state.to(device=theta.device, dtype=theta.dtype)
+    if x0.ndim == 1:
+        x0 = x0.unsqueeze(0).expand(M, -1)
+    if tuple(x0.shape) != (M, S):
+        raise ValueError(f"initial_state [{S}] or [{M}, {S}] expected (state_dim {S}), got {tuple(initial_state.shape)}")
+    return theta, x0
+
+
+def particle_filter(sde: SDE, observations: Observations, observation_likelihood: ObservationLikelihood, theta: Tensor,
+                    time_step: float, n_particles: int = 1024, initial_state: Optional[Tensor] = None,
+                    positive_dims: Sequence[int] = (), return_particles: bool = False,
+                    key: Optional[Tensor] = None) -> ParticleFilterResult:
+    """Bootstrap particle filters with ``n_particles`` particles, one per row of ``theta`` (``[M, P]``, or ``[P]`` for M = 1), all
+    started at ``initial_state`` (``[S]`` or ``[M, S]``; default: the first observation).  The observation at the start row counts
+    like any other, so ``log_likelihood`` targets what ``VariationalPosterior.log_evidence`` conditions on.  ``key``: two int32
+    words (a tensor); default: drawn from torch's generator on theta's device, so ``torch.manual_seed`` makes the call repeatable
+    and a call captured in a HIP graph draws a fresh key per replay.  No gradients."""
+    theta, x0 = _validate(sde, observations, theta, time_step, n_particles, initial_state)
+    dev = theta.device
+    obs = observations if observations.values.device == dev else observations.to(dev)
+    if key is None:
+        key = torch.randint(-2 ** 31, 2 ** 31, (2,), device=dev, dtype=torch.int32)
+    else:
+        key = torch.as_tensor(key).to(dev)
+        if key.numel() != 2 or key.is_floating_point():
+            raise ValueError("key must hold two 32-bit integer words")
+        key = key.reshape(2)
+    pos = tuple(positive_dims)
+    with torch.no_grad():
+        route = _kernel_route(sde, obs, observation_likelihood, theta, n_particles)
+        if route is not None:
+            from .. import _hip
+            kind, network = route
+            H = observation_likelihood.obs_matrix
+            rows = torch.round(obs.times / time_step).to(torch.int32)
+            out = _hip.particle_filter(kind, x0, kernel_theta(network, theta), rows, obs.values, None if H is None else H.to(theta),
+                                       float(observation_likelihood.variance), key.to(torch.int32) if key.dtype != torch.int32 else key,
+                                       float(time_step), n_particles, pos, network=network, return_particles=return_particles)
+            return ParticleFilterResult(*out)
+        return _torch_filter(sde, obs, observation_likelihood, theta, float(time_step), n_particles, x0, pos, return_particles, key)
+
+
+def _kernel_route(sde, obs, like, theta, n_particles):
+    """``builtin_sde_route(sde)`` when the filter kernel takes the call, else None."""
+    if not (HIP_FILTER and theta.is_cuda and theta.dtype == torch.float32 and obs.values.dtype == torch.float32):
+        return None
+    if type(like) is not GaussianObservationLikelihood:
+        return None
+    kind, network = builtin_sde_route(sde)
+    if kind is None:
+        return None
+    from .. import _hip
+    S, O, H = int(sde.state_dim), obs.values.shape[1], like.obs_matrix
+    if S > _hip.PF_MAX_STATE or O > _hip.PF_MAX_OBS or (H is None and O != S) or (H is not None and tuple(H.shape) != (O, S)):
+        return None
+    if n_particles % 64 != 0 or n_particles > _hip.particle_filter_max_particles(kind, S):
+        return None
+    return kind, network
+
+
+def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key) -> ParticleFilterResult:
+    dev, dtype = theta.device, theta.dtype
+    M, P = theta.shape
+    S = x0.shape[1]
+    rows = torch.round(obs.times / dt).long().tolist()
+    K = len(rows)
+    x = x0[:, None, :].expand(M, N, S).reshape(M * N, S).clone()
+    th = theta[:, None, :].expand(M, N, P).reshape(M * N, P)
+    floor = _floor_vector(list(pos), S, dev, dtype) if pos else None
+    root_dt = dt ** 0.5
+    slot = torch.arange(N, device=dev)
+    neg_inf = torch.tensor(float("-inf"), device=dev, dtype=dtype)
+    incr, ess, means, stds, parts, ancs = [], [], [], [], [], []
+    t, z, z_block = 0, None, -1
+    for k in range(K):
+        while t < rows[k]:
+            if t // 4 != z_block:
+                z_block = t // 4
+                z = stream_normals(M * N, z_block, S, key).to(dtype)
+            shock = torch.einsum("bij,bj->bi", sde.diffusion(x, th), z[..., t % 4])
+            x = x + sde.drift(x, th) * dt + shock * root_dt
+            if floor is not None:
+                x = torch.maximum(x, floor)
+            t += 1
+        lw = like.log_prob(obs.values[k].to(dtype).unsqueeze(0).expand(M * N, -1), x).reshape(M, N)
+        lw = torch.where(torch.isnan(lw), neg_inf, lw)
+        mx = lw.max(dim=1, keepdim=True).values
+        dead = torch.isneginf(mx)
+        w = torch.exp(lw - torch.where(dead, torch.zeros_like(mx), mx))
+        s1, s2 = w.sum(dim=1), (w * w).sum(dim=1)
+        xm = x.reshape(M, N, S)
+        has = (w > 0)[..., None]
+        mean = torch.where(has, w[..., None] * xm, torch.zeros_like(xm)).sum(dim=1) / s1[:, None]
+        dx = xm - mean[:, None, :]
+        var = torch.where(has, w[..., None] * dx * dx, torch.zeros_like(xm)).sum(dim=1) / s1[:, None]
+        incr.append(torch.where(dead[:, 0], neg_inf, mx[:, 0] + torch.log(s1) - math.log(N)))
+        ess.append(torch.where(dead[:, 0], torch.zeros_like(s1), s1 * s1 / s2))
+        means.append(mean)
+        stds.append(var.sqrt())
+        safe = torch.where(dead, torch.ones_like(w), w)          # a dead filter keeps its particles: its row is overwritten below
+        anc = systematic_ancestors(safe, resampling_uniforms(M, k, key))
+        anc = torch.where(dead, slot[None, :], anc)
+        if return_particles:
+            parts.append(xm)
+            ancs.append(anc.to(torch.int32))
+        x = torch.gather(xm, 1, anc[..., None].expand(-1, -1, S)).reshape(M * N, S)
+    increments = torch.stack(incr, dim=1)
+    return ParticleFilterResult(
+        log_likelihood=increments.sum(dim=1), increments=increments, effective_sample_size=torch.stack(ess, dim=1),
+        filtered_mean=torch.stack(means, dim=1), filtered_std=torch.stack(stds, dim=1),
+        particles=torch.stack(parts, dim=1) if return_particles else None,
+        ancestors=torch.stack(ancs, dim=1) if return_particles else None)

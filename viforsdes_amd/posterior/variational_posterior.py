@@ -133,6 +133,37 @@ class PosteriorPredictive:
         return self._draws(observations).std(dim=0)
 
 
+@dataclass(frozen=True)
+class ParameterReweighting:
+    """Check of q(theta) alone (``VariationalPosterior.reweight_parameters``): ``n_samples`` draws theta ~ q with importance weights
+    ``log w = log p(theta) + log p^(y | theta) - log q(theta)``, the marginal likelihood estimated by a bootstrap particle filter
+    (unbiased, so the weights are proper although noisy).  Neither the encoder nor the head enters.
+
+    * ``log_evidence``, ``standard_error``, ``effective_sample_size``, ``n_nonfinite``: as in ``EvidenceEstimate``; a second,
+      independent estimate of the ``log p(y)`` that ``log_evidence()`` estimates.  The ESS says how far q(theta) is from the exact
+      theta posterior (the filter's own noise lowers it further);
+    * ``mean``, ``std`` ``[P]`` and ``quantiles`` of theta under the normalised weights (the quantile at level a is the smallest
+      draw whose cumulative normalised weight, in sorted order, reaches a), next to ``variational_mean`` / ``variational_std``, the
+      plain moments of the same draws;
+    * ``filter_effective_sample_size [n]``: the smallest particle ESS seen in each draw's filter -- near 1 the bootstrap filter
+      itself is starved (sharply informative observations) and ``log p^`` is noisy;
+    * ``sde_parameters [n, P]``, ``log_likelihood [n]``, ``log_weights [n]`` (float64) when asked for, else None."""
+    log_evidence: float
+    standard_error: float
+    effective_sample_size: float
+    n_samples: int
+    n_nonfinite: int
+    mean: Tensor
+    std: Tensor
+    quantiles: Quantiles
+    variational_mean: Tensor
+    variational_std: Tensor
+    filter_effective_sample_size: Tensor
+    sde_parameters: Optional[Tensor] = None
+    log_likelihood: Optional[Tensor] = None
+    log_weights: Optional[Tensor] = None
+
+
 class VariationalPosteriorCheckpoint(BaseModel):
     model_config = ConfigDict(frozen=True, arbitrary_types_allowed=True)
     model_state: dict[str, Tensor]
@@ -353,6 +384,63 @@ class VariationalPosterior:
             states = torch.cat([inside, after.to(inside.dtype)], dim=1)
         observations = like.sample(states) if like is not None else None
         return PosteriorPredictive(times=times.to(dev), sde_parameters=theta_all, states=states, observations=observations)
+
+    @torch.no_grad()
+    def reweight_parameters(self, sde: SDE, observation_likelihood: ObservationLikelihood, n_samples: int = 1024,
+                            n_particles: int = 512, chunk_size: int = 256, return_draws: bool = True) -> ParameterReweighting:
+        """Is q(theta) any good?  Draws theta ~ q with the EMA weights as ``sample()`` draws them, estimates ``log p(y | theta)`` of
+        the Euler-Maruyama-discretised model on this posterior's grid with a bootstrap particle filter (``particle_filter``:
+        ``n_particles`` particles per theta, ``chunk_size`` thetas per call, start state = first observation as in
+        ``log_evidence``), and weights the draws by ``p(theta) p^(y | theta) / q(theta)``.  Unlike ``log_evidence`` the variational
+        paths do not enter, so a poor path posterior cannot hide a good theta posterior or the reverse; and unlike it this also
+        runs on a CPU posterior (the filter's torch route).  It touches none of ``sample()``'s caches or graphs."""
+        from ..inference import particle_filter as _pf
+        if n_samples < 1 or chunk_size < 1 or n_particles < 1:
+            raise ValueError(f"n_samples, n_particles and chunk_size must be >= 1 (got {n_samples}, {n_particles}, {chunk_size})")
+        q = self.model.sde_parameter_posterior
+        S, P = self.state_space.dim, q.sde_param_dim
+        if sde.state_dim != S or sde.sde_param_dim != P:
+            raise ValueError(f"sde has state_dim {sde.state_dim}, sde_param_dim {sde.sde_param_dim}; the posterior has {S}, {P}")
+        self.model.eval()
+        with self.exponential_moving_average.apply():
+            theta = q.rsample(n_samples)
+            log_q = q.log_prob(theta).double()
+        log_prior = self.prior.log_prob(theta)
+        if log_prior.ndim > 1:
+            log_prior = log_prior.sum(dim=-1)
+        x0 = self.observations.values[0]
+        loglik = torch.empty(n_samples, device=theta.device, dtype=theta.dtype)
+        min_ess = torch.empty(n_samples, device=theta.device, dtype=theta.dtype)
+        for lo in range(0, n_samples, chunk_size):
+            res = _pf.particle_filter(sde, self.observations, observation_likelihood, theta[lo:lo + chunk_size], self.time_step,
+                                      n_particles=n_particles, initial_state=x0, positive_dims=self.state_space.positive_dims)
+            loglik[lo:lo + chunk_size] = res.log_likelihood
+            min_ess[lo:lo + chunk_size] = res.effective_sample_size.min(dim=1).values
+        log_w = log_prior.double() + loglik.double() - log_q
+        th = theta.double()
+        bad = int((torch.isnan(log_w) | torch.isposinf(log_w)).sum())
+        draws = (theta, loglik, log_w) if return_draws else (None, None, None)
+        v_mean, v_std = theta.mean(dim=0), theta.std(dim=0) if n_samples > 1 else torch.zeros_like(theta[0])
+        nan_p = torch.full_like(v_mean, float("nan"))
+        nan_q = Quantiles(*([nan_p] * len(QUANTILE_LEVELS)))
+        m = float(log_w.max()) if bad == 0 else float("nan")
+        if bad > 0 or m == float("-inf"):    # NaN weights: every estimate is NaN; all weights zero: -inf, as EvidenceEstimate says
+            head = (float("nan"),) * 3 if bad > 0 else (float("-inf"), float("inf"), 0.0)
+            return ParameterReweighting(*head, n_samples, bad, nan_p, nan_p, nan_q, v_mean, v_std, min_ess, *draws)
+        w = torch.exp(log_w - m)
+        s1, s2 = float(w.sum()), float((w * w).sum())
+        ess = s1 * s1 / s2
+        wn = w / s1
+        mean = (wn[:, None] * th).sum(dim=0)
+        std = (wn[:, None] * (th - mean) ** 2).sum(dim=0).sqrt()
+        order = torch.argsort(th, dim=0)
+        cdf = torch.cumsum(wn[order], dim=0)                                    # [n, P]: cumulative weight in each dim's sorted order
+        levels = torch.tensor(QUANTILE_LEVELS, device=th.device, dtype=th.dtype)
+        first = (cdf[None, :, :] < levels[:, None, None]).sum(dim=1).clamp(max=n_samples - 1)    # [levels, P]
+        quant = torch.gather(torch.gather(th, 0, order), 0, first)
+        return ParameterReweighting(
+            m + math.log(s1) - math.log(n_samples), math.sqrt(max(1.0 / ess - 1.0 / n_samples, 0.0)), ess, n_samples, 0,
+            mean.to(theta.dtype), std.to(theta.dtype), Quantiles(*quant.to(theta.dtype).unbind(0)), v_mean, v_std, min_ess, *draws)
 
     def summary(self, n_samples: int = 1000, mixed_precision: bool = False) -> VariationalPosteriorSummary:
         s = self.sample(n_samples, mixed_precision)
