@@ -942,15 +942,18 @@ def attention_bwd(dout, q, k, v, o, lse, scale: float):
 
 
 def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, want_bias: bool, row_map: Optional[torch.Tensor] = None,
-                 out_rows: Optional[int] = None):
+                 out_rows: Optional[int] = None, out: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None):
     """dW[N,K] = dy^T x and db[N] = colsum(dy) in fp32 for bf16 dy [M,N], x [M,K].  ``row_map`` (int32 [N] on the device):
-    product row n is stored at output row ``row_map[n]`` (negative: dropped) of an ``[out_rows, K]`` result."""
+    product row n is stored at output row ``row_map[n]`` (negative: dropped) of an ``[out_rows, K]`` result.
+    ``out`` / ``out_bias``: contiguous fp32 buffers [rows, K] / [rows] to write into instead of fresh ones."""
     lib = load(); dev = _require_hip(dy, x)
     M, N = dy.shape
     K = x.shape[1]
     rows = N if row_map is None else int(out_rows)
-    dW = torch.empty(rows, K, device=dev, dtype=torch.float32)
-    db = torch.empty(rows, device=dev, dtype=torch.float32) if want_bias else None
+    dW = torch.empty(rows, K, device=dev, dtype=torch.float32) if out is None else _given(out, (rows, K), torch.float32)
+    db = None
+    if want_bias:
+        db = torch.empty(rows, device=dev, dtype=torch.float32) if out_bias is None else _given(out_bias, (rows,), torch.float32)
     nbytes = lib.vsde_linear_wgrad_workspace_bytes(_i64(M), ctypes.c_int(N), ctypes.c_int(K))
     ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
@@ -964,21 +967,26 @@ class _WgradItem(ctypes.Structure):
                 ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p), ("row_map", ctypes.c_void_p)]
 
 
-def linear_wgrad_group(problems, group_plan: bool = False):
+def linear_wgrad_group(problems, group_plan: bool = False, outs=None):
     """``[(dy, x, want_bias, row_map, out_rows), ...]`` -> ``[(dW, db), ...]``: every problem as ``linear_wgrad`` computes it, all of
     them in a handful of launches (csrc/vsde_wgrad.hip, ``vsde_linear_wgrad_group_bf16``).  ``group_plan=False``: bit-identical to
-    one call per problem; ``True``: split counts chosen for the group as a whole (other summation order, less partial traffic)."""
+    one call per problem; ``True``: split counts chosen for the group as a whole (other summation order, less partial traffic).
+    ``outs``: ``[(dW, db or None), ...]`` contiguous fp32 buffers to write into instead of fresh ones."""
     lib = load()
     dev = _require_hip(*[t for pr in problems for t in pr[:2]])
     n = len(problems)
     items = (_WgradItem * n)()
-    outs = []
+    given, outs = outs, []
     for i, (dy, x, want_bias, row_map, out_rows) in enumerate(problems):
         M, N = dy.shape
         K = x.shape[1]
         rows = N if row_map is None else int(out_rows)
-        dW = torch.empty(rows, K, device=dev, dtype=torch.float32)
-        db = torch.empty(rows, device=dev, dtype=torch.float32) if want_bias else None
+        if given is None:
+            dW = torch.empty(rows, K, device=dev, dtype=torch.float32)
+            db = torch.empty(rows, device=dev, dtype=torch.float32) if want_bias else None
+        else:
+            dW = _given(given[i][0], (rows, K), torch.float32)
+            db = _given(given[i][1], (rows,), torch.float32) if want_bias else None
         items[i] = _WgradItem(dy.data_ptr(), x.data_ptr(), M, N, K, dW.data_ptr(), None if db is None else db.data_ptr(),
                               None if row_map is None else row_map.data_ptr())
         outs.append((dW, db))
@@ -1003,6 +1011,14 @@ def linear_supported(M: int, N: int, K: int, epilogue: int = EPI_PLAIN) -> bool:
     return linear_variant(M, N, K, epilogue) != 0
 
 
+def _given(t: torch.Tensor, shape, dtype, pitched: bool = False):
+    """A caller's output buffer: the expected shape and type, contiguous (``pitched``: rows contiguous, any row pitch)."""
+    ok = t.dtype == dtype and tuple(t.shape) == tuple(shape) and (t.is_contiguous() or (pitched and t.ndim == 2 and t.stride(1) == 1))
+    if not ok:
+        raise ValueError(f"output buffer: expected {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
 def _rows2d(t: torch.Tensor):
     """(tensor, row pitch) of a bf16 matrix whose rows are contiguous (a column range of a wider buffer is fine)."""
     if t.dtype != torch.bfloat16 or t.ndim != 2 or t.stride(1) != 1:
@@ -1023,17 +1039,21 @@ def linear_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], 
     return y
 
 
-def linear_swiglu_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], want_u: bool = True):
-    """(u [M,N] or None, s [M,N/2]) for the interleaved-packed SwiGLU input projection w [N,K]."""
+def linear_swiglu_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], want_u: bool = True,
+                       out_u: Optional[torch.Tensor] = None, out_s: Optional[torch.Tensor] = None):
+    """(u [M,N] or None, s [M,N/2]) for the interleaved-packed SwiGLU input projection w [N,K].  ``out_u`` / ``out_s``: row-pitched
+    bf16 buffers to write into instead of fresh ones."""
     lib = load(); dev = _require_hip(x, w)
     x, ldx = _rows2d(x)
     M, K = x.shape
     N = w.shape[0]
-    u = torch.empty(M, N, device=dev, dtype=torch.bfloat16) if want_u else None
-    s = torch.empty(M, N // 2, device=dev, dtype=torch.bfloat16)
+    u = None
+    if want_u:
+        u = torch.empty(M, N, device=dev, dtype=torch.bfloat16) if out_u is None else _given(out_u, (M, N), torch.bfloat16, True)
+    s = torch.empty(M, N // 2, device=dev, dtype=torch.bfloat16) if out_s is None else _given(out_s, (M, N // 2), torch.bfloat16, True)
     with torch.cuda.device(dev):
-        _call(lib.vsde_linear_bf16, _ptr(x), _i64(ldx), _ptr(w), _ptr(bias), _ptr(u), _i64(N), _i64(M), ctypes.c_int(N),
-              ctypes.c_int(K), ctypes.c_int(EPI_SWIGLU), _ptr(s), _i64(N // 2), None, _i64(0), _stream(dev))
+        _call(lib.vsde_linear_bf16, _ptr(x), _i64(ldx), _ptr(w), _ptr(bias), _ptr(u), _i64(N if u is None else u.stride(0)), _i64(M),
+              ctypes.c_int(N), ctypes.c_int(K), ctypes.c_int(EPI_SWIGLU), _ptr(s), _i64(s.stride(0)), None, _i64(0), _stream(dev))
     return u, s
 
 
@@ -1109,16 +1129,19 @@ def mlp_image_bytes(C: int) -> tuple[int, int, int]:
 
 
 def mlp_fwd(x: torch.Tensor, w1_img: torch.Tensor, w2_img: torch.Tensor, b1_img: torch.Tensor, b2: Optional[torch.Tensor], H: int,
-            want_s: bool = False):
-    """Fused SwiGLU MLP forward (csrc/vsde_mlp.hip): x [M,C] bf16 (row-pitched) -> (y [M,C] bf16, s [M,H] bf16 or None)."""
+            want_s: bool = False, out_y: Optional[torch.Tensor] = None, out_s: Optional[torch.Tensor] = None):
+    """Fused SwiGLU MLP forward (csrc/vsde_mlp.hip): x [M,C] bf16 (row-pitched) -> (y [M,C] bf16, s [M,H] bf16 or None).
+    ``out_y`` / ``out_s``: row-pitched bf16 buffers to write into instead of fresh ones."""
     lib = load(); dev = _require_hip(x, w1_img, w2_img, b1_img)
     x, ldx = _rows2d(x)
     M, C = x.shape
-    y = torch.empty(M, C, device=dev, dtype=torch.bfloat16)
-    s = torch.empty(M, H, device=dev, dtype=torch.bfloat16) if want_s else None
+    y = torch.empty(M, C, device=dev, dtype=torch.bfloat16) if out_y is None else _given(out_y, (M, C), torch.bfloat16, True)
+    s = None
+    if want_s:
+        s = torch.empty(M, H, device=dev, dtype=torch.bfloat16) if out_s is None else _given(out_s, (M, H), torch.bfloat16, True)
     with torch.cuda.device(dev):
-        _call(lib.vsde_mlp_fwd_bf16, _ptr(x), _i64(ldx), _ptr(w1_img), _ptr(w2_img), _ptr(b1_img), _ptr(b2), _ptr(y), _i64(C), _ptr(s),
-              _i64(H), _i64(M), ctypes.c_int(C), ctypes.c_int(H), _stream(dev))
+        _call(lib.vsde_mlp_fwd_bf16, _ptr(x), _i64(ldx), _ptr(w1_img), _ptr(w2_img), _ptr(b1_img), _ptr(b2), _ptr(y), _i64(y.stride(0)), _ptr(s),
+              _i64(H if s is None else s.stride(0)), _i64(M), ctypes.c_int(C), ctypes.c_int(H), _stream(dev))
     return y, s
 
 
@@ -1242,15 +1265,15 @@ def linear_gated_bf16(attn: torch.Tensor, gate: torch.Tensor, w: torch.Tensor, b
     return y
 
 
-def linear_swiglu_bwd_bf16(dy: torch.Tensor, w_t: torch.Tensor, u: torch.Tensor):
+def linear_swiglu_bwd_bf16(dy: torch.Tensor, w_t: torch.Tensor, u: torch.Tensor, out: Optional[torch.Tensor] = None):
     """du [M,2H] (interleaved, like u) from dy [M,K] and w_t [H,K] = the SwiGLU output projection transposed: the product
-    ds = dy w_t^T never leaves the registers."""
+    ds = dy w_t^T never leaves the registers.  ``out``: a row-pitched bf16 buffer to write into instead of a fresh one."""
     lib = load(); dev = _require_hip(dy, w_t, u)
     dy, ldx = _rows2d(dy)
     M, K = dy.shape
     H = w_t.shape[0]
-    du = torch.empty(M, 2 * H, device=dev, dtype=torch.bfloat16)
+    du = torch.empty(M, 2 * H, device=dev, dtype=torch.bfloat16) if out is None else _given(out, (M, 2 * H), torch.bfloat16, True)
     with torch.cuda.device(dev):
-        _call(lib.vsde_linear_bf16, _ptr(dy), _i64(ldx), _ptr(w_t), None, _ptr(du), _i64(2 * H), _i64(M), ctypes.c_int(H),
+        _call(lib.vsde_linear_bf16, _ptr(dy), _i64(ldx), _ptr(w_t), None, _ptr(du), _i64(du.stride(0)), _i64(M), ctypes.c_int(H),
               ctypes.c_int(K), ctypes.c_int(EPI_SWIGLU_BWD), None, _i64(0), _ptr(u), _i64(u.stride(0)), _stream(dev))
     return du
