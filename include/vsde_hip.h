@@ -595,6 +595,33 @@ int vsde_crn_kinetic_particle_filter(const vsde_crn_network *net, const vsde_crn
                                      const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
                                      float *filtered_mean, float *filtered_std, float *particles, int *ancestors, void *stream);
 
+/* Guided particle filter (proposal = "bridge": the modified diffusion bridge, viforsdes_amd/inference/particle_filter.py is the
+ * specification): vsde_particle_filter with every Euler step drawn from a Gaussian pulled towards the next observation and the
+ * ratio model / proposal carried in the log-weight, so log p^ stays unbiased.  Same arguments, same checks, same noise stream and
+ * the same rules from the log-weight on; in addition S <= 4 and O <= 4 (VSDE_E_BADARG otherwise).  Step t -> t + 1 of a particle
+ * at x, with k the first observation whose row exceeds t, n = obs_rows[k] - t, f / G the drift / diffusion factor at x:
+ * A = sqrt(time_step) H G, psi = n A A^T + variance I = R R^T, W = R^-1 A, r = R^-1 (y_k - H (x + n time_step f)), m = W^T r,
+ * C = I - W^T W = M M^T (lower factor, every pivot floored at 1e-6 before its square root), eps = m + M z with z the stream's
+ * normals of the step, x' = x + f time_step + sqrt(time_step) G eps, then the 1e-6 clamp; lr += -|eps|^2 / 2 + |z|^2 / 2 +
+ * sum_j log M_jj.  At observation k: lw_j = lr_j + the Gaussian term of vsde_particle_filter, then lr = 0.
+ * log_weights [m][k][N] (those lw) is optional like particles (NULL = not written). */
+int vsde_guided_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
+                                const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                                const uint32_t *key, double time_step, const uint8_t *positive_mask_host, float *log_likelihood,
+                                float *increments, float *ess, float *filtered_mean, float *filtered_std, float *particles,
+                                int *ancestors, float *log_weights, void *stream);
+int vsde_crn_guided_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
+                                    const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                    double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                    float *log_likelihood, float *increments, float *ess, float *filtered_mean, float *filtered_std,
+                                    float *particles, int *ancestors, float *log_weights, void *stream);
+int vsde_crn_kinetic_guided_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P,
+                                            int K, int O, const float *x0, const float *rates, const int *obs_rows,
+                                            const float *obs_values, const float *obs_matrix, double variance, const uint32_t *key,
+                                            double time_step, const uint8_t *positive_mask_host, float *log_likelihood,
+                                            float *increments, float *ess, float *filtered_mean, float *filtered_std,
+                                            float *particles, int *ancestors, float *log_weights, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

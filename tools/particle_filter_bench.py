@@ -9,7 +9,12 @@ them.  Bytes: what the kernel route has to move (theta, start states, observatio
 out: O(M K S)) against the [M N, S]-sized tensors the torch route reads and writes per Euler step.
 There is no earlier version of the feature to compare with: the torch route on the same device is the baseline.
 
-    python tools/particle_filter_bench.py [--m 1024] [--n 1024] [--reps 200] [--torch-reps 2]"""
+``--proposal bridge`` runs the guided filter instead; ``--proposal both`` adds, per case, what the proposal is for: ONE theta (the
+Lotka-Volterra example at the classical values 0.5, 0.0025, 0.3 with its own observation variance 1.0; the SIR case at 0.004, 0.15)
+repeated over ``--m`` filters with one key, so the spread of ``log p^`` over the filters is the estimator's own noise -- its
+standard deviation and the time per kernel launch, for both proposals, and the ratio of the times.
+
+    python tools/particle_filter_bench.py [--m 1024] [--n 1024] [--reps 200] [--torch-reps 2] [--proposal bootstrap|bridge|both]"""
 import argparse
 import json
 import os
@@ -38,10 +43,31 @@ def timed(fn, warmup, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def noise(sde, obs, like, theta, dt, N, pos, a):
+    """Time per kernel launch and the standard deviation of log p^ over ``--m`` filters of ONE theta, for both proposals."""
+    obs, theta = obs.to(DEV), theta.to(DEV).expand(a.m, -1).contiguous()
+    key = torch.tensor([2468, 1357], dtype=torch.int32, device=DEV)
+    out = {"M": a.m, "N": N, "theta": [round(float(v), 6) for v in theta[0]], "variance": float(like.variance)}
+    for proposal in ("bootstrap", "bridge"):
+        run = lambda: particle_filter(sde, obs, like, theta, dt, n_particles=N, positive_dims=pos, key=key, proposal=proposal)
+        t1 = timed(run, a.warmup, a.reps)
+        t2 = timed(run, 0, a.reps)
+        res = run()
+        ll = res.log_likelihood.double()
+        ok = torch.isfinite(ll)
+        out[proposal] = {"kernel_ms": round(min(t1, t2), 4), "kernel_ms_runs": [round(t1, 4), round(t2, 4)],
+                         "log_likelihood_mean": round(float(ll[ok].mean()), 4), "log_likelihood_std": round(float(ll[ok].std()), 4),
+                         "finite_fraction": float(ok.double().mean()),
+                         "min_particle_ess": round(float(res.effective_sample_size.min()), 1),
+                         "median_min_particle_ess": round(float(res.effective_sample_size.min(dim=1).values.median()), 1)}
+    out["time_ratio_bridge_over_bootstrap"] = round(out["bridge"]["kernel_ms"] / out["bootstrap"]["kernel_ms"], 2)
+    return out
+
+
 def compare(sde, obs, like, theta, dt, N, pos, a):
     obs, theta = obs.to(DEV), theta.to(DEV)
     key = torch.tensor([12345, 678], dtype=torch.int32, device=DEV)
-    run = lambda: particle_filter(sde, obs, like, theta, dt, n_particles=N, positive_dims=pos, key=key)
+    run = lambda: particle_filter(sde, obs, like, theta, dt, n_particles=N, positive_dims=pos, key=key, proposal=a.proposal)
     M, P = theta.shape
     S, (K, O) = sde.state_dim, obs.values.shape
     T = int(torch.round(obs.times[-1] / dt))
@@ -75,6 +101,7 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--torch-reps", type=int, default=2)
+    ap.add_argument("--proposal", choices=["bootstrap", "bridge", "both"], default="bootstrap")
     a = ap.parse_args()
     from viforsdes_amd.examples.sdes import lv_problem
     g = torch.Generator().manual_seed(0)
@@ -85,9 +112,14 @@ def main():
     sir_obs = Observations(times=torch.tensor([0.0, 5.0, 10.0, 15.0, 20.0]),
                            values=torch.tensor([[95.0, 5.0], [85.0, 8.0], [72.0, 11.0], [60.0, 12.0], [50.0, 11.0]]))
     sir_th = torch.tensor([0.004, 0.15]) * (1.0 + 0.1 * torch.rand(a.m, 2, generator=g))
-    rec = {"tool": "particle_filter_bench", "device": torch.cuda.get_device_name(DEV),
-           "lv": compare(lv, lv_obs, lv_like, lv_th, lv_dt, a.n, lv_pos, a),
-           "sir": compare(sir, sir_obs, GaussianObservationLikelihood(variance=1.0), sir_th, 0.1, a.n, [0, 1], a)}
+    sir_like = GaussianObservationLikelihood(variance=1.0)
+    rec = {"tool": "particle_filter_bench", "device": torch.cuda.get_device_name(DEV), "proposal": a.proposal}
+    if a.proposal == "both":
+        rec["lv_noise"] = noise(lv, lv_obs, lv_like, torch.tensor([[0.5, 0.0025, 0.3]]), lv_dt, a.n, lv_pos, a)
+        rec["sir_noise"] = noise(sir, sir_obs, sir_like, torch.tensor([[0.004, 0.15]]), 0.1, a.n, [0, 1], a)
+    else:
+        rec["lv"] = compare(lv, lv_obs, lv_like, lv_th, lv_dt, a.n, lv_pos, a)
+        rec["sir"] = compare(sir, sir_obs, sir_like, sir_th, 0.1, a.n, [0, 1], a)
     print(json.dumps(rec))
 
 

@@ -66,6 +66,7 @@ EXPORTS = (
     "vsde_crn_forecast", "vsde_crn_log_weights", "vsde_crn_kinetic_sde_coefficients_fwd", "vsde_crn_kinetic_sde_coefficients_bwd",
     "vsde_crn_kinetic_euler_maruyama_fwd", "vsde_crn_kinetic_euler_maruyama_bwd", "vsde_crn_kinetic_forecast",
     "vsde_crn_kinetic_log_weights", "vsde_particle_filter", "vsde_crn_particle_filter", "vsde_crn_kinetic_particle_filter",
+    "vsde_guided_particle_filter", "vsde_crn_guided_particle_filter", "vsde_crn_kinetic_guided_particle_filter",
     "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
@@ -431,22 +432,23 @@ def forecast(kind: str, x_start, theta, n_steps: int, out_steps, key, time_step:
 
 
 PF_MAX_STATE, PF_MAX_OBS, PF_MAX_PARTICLES = 16, 16, 1024
+PF_GUIDED_MAX_STATE, PF_GUIDED_MAX_OBS = 4, 4
 
 
-def particle_filter_max_particles(kind: str, state_dim: int) -> int:
+def particle_filter_max_particles(kind: str, state_dim: int, proposal: str = "bootstrap") -> int:
     """The largest ``n_particles`` (a multiple of 64) the filter kernel of a built-in SDE takes (csrc/vsde_filter.hip: pf_max_n):
-    1024, and 512 for a reaction network of 5..8 species (its step needs more than the 128 registers of a 1024-thread workgroup)."""
+    1024, and 512 for a reaction network of 5..8 species (its step needs more than the 128 registers of a 1024-thread workgroup).
+    ``proposal="bridge"``: the guided step fits those registers up to state_dim 3; at state_dim 4 its instantiations are built
+    for 512 threads: 512."""
+    if proposal not in ("bootstrap", "bridge"):
+        raise ValueError(f"proposal must be 'bootstrap' or 'bridge', got {proposal!r}")
+    if proposal == "bridge" and state_dim > 3:
+        return PF_MAX_PARTICLES // 2
     return PF_MAX_PARTICLES // 2 if kind == "reaction_network" and state_dim > 4 else PF_MAX_PARTICLES
 
 
-def particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, key, time_step: float,
-                    n_particles: int, positive_dims=(), network=None, return_particles: bool = False):
-    """Bootstrap particle filters of a built-in model SDE (``kind`` in SDE_KINDS), one per row of theta [M, P] (the effective
-    constants [M, 2R] for a CrnKineticRoute) from the start states x0 [M, S], against obs_values [K, O] at the grid rows obs_rows
-    (int32 device tensor [K]) with a Gaussian observation term (obs_matrix [O, S] or None); noise and resampling uniforms come from
-    the Philox stream of ``key`` (2 int32 words on the device).  See include/vsde_hip.h: vsde_particle_filter.  Returns
-    (log_likelihood [M], increments [M, K], effective_sample_size [M, K], filtered_mean [M, K, S], filtered_std [M, K, S],
-    particles [M, K, N, S] or None, ancestors [M, K, N] int32 or None)."""
+def _particle_filter(entry: str, want_lw: bool, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
+                     n_particles, positive_dims, network, return_particles):
     lib = load()
     dev = _require_hip(x0, theta, obs_rows, obs_values, obs_matrix, key)
     x0, theta, obs_values = _f32c(x0), _f32c(theta), _f32c(obs_values)
@@ -470,11 +472,35 @@ def particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, vari
         keep = return_particles and 0 < N <= PF_MAX_PARTICLES   # a bad N is the entry point's to refuse: allocate nothing for it
         particles = torch.empty(M, K, N, S, **f32) if keep else None
         ancestors = torch.empty(M, K, N, device=dev, dtype=torch.int32) if keep else None
-        _call(*_sde_entry(lib, "particle_filter", kind, network), ctypes.c_int(M), ctypes.c_int(N), ctypes.c_int(S),
+        extra = ()
+        if want_lw:
+            extra = (torch.empty(M, K, N, **f32) if keep else None,)
+        _call(*_sde_entry(lib, entry, kind, network), ctypes.c_int(M), ctypes.c_int(N), ctypes.c_int(S),
               ctypes.c_int(theta.shape[1]), ctypes.c_int(K), ctypes.c_int(O), _ptr(x0), _ptr(theta), _ptr(obs_rows), _ptr(obs_values),
               _ptr(obs_matrix), ctypes.c_double(variance), _ptr(key), ctypes.c_double(time_step), _mask_bytes(positive_dims, S),
-              _ptr(loglik), _ptr(incr), _ptr(ess), _ptr(mean), _ptr(std), _ptr(particles), _ptr(ancestors), _stream(dev))
-    return loglik, incr, ess, mean, std, particles, ancestors
+              _ptr(loglik), _ptr(incr), _ptr(ess), _ptr(mean), _ptr(std), _ptr(particles), _ptr(ancestors),
+              *[_ptr(t) for t in extra], _stream(dev))
+    return (loglik, incr, ess, mean, std, particles, ancestors) + extra
+
+
+def particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, key, time_step: float,
+                    n_particles: int, positive_dims=(), network=None, return_particles: bool = False):
+    """Bootstrap particle filters of a built-in model SDE (``kind`` in SDE_KINDS), one per row of theta [M, P] (the effective
+    constants [M, 2R] for a CrnKineticRoute) from the start states x0 [M, S], against obs_values [K, O] at the grid rows obs_rows
+    (int32 device tensor [K]) with a Gaussian observation term (obs_matrix [O, S] or None); noise and resampling uniforms come from
+    the Philox stream of ``key`` (2 int32 words on the device).  See include/vsde_hip.h: vsde_particle_filter.  Returns
+    (log_likelihood [M], increments [M, K], effective_sample_size [M, K], filtered_mean [M, K, S], filtered_std [M, K, S],
+    particles [M, K, N, S] or None, ancestors [M, K, N] int32 or None)."""
+    return _particle_filter("particle_filter", False, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
+                            n_particles, positive_dims, network, return_particles)
+
+
+def guided_particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, key, time_step: float,
+                           n_particles: int, positive_dims=(), network=None, return_particles: bool = False):
+    """``particle_filter`` with the bridge proposal (include/vsde_hip.h: vsde_guided_particle_filter; S <= 4, O <= 4): the same
+    arguments, and the same 7 outputs followed by log_weights [M, K, N] or None."""
+    return _particle_filter("guided_particle_filter", True, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key,
+                            time_step, n_particles, positive_dims, network, return_particles)
 
 
 def _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean, post_log_std, theta_positive_dims):

@@ -7,6 +7,9 @@
 // scan of the weights (wave scan by cross-lane moves, wave totals through LDS); cumulative sums and particle states go to LDS
 // (row stride S | 1: the gather below is not a bank conflict), every thread finds its ancestor by binary search over the cumulative
 // sums (systematic resampling, one uniform per (filter, observation)) and reads that state row.
+// The guided variant (template argument NO > 0: proposal = "bridge", S <= 4, O <= NO in {2, 4}) replaces the Euler step by the
+// modified-diffusion-bridge step of the specification (pf_bridge_step) and carries the log-ratio model / proposal in one more
+// register to the observation; everything from the log-weight on is the same code.
 // LDS (dynamic): N cumulative sums + N (S | 1) state floats + 16 x 18 reduction slots: 73 KiB at N = 1024, S = 16.
 #include "vsde_sde_step.h"
 
@@ -18,7 +21,14 @@ constexpr int kPfRed = kPfWaves * (kPfMaxS + 2);   // floats of the reduction st
 // Particles per filter an instantiation is built for.  A 1024-thread workgroup leaves 128 VGPRs per lane; the reaction-network step
 // at 5..8 species (its S x S covariance and Cholesky factor in registers) needs more, so those instantiations are built for 512
 // threads (256 VGPRs) and refuse a larger N rather than spill.
-constexpr int pf_max_n(int kind, int S) { return kind == 4 && S > 4 ? kPfMaxN / 2 : kPfMaxN; }
+// The guided step (A, psi, W, C and their factors next to f and G) fits the 128 VGPRs up to S = 3 (at most 122); at S = 4 it
+// would spill (12..68 bytes of scratch per lane), so the guided S = 4 instantiations are 512-thread ones too.
+constexpr int pf_max_n(int kind, int S, bool guided = false) {
+    return (kind == 4 && S > 4) || (guided && S > 3) ? kPfMaxN / 2 : kPfMaxN;
+}
+
+constexpr int kPfGuidedMaxS = 4, kPfGuidedMaxO = 4;
+constexpr float kPfPivotFloor = 1e-6f;   // inference/particle_filter.py: BRIDGE_PIVOT_FLOOR
 
 struct PfParams {
     int M, N, S, P, K, O;
@@ -30,6 +40,9 @@ struct PfParams {
     uint32_t pos_mask;
     float dt, sqdt, inv_var, log_norm, log_n;
     CrnNet net;    // kind 4
+    // guided variant only (at the end: the bootstrap kernels read their arguments at the offsets they always had)
+    float var;
+    float *log_weights;
 };
 
 __device__ __forceinline__ float pf_wave_max(float v) {
@@ -107,11 +120,165 @@ __device__ __forceinline__ void pf_propagate(const PfParams &p, float *x, const 
     }
 }
 
+// in place: the lower triangle of a [N][N] -> its Cholesky factor; FLOOR: every pivot is floored at kPfPivotFloor before its square
+// root (NaN stays NaN).  inv[j] = 1 / L_jj
+template <int N, bool FLOOR> __device__ __forceinline__ void pf_chol(float *a, float *inv) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        float s = a[j * N + j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) s -= a[j * N + k] * a[j * N + k];
+        if constexpr (FLOOR) s = s < kPfPivotFloor ? kPfPivotFloor : s;
+        const float d = sqrtf(s);
+        a[j * N + j] = d;
+        inv[j] = 1.f / d;
+#pragma unroll
+        for (int i = j + 1; i < N; ++i) {
+            float v = a[i * N + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v -= a[i * N + k] * a[j * N + k];
+            a[i * N + j] = v * inv[j];
+        }
+    }
+}
+
+// One guided Euler step (modified diffusion bridge) of a particle at x towards the observation yk that is nleft grid steps ahead:
+// A = sqrt(dt) H G, psi = nleft A A^T + var I = R R^T, W = R^-1 A, r = R^-1 (yk - H (x + nleft dt f)), m = W^T r, C = I - W^T W =
+// M M^T (floored pivots), eps = m + M z, x <- clamp(x + f dt + sqrt(dt) G eps), lr += -|eps|^2 / 2 + |z|^2 / 2 + sum log M_jj.
+// Rows o >= O of A, psi and the residual are exact zeros (psi_oo = var), so they add nothing.  th: kinds 1, 2, 4 as em_load_theta /
+// crn_load_rates leave it; kind 3: th[i] = a_i, th[NS + i] = softplus(b_i) + 1e-3
+template <int KIND, int NS, int NR, bool KIN, int NO>
+__device__ __forceinline__ void pf_bridge_step(const PfParams &p, float *x, const float *th, const float *z, const float *yk,
+                                               float nleft, float &lr) {
+    float f[NS], G[NS * NS];
+    if constexpr (KIND == 4) {
+        crn_coef<NS, NR, KIN>(p.net, x, th, f, G);
+    } else if constexpr (KIND == 3) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            f[i] = -th[i] * x[i];
+#pragma unroll
+            for (int k = 0; k < NS; ++k) G[i * NS + k] = i == k ? th[NS + i] : 0.f;
+        }
+    } else {
+        coef_fwd<KIND>(x, th, f, G);
+    }
+    const float ndt = nleft * p.dt;
+    float A[NO * NS], e[NO];
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) A[o * NS + i] = 0.f;
+        e[o] = 0.f;
+        if (o < p.O) {
+            float pred = 0.f;
+            if (p.obs_matrix) {
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    const float h = p.obs_matrix[o * NS + k];
+                    pred += h * (x[k] + ndt * f[k]);
+#pragma unroll
+                    for (int i = 0; i <= k; ++i) A[o * NS + i] += h * G[k * NS + i];
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NS; ++i)
+                    if (i <= o && o < NS) A[o * NS + i] = G[(o < NS ? o : 0) * NS + i];
+                pred = x[o < NS ? o : 0] + ndt * f[o < NS ? o : 0];
+            }
+#pragma unroll
+            for (int i = 0; i < NS; ++i) A[o * NS + i] *= p.sqdt;
+            e[o] = yk[o] - pred;
+        }
+    }
+    float psi[NO * NO], rinv[NO];
+#pragma unroll
+    for (int o = 0; o < NO; ++o)
+#pragma unroll
+        for (int q = 0; q <= o; ++q) {
+            float acc = 0.f;
+#pragma unroll
+            for (int i = 0; i < NS; ++i) acc += A[o * NS + i] * A[q * NS + i];
+            psi[o * NO + q] = nleft * acc + (o == q ? p.var : 0.f);
+        }
+    pf_chol<NO, false>(psi, rinv);
+    // forward substitution, in place: A <- W = R^-1 A, e <- r = R^-1 e
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+#pragma unroll
+        for (int q = 0; q < o; ++q) {
+#pragma unroll
+            for (int i = 0; i < NS; ++i) A[o * NS + i] -= psi[o * NO + q] * A[q * NS + i];
+            e[o] -= psi[o * NO + q] * e[q];
+        }
+#pragma unroll
+        for (int i = 0; i < NS; ++i) A[o * NS + i] *= rinv[o];
+        e[o] *= rinv[o];
+    }
+    float C[NS * NS], minv[NS], eps[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        float mi = 0.f;
+#pragma unroll
+        for (int o = 0; o < NO; ++o) mi += A[o * NS + i] * e[o];
+        eps[i] = mi;
+#pragma unroll
+        for (int k = 0; k <= i; ++k) {
+            float acc = 0.f;
+#pragma unroll
+            for (int o = 0; o < NO; ++o) acc += A[o * NS + i] * A[o * NS + k];
+            C[i * NS + k] = (i == k ? 1.f : 0.f) - acc;
+        }
+    }
+    pf_chol<NS, true>(C, minv);
+    float dl = 0.f;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+#pragma unroll
+        for (int k = 0; k <= i; ++k) eps[i] += C[i * NS + k] * z[k];
+        dl += -0.5f * eps[i] * eps[i] + 0.5f * z[i] * z[i] + logf(C[i * NS + i]);
+    }
+    lr += dl;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k <= i; ++k) acc += G[i * NS + k] * eps[k];
+        const float y = x[i] + f[i] * p.dt + acc * p.sqdt;
+        f[i] = ((p.pos_mask >> i) & 1u) ? floor_nan(y) : y;
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) x[i] = f[i];
+}
+
+// guided steps t0 .. t1 - 1 of one particle towards the observation yk at grid row t1
+template <int KIND, int NS, int NR, bool KIN, int NO>
+__device__ __forceinline__ void pf_propagate_guided(const PfParams &p, float *x, const float *th, int t0, int t1, uint32_t b,
+                                                    uint32_t k0, uint32_t k1, const float *yk, float &lr) {
+    for (int blk = t0 >> 2; blk <= (t1 - 1) >> 2; ++blk) {
+        float z[NS][4];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) fc_normals((uint32_t)blk, (uint32_t)i, b, k0, k1, z[i]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int t = 4 * blk + q;
+            if (t >= t0 && t < t1) {
+                float zq[NS];
+#pragma unroll
+                for (int i = 0; i < NS; ++i) zq[i] = z[i][q];
+                pf_bridge_step<KIND, NS, NR, KIN, NO>(p, x, th, zq, yk, (float)(t1 - t), lr);
+            }
+        }
+    }
+}
+
 // workgroup = filter m (theta_m), thread = particle j.  NS: the state dim (kind 3: one instantiation per dim: a run-time dim under
 // `i < S` guards costs a hoisted 64-lane mask per guard and pushes the S = 16 kernel into scratch); NR: reaction bound
-template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false>
-__global__ void __launch_bounds__(pf_max_n(KIND, NS)) pf_kernel(PfParams p) {
-    constexpr int P = KIND == 3 ? 1 : KIN ? 2 * NR : NR;
+// NO: 0 = bootstrap; > 0 = the guided variant for O <= NO observed dims
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false, int NO = 0>
+__global__ void __launch_bounds__(pf_max_n(KIND, NS, NO > 0)) pf_kernel(PfParams p) {
+    constexpr bool GUIDED = NO > 0;
+    constexpr int P = KIND == 3 ? (GUIDED ? 2 * NS : 1) : KIN ? 2 * NR : NR;
     extern __shared__ __attribute__((aligned(16))) float pf_lds[];
     constexpr int S = NS, RS = S | 1;
     const int N = p.N;
@@ -122,15 +289,23 @@ __global__ void __launch_bounds__(pf_max_n(KIND, NS)) pf_kernel(PfParams p) {
     float x[NS], th[P];
 #pragma unroll
     for (int i = 0; i < NS; ++i) x[i] = i < S ? p.x0[(int64_t)m * S + i] : 0.f;
-    if constexpr (KIND == 3) th[0] = 0.f;
+    if constexpr (KIND == 3 && GUIDED) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            th[i] = p.theta[(int64_t)m * p.P + i];
+            th[NS + i] = softplus_f(p.theta[(int64_t)m * p.P + NS + i]) + 1e-3f;
+        }
+    } else if constexpr (KIND == 3) th[0] = 0.f;
     else if constexpr (KIN) crn_load_rates<NR>(th, p.theta, m, p.net.R, true);
     else em_load_theta<KIND, P>(th, p.theta, m, p.P, true);
     float loglik = 0.f;
+    [[maybe_unused]] float lr = 0.f;   // guided: log (model / proposal) of the steps since the last observation
     int row_prev = 0;
     for (int k = 0; k < p.K; ++k) {
         const int row = p.rows[k];
         if (row > row_prev) {
-            pf_propagate<KIND, NS, NR, KIN, P>(p, x, th, row_prev, row, b, k0, k1, m);
+            if constexpr (GUIDED) pf_propagate_guided<KIND, NS, NR, KIN, NO>(p, x, th, row_prev, row, b, k0, k1, p.obs_values + (int64_t)k * p.O, lr);
+            else pf_propagate<KIND, NS, NR, KIN, P>(p, x, th, row_prev, row, b, k0, k1, m);
             row_prev = row;
         }
         // Gaussian log-weight (the observation term of the ELBO tail kernel); NaN counts as -inf
@@ -153,7 +328,10 @@ __global__ void __launch_bounds__(pf_max_n(KIND, NS)) pf_kernel(PfParams p) {
                     lw += -0.5f * r * r * p.inv_var + p.log_norm;
                 }
         }
+        if constexpr (GUIDED) { lw += lr; lr = 0.f; }
         if (!(lw == lw)) lw = -__builtin_inff();
+        if constexpr (GUIDED)
+            if (p.log_weights) p.log_weights[((int64_t)m * p.K + k) * N + j] = lw;
         if (p.particles)
 #pragma unroll
             for (int i = 0; i < NS; ++i)
@@ -283,6 +461,20 @@ static int pf_fill(PfParams &p, int M, int N, int S, int P, int K, int O, const 
     return 0;
 }
 
+// the guided entry points: their own limits first, then the checks of pf_fill
+static int pf_fill_guided(PfParams &p, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
+                          const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, const uint32_t *key,
+                          double time_step, const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
+                          float *filtered_mean, float *filtered_std, float *particles, int *ancestors, float *log_weights) {
+    VSDE_CHECK_ARG(S >= 1 && S <= kPfGuidedMaxS, VSDE_E_BADARG, "guided particle filter: state_dim %d (1..%d supported)", S, kPfGuidedMaxS);
+    VSDE_CHECK_ARG(O >= 1 && O <= kPfGuidedMaxO, VSDE_E_BADARG, "guided particle filter: obs_dim %d (1..%d supported)", O, kPfGuidedMaxO);
+    int rc = pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step, positive_mask_host,
+                     log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
+    if (rc) return rc;
+    p.var = (float)variance; p.log_weights = log_weights;
+    return 0;
+}
+
 template <class Kern> static int pf_launch(Kern kern, const PfParams &p, void *stream, int max_n = kPfMaxN) {
     VSDE_CHECK_ARG(p.N <= max_n, VSDE_E_BADARG, "particle filter: %d particles (up to %d supported at state_dim %d of this SDE)", p.N,
                    max_n, p.S);
@@ -292,6 +484,22 @@ template <class Kern> static int pf_launch(Kern kern, const PfParams &p, void *s
     hipLaunchKernelGGL(kern, dim3(p.M), dim3(p.N), lds, (hipStream_t)stream, p);
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// the guided instantiation of (KIND, NS, NR, KIN) for the call's observation dim: the bound NO is 2 or 4
+template <int KIND, int NS, int NR, bool KIN> static int pf_launch_guided(const PfParams &p, void *stream) {
+    if (p.O <= 2) return pf_launch(pf_kernel<KIND, NS, NR, KIN, 2>, p, stream, pf_max_n(KIND, NS, true));
+    return pf_launch(pf_kernel<KIND, NS, NR, KIN, 4>, p, stream, pf_max_n(KIND, NS, true));
+}
+
+// crn_dispatch for the guided filter's S <= 4 (checked by pf_fill_guided)
+template <class F> static int pf_crn_dispatch_guided(int S, int R, F &&f) {
+    switch (S) {
+        case 1: return crn_dispatch_r<1>(R, f);
+        case 2: return crn_dispatch_r<2>(R, f);
+        case 3: return crn_dispatch_r<3>(R, f);
+        default: return crn_dispatch_r<4>(R, f);
+    }
 }
 
 }  // namespace vsde
@@ -355,5 +563,71 @@ extern "C" int vsde_crn_kinetic_particle_filter(const vsde_crn_network *net, con
     p.net = n;
     return crn_dispatch(S, n.R, [&](auto ns, auto nr) {
         return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value, true>, p, stream, pf_max_n(4, decltype(ns)::value));
+    });
+}
+
+extern "C" int vsde_guided_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
+                                           const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                                           const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                           float *log_likelihood, float *increments, float *ess, float *filtered_mean,
+                                           float *filtered_std, float *particles, int *ancestors, float *log_weights, void *stream) {
+    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);
+    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim");
+    PfParams p = {};
+    int rc = pf_fill_guided(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
+                            positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors,
+                            log_weights);
+    if (rc) return rc;
+    if (kind == 1) return pf_launch_guided<1, 1, EmDims<1>::P, false>(p, stream);
+    if (kind == 2) return pf_launch_guided<2, 2, EmDims<2>::P, false>(p, stream);
+    switch (S) {
+        case 1: return pf_launch_guided<3, 1, EmDims<3>::P, false>(p, stream);
+        case 2: return pf_launch_guided<3, 2, EmDims<3>::P, false>(p, stream);
+        case 3: return pf_launch_guided<3, 3, EmDims<3>::P, false>(p, stream);
+        default: return pf_launch_guided<3, 4, EmDims<3>::P, false>(p, stream);
+    }
+}
+
+extern "C" int vsde_crn_guided_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
+                                               const float *theta, const int *obs_rows, const float *obs_values,
+                                               const float *obs_matrix, double variance, const uint32_t *key, double time_step,
+                                               const uint8_t *positive_mask_host, float *log_likelihood, float *increments,
+                                               float *ess, float *filtered_mean, float *filtered_std, float *particles,
+                                               int *ancestors, float *log_weights, void *stream) {
+    PfParams p = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n);
+    if (rc) return rc;
+    rc = pf_fill_guided(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
+                        positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors,
+                        log_weights);
+    if (rc) return rc;
+    p.net = n;
+    return pf_crn_dispatch_guided(S, P, [&](auto ns, auto nr) {
+        return pf_launch_guided<4, decltype(ns)::value, decltype(nr)::value, false>(p, stream);
+    });
+}
+
+extern "C" int vsde_crn_kinetic_guided_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S,
+                                                       int P, int K, int O, const float *x0, const float *rates, const int *obs_rows,
+                                                       const float *obs_values, const float *obs_matrix, double variance,
+                                                       const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                                       float *log_likelihood, float *increments, float *ess, float *filtered_mean,
+                                                       float *filtered_std, float *particles, int *ancestors, float *log_weights,
+                                                       void *stream) {
+    PfParams p = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n, true);
+    if (!rc) rc = crn_kinetics(kin, S, n);
+    if (rc) return rc;
+    rc = pf_fill_guided(p, M, N, S, P, K, O, x0, rates, obs_rows, obs_values, obs_matrix, variance, key, time_step,
+                        positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors,
+                        log_weights);
+    if (rc) return rc;
+    p.net = n;
+    return pf_crn_dispatch_guided(S, n.R, [&](auto ns, auto nr) {
+        return pf_launch_guided<4, decltype(ns)::value, decltype(nr)::value, true>(p, stream);
     });
 }

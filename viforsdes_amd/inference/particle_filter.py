@@ -21,7 +21,35 @@ The algorithm, for filter ``m`` (parameters ``theta_m``, ``N`` particles, all st
 * randomness is the forecast kernel's stream (include/vsde_hip.h): the normal of filter m, particle slot j, GLOBAL grid step t,
   dim i is the normal of path ``b = m N + j``, step t, dim i for the call's key; the resampling uniform of (m, k) is
   ``((w0 >> 8) + 0.5) 2^-24`` with ``w0`` the first word of ``philox4x32_10({k, 0, m, 1}, key)``.  A slot keeps its own noise
-  stream across resampling.  Same key => same result."""
+  stream across resampling.  Same key => same result.
+
+``proposal="bridge"`` (a guided filter: the modified diffusion bridge of Durham-Gallant, in Golightly-Wilkinson's form for noisy
+linear-Gaussian observations) draws every Euler step from a Gaussian pulled towards the next observation and carries the ratio
+model / proposal in the weight, so ``exp(log_likelihood)`` stays unbiased while the particles arrive where the observation is: the
+filter to use when the bootstrap filter's ``effective_sample_size.min()`` is near 1 (sharply informative observations) and the drift
+changes little between observations (the proposal extrapolates it linearly over the steps that are left: across a long gap of a
+strongly nonlinear model it can be worse than the bootstrap filter; the particle ESS of the two runs tells).  It needs a
+``GaussianObservationLikelihood`` (the proposal is derived from its H and variance), no trained network, and exactly the normals the
+bootstrap filter uses.  With D = time_step, f = drift(x, theta), L = diffusion(x, theta) [S, S], H = obs_matrix (identity when
+absent, O = S) and v = variance, the Euler step t -> t + 1 of a particle at x is:
+
+* k = the first observation with ``rows[k] > t``, n = ``rows[k] - t``;
+* A = sqrt(D) H L [O, S];  psi = n A A^T + v I [O, O];  e = y_k - H (x + n D f);
+* with psi = R R^T (lower Cholesky factor), W = R^-1 A and r = R^-1 e:  m = W^T r (= A^T psi^-1 e) and C = I_S - W^T W
+  (= I - A^T psi^-1 A);
+* M = the lower Cholesky factor of C with every pivot floored at ``BRIDGE_PIVOT_FLOOR`` before its square root (in exact arithmetic
+  the pivots are >= v / (lambda_max(A A^T) + v) for n = 1 and >= 1 - 1 / n otherwise; any invertible M gives a valid weight because
+  the same M makes the draw and its density);
+* z [S] = the stream's normals of (path b = m N + j, global step t), eps = m + M z, x' = x + f D + sqrt(D) L eps, then the 1e-6
+  clamp of the positive dims;
+* the particle's running log-ratio:  ``lr += -|eps|^2 / 2 + |z|^2 / 2 + sum_j log M_jj``  (model over proposal in noise space, so
+  it stays valid where the diffusion factor is floored or singular, and under the clamp).
+
+At observation k ``lw_j = lr_j + log p(y_k | x_j)`` (NaN counts as -inf) and everything after that is the bootstrap rule with this
+``lw``; ``lr`` is zero after every observation, so later observations on the same grid row get the plain Gaussian weight.  For n = 1
+the step ratio plus the observation term is ``log N(y; H (x + f D), D H L L^T H^T + v I)`` whatever z is (the fully adapted filter).
+The kernel takes the bridge for built-in SDEs with S <= 4 and O <= 4 (``_hip.particle_filter_max_particles(kind, S, proposal)``
+particles at most); everything else runs the torch route."""
 from __future__ import annotations
 
 import math
@@ -37,6 +65,8 @@ from ..core.observations import GaussianObservationLikelihood, ObservationLikeli
 from ..core.sde import SDE, builtin_sde_route, kernel_theta
 
 HIP_FILTER = True   # set False to force the torch route (A/B tests)
+PROPOSALS = ("bootstrap", "bridge")
+BRIDGE_PIVOT_FLOOR = 1e-6   # floor of the pivots of C = I - A^T psi^-1 A before their square root (csrc/vsde_filter.hip: kPfPivotFloor)
 
 _M0, _M1, _W0, _W1, _MASK = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xFFFFFFFF
 
@@ -46,7 +76,8 @@ class ParticleFilterResult:
     """``log_likelihood [M]``: log p^(y | theta_m) given the start state; ``increments [M, K]``: log p^(y_k | y_<k, theta_m), whose sum
     over k it is; ``effective_sample_size [M, K]``: (sum w)^2 / sum w^2 of the weights at observation k, in [0, N];
     ``filtered_mean`` / ``filtered_std [M, K, S]``: weighted moments of the particles before resampling; ``particles [M, K, N, S]``
-    (those states) and ``ancestors [M, K, N]`` (int32), or None unless asked for."""
+    (those states) and ``ancestors [M, K, N]`` (int32), or None unless asked for; ``log_weights [M, K, N]``: the log-weights ``lw`` of
+    those states (bootstrap: the observation term; bridge: plus the running log-ratio), filled with ``particles``."""
     log_likelihood: Tensor
     increments: Tensor
     effective_sample_size: Tensor
@@ -54,6 +85,7 @@ class ParticleFilterResult:
     filtered_std: Tensor
     particles: Optional[Tensor] = None
     ancestors: Optional[Tensor] = None
+    log_weights: Optional[Tensor] = None
 
 
 def _mul_hi_lo(m: int, c: Tensor) -> tuple[Tensor, Tensor]:
@@ -150,12 +182,19 @@ def _validate(sde, observations, theta, time_step, n_particles, initial_state):
 def particle_filter(sde: SDE, observations: Observations, observation_likelihood: ObservationLikelihood, theta: Tensor,
                     time_step: float, n_particles: int = 1024, initial_state: Optional[Tensor] = None,
                     positive_dims: Sequence[int] = (), return_particles: bool = False,
-                    key: Optional[Tensor] = None) -> ParticleFilterResult:
-    """Bootstrap particle filters with ``n_particles`` particles, one per row of ``theta`` (``[M, P]``, or ``[P]`` for M = 1), all
+                    key: Optional[Tensor] = None, proposal: str = "bootstrap") -> ParticleFilterResult:
+    """Particle filters with ``n_particles`` particles, one per row of ``theta`` (``[M, P]``, or ``[P]`` for M = 1), all
     started at ``initial_state`` (``[S]`` or ``[M, S]``; default: the first observation).  The observation at the start row counts
     like any other, so ``log_likelihood`` targets what ``VariationalPosterior.log_evidence`` conditions on.  ``key``: two int32
     words (a tensor); default: drawn from torch's generator on theta's device, so ``torch.manual_seed`` makes the call repeatable
-    and a call captured in a HIP graph draws a fresh key per replay.  No gradients."""
+    and a call captured in a HIP graph draws a fresh key per replay.  ``proposal``: "bootstrap", or "bridge" for the guided filter
+    of the module docstring.  No gradients."""
+    if proposal not in PROPOSALS:
+        raise ValueError(f"proposal must be one of {PROPOSALS}, got {proposal!r}")
+    bridge = proposal == "bridge"
+    if bridge and not isinstance(observation_likelihood, GaussianObservationLikelihood):
+        raise ValueError("proposal='bridge' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
+                         f"variance (got {type(observation_likelihood).__name__})")
     theta, x0 = _validate(sde, observations, theta, time_step, n_particles, initial_state)
     dev = theta.device
     obs = observations if observations.values.device == dev else observations.to(dev)
@@ -168,20 +207,33 @@ def particle_filter(sde: SDE, observations: Observations, observation_likelihood
         key = key.reshape(2)
     pos = tuple(positive_dims)
     with torch.no_grad():
-        route = _kernel_route(sde, obs, observation_likelihood, theta, n_particles)
+        route = _kernel_route(sde, obs, observation_likelihood, theta, n_particles, proposal)
         if route is not None:
             from .. import _hip
             kind, network = route
             H = observation_likelihood.obs_matrix
             rows = torch.round(obs.times / time_step).to(torch.int32)
-            out = _hip.particle_filter(kind, x0, kernel_theta(network, theta), rows, obs.values, None if H is None else H.to(theta),
-                                       float(observation_likelihood.variance), key.to(torch.int32) if key.dtype != torch.int32 else key,
-                                       float(time_step), n_particles, pos, network=network, return_particles=return_particles)
-            return ParticleFilterResult(*out)
-        return _torch_filter(sde, obs, observation_likelihood, theta, float(time_step), n_particles, x0, pos, return_particles, key)
+            args = (kind, x0, kernel_theta(network, theta), rows, obs.values, None if H is None else H.to(theta),
+                    float(observation_likelihood.variance), key.to(torch.int32) if key.dtype != torch.int32 else key,
+                    float(time_step), n_particles, pos)
+            if bridge:
+                return ParticleFilterResult(*_hip.guided_particle_filter(*args, network=network, return_particles=return_particles))
+            out = _hip.particle_filter(*args, network=network, return_particles=return_particles)
+            lw = _gaussian_log_weights(observation_likelihood, obs.values, out[5]) if return_particles else None
+            return ParticleFilterResult(*out, lw)
+        return _torch_filter(sde, obs, observation_likelihood, theta, float(time_step), n_particles, x0, pos, return_particles, key,
+                             bridge)
 
 
-def _kernel_route(sde, obs, like, theta, n_particles):
+def _gaussian_log_weights(like, values, particles):
+    """``lw [M, K, N]`` of the bootstrap kernel's stored particles [M, K, N, S]: the observation term, NaN as -inf."""
+    M, K, N, S = particles.shape
+    y = values[None, :, None, :].expand(M, K, N, -1).reshape(M * K * N, -1)
+    lw = like.log_prob(y, particles.reshape(M * K * N, S)).reshape(M, K, N)
+    return torch.where(torch.isnan(lw), torch.full_like(lw, float("-inf")), lw)
+
+
+def _kernel_route(sde, obs, like, theta, n_particles, proposal="bootstrap"):
     """``builtin_sde_route(sde)`` when the filter kernel takes the call, else None."""
     if not (HIP_FILTER and theta.is_cuda and theta.dtype == torch.float32 and obs.values.dtype == torch.float32):
         return None
@@ -194,12 +246,49 @@ def _kernel_route(sde, obs, like, theta, n_particles):
     S, O, H = int(sde.state_dim), obs.values.shape[1], like.obs_matrix
     if S > _hip.PF_MAX_STATE or O > _hip.PF_MAX_OBS or (H is None and O != S) or (H is not None and tuple(H.shape) != (O, S)):
         return None
-    if n_particles % 64 != 0 or n_particles > _hip.particle_filter_max_particles(kind, S):
+    if proposal == "bridge" and (S > _hip.PF_GUIDED_MAX_STATE or O > _hip.PF_GUIDED_MAX_OBS):
+        return None
+    if n_particles % 64 != 0 or n_particles > _hip.particle_filter_max_particles(kind, S, proposal=proposal):
         return None
     return kind, network
 
 
-def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key) -> ParticleFilterResult:
+def _floored_cholesky(a: Tensor, floor: Optional[float] = None) -> Tensor:
+    """Lower Cholesky factor of a [B, n, n] (its lower triangle is read), column by column; ``floor``: every pivot is clamped there
+    before its square root.  Never raises: a NaN or indefinite matrix gives NaN entries."""
+    n = a.shape[-1]
+    out = torch.zeros_like(a)
+    for j in range(n):
+        s = a[:, j, j] - (out[:, j, :j] * out[:, j, :j]).sum(dim=-1)
+        if floor is not None:
+            s = s.clamp(min=floor)
+        d = s.sqrt()
+        out[:, j, j] = d
+        if j + 1 < n:
+            out[:, j + 1:, j] = (a[:, j + 1:, j] - (out[:, j + 1:, :j] * out[:, j:j + 1, :j]).sum(dim=-1)) / d[:, None]
+    return out
+
+
+def _bridge_step(sde, x, th, z, y, H, variance, n, dt, root_dt):
+    """One guided Euler step of the module docstring: (x' before the clamp [B, S], the step's log-ratio [B])."""
+    f, L = sde.drift(x, th), sde.diffusion(x, th)
+    A = root_dt * (L if H is None else torch.einsum("ok,bki->boi", H, L))
+    ahead = x + (n * dt) * f
+    e = y[None, :] - (ahead if H is None else ahead @ H.T)
+    O = A.shape[1]
+    psi = n * (A @ A.transpose(1, 2)) + variance * torch.eye(O, device=x.device, dtype=x.dtype)
+    R = _floored_cholesky(psi)
+    sol = torch.linalg.solve_triangular(R, torch.cat([A, e[..., None]], dim=-1), upper=False)
+    W, r = sol[..., :-1], sol[..., -1]
+    m = torch.einsum("boi,bo->bi", W, r)
+    C = torch.eye(x.shape[1], device=x.device, dtype=x.dtype) - W.transpose(1, 2) @ W
+    Mf = _floored_cholesky(C, BRIDGE_PIVOT_FLOOR)
+    eps = m + torch.einsum("bij,bj->bi", Mf, z)
+    lr = -0.5 * (eps * eps).sum(dim=-1) + 0.5 * (z * z).sum(dim=-1) + torch.log(torch.diagonal(Mf, dim1=1, dim2=2)).sum(dim=-1)
+    return x + f * dt + torch.einsum("bij,bj->bi", L, eps) * root_dt, lr
+
+
+def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, bridge=False) -> ParticleFilterResult:
     dev, dtype = theta.device, theta.dtype
     M, P = theta.shape
     S = x0.shape[1]
@@ -211,19 +300,30 @@ def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key) 
     root_dt = dt ** 0.5
     slot = torch.arange(N, device=dev)
     neg_inf = torch.tensor(float("-inf"), device=dev, dtype=dtype)
-    incr, ess, means, stds, parts, ancs = [], [], [], [], [], []
+    incr, ess, means, stds, parts, ancs, lws = [], [], [], [], [], [], []
     t, z, z_block = 0, None, -1
+    H = like.obs_matrix if bridge else None
+    H = None if H is None else H.to(device=dev, dtype=dtype)
+    lr = torch.zeros(M * N, device=dev, dtype=dtype) if bridge else None
     for k in range(K):
         while t < rows[k]:
             if t // 4 != z_block:
                 z_block = t // 4
                 z = stream_normals(M * N, z_block, S, key).to(dtype)
-            shock = torch.einsum("bij,bj->bi", sde.diffusion(x, th), z[..., t % 4])
-            x = x + sde.drift(x, th) * dt + shock * root_dt
+            if bridge:
+                x, step_lr = _bridge_step(sde, x, th, z[..., t % 4], obs.values[k].to(dtype), H, float(like.variance), rows[k] - t,
+                                          dt, root_dt)
+                lr = lr + step_lr
+            else:
+                shock = torch.einsum("bij,bj->bi", sde.diffusion(x, th), z[..., t % 4])
+                x = x + sde.drift(x, th) * dt + shock * root_dt
             if floor is not None:
                 x = torch.maximum(x, floor)
             t += 1
-        lw = like.log_prob(obs.values[k].to(dtype).unsqueeze(0).expand(M * N, -1), x).reshape(M, N)
+        lw = like.log_prob(obs.values[k].to(dtype).unsqueeze(0).expand(M * N, -1), x)
+        if bridge:
+            lw, lr = lw + lr, torch.zeros_like(lr)
+        lw = lw.reshape(M, N)
         lw = torch.where(torch.isnan(lw), neg_inf, lw)
         mx = lw.max(dim=1, keepdim=True).values
         dead = torch.isneginf(mx)
@@ -244,10 +344,12 @@ def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key) 
         if return_particles:
             parts.append(xm)
             ancs.append(anc.to(torch.int32))
+            lws.append(lw)
         x = torch.gather(xm, 1, anc[..., None].expand(-1, -1, S)).reshape(M * N, S)
     increments = torch.stack(incr, dim=1)
     return ParticleFilterResult(
         log_likelihood=increments.sum(dim=1), increments=increments, effective_sample_size=torch.stack(ess, dim=1),
         filtered_mean=torch.stack(means, dim=1), filtered_std=torch.stack(stds, dim=1),
         particles=torch.stack(parts, dim=1) if return_particles else None,
-        ancestors=torch.stack(ancs, dim=1) if return_particles else None)
+        ancestors=torch.stack(ancs, dim=1) if return_particles else None,
+        log_weights=torch.stack(lws, dim=1) if return_particles else None)

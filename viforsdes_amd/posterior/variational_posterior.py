@@ -146,7 +146,7 @@ class ParameterReweighting:
       draw whose cumulative normalised weight, in sorted order, reaches a), next to ``variational_mean`` / ``variational_std``, the
       plain moments of the same draws;
     * ``filter_effective_sample_size [n]``: the smallest particle ESS seen in each draw's filter -- near 1 the bootstrap filter
-      itself is starved (sharply informative observations) and ``log p^`` is noisy;
+      itself is starved (sharply informative observations) and ``log p^`` is noisy: rerun with ``proposal="bridge"``;
     * ``sde_parameters [n, P]``, ``log_likelihood [n]``, ``log_weights [n]`` (float64) when asked for, else None."""
     log_evidence: float
     standard_error: float
@@ -387,14 +387,22 @@ class VariationalPosterior:
 
     @torch.no_grad()
     def reweight_parameters(self, sde: SDE, observation_likelihood: ObservationLikelihood, n_samples: int = 1024,
-                            n_particles: int = 512, chunk_size: int = 256, return_draws: bool = True) -> ParameterReweighting:
+                            n_particles: int = 512, chunk_size: int = 256, return_draws: bool = True,
+                            proposal: str = "bootstrap") -> ParameterReweighting:
         """Is q(theta) any good?  Draws theta ~ q with the EMA weights as ``sample()`` draws them, estimates ``log p(y | theta)`` of
         the Euler-Maruyama-discretised model on this posterior's grid with a bootstrap particle filter (``particle_filter``:
         ``n_particles`` particles per theta, ``chunk_size`` thetas per call, start state = first observation as in
         ``log_evidence``), and weights the draws by ``p(theta) p^(y | theta) / q(theta)``.  Unlike ``log_evidence`` the variational
         paths do not enter, so a poor path posterior cannot hide a good theta posterior or the reverse; and unlike it this also
-        runs on a CPU posterior (the filter's torch route).  It touches none of ``sample()``'s caches or graphs."""
+        runs on a CPU posterior (the filter's torch route).  It touches none of ``sample()``'s caches or graphs.
+        ``proposal`` goes to ``particle_filter``: switch to ``"bridge"`` (the guided filter; Gaussian observation term only) when
+        ``filter_effective_sample_size.min()`` of a bootstrap run is near 1 -- the observations are then too informative for a
+        proposal that does not look at them, and ``log p^`` too noisy for the weights to mean much.  The bridge extrapolates the
+        drift linearly to the next observation: it pays when observations are a few steps apart or the drift changes little between
+        them, not across a long gap of a strongly nonlinear model (compare ``filter_effective_sample_size`` of the two)."""
         from ..inference import particle_filter as _pf
+        if proposal not in _pf.PROPOSALS:
+            raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
         if n_samples < 1 or chunk_size < 1 or n_particles < 1:
             raise ValueError(f"n_samples, n_particles and chunk_size must be >= 1 (got {n_samples}, {n_particles}, {chunk_size})")
         q = self.model.sde_parameter_posterior
@@ -413,7 +421,8 @@ class VariationalPosterior:
         min_ess = torch.empty(n_samples, device=theta.device, dtype=theta.dtype)
         for lo in range(0, n_samples, chunk_size):
             res = _pf.particle_filter(sde, self.observations, observation_likelihood, theta[lo:lo + chunk_size], self.time_step,
-                                      n_particles=n_particles, initial_state=x0, positive_dims=self.state_space.positive_dims)
+                                      n_particles=n_particles, initial_state=x0, positive_dims=self.state_space.positive_dims,
+                                      proposal=proposal)
             loglik[lo:lo + chunk_size] = res.log_likelihood
             min_ess[lo:lo + chunk_size] = res.effective_sample_size.min(dim=1).values
         log_w = log_prior.double() + loglik.double() - log_q
