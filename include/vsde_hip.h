@@ -445,6 +445,32 @@ int vsde_elbo_tail_bwd(int B, int K, int S, int O, int P, const float *x_obs, co
                        const float *g_out6, float *g_x_obs, float *g_theta, float *g_post_mean, float *g_post_log_std,
                        float *g_sde, float *g_gen, float *g_jac, void *stream);
 
+/* Count observation terms (core/observations.py: PoissonObservationLikelihood, NegativeBinomialObservationLikelihood).  The
+ * vsde_*count_* entry points mirror the entry point named after them with (lik_kind, scale, dispersion, row_const) in place of
+ * variance: lambda_o = max(scale (H x)_o, 1e-6) (torch.clamp: NaN propagates, no gradient where scale (H x)_o < 1e-6) and, per
+ * observed count y = obs_values[k][o],
+ *   VSDE_LIK_POISSON            log p = y log lambda - lambda - lgamma(y + 1)
+ *   VSDE_LIK_NEGATIVE_BINOMIAL  log p = lgamma(y + r) - lgamma(r) - lgamma(y + 1) + r log(r / (r + lambda)) + y log(lambda / (r + lambda))
+ * with r = dispersion > 0 (mean lambda, variance lambda + lambda^2 / r; ignored for Poisson).  The kernels evaluate the deviance
+ * form  y log(lambda / y) - (lambda - y)  resp.  y log(lambda / y) - (r + y) log((r + lambda) / (r + y))  (the y log term absent
+ * at y = 0) and add row_const[k] (DEVICE memory, K floats), the sum over o of the terms of y alone, which the caller computes:
+ *   Poisson  y log y - y - lgamma(y + 1);   NB  lgamma(y + r) - lgamma(r) - lgamma(y + 1) + r log r + y log y - (r + y) log(r + y).
+ * The same argument checks as the mirrored entry point, before any HIP call; in addition VSDE_E_BADARG for an unknown lik_kind,
+ * scale <= 0, dispersion <= 0 for the negative binomial, or row_const NULL while K > 0.  The counts are not checked (a negative
+ * or fractional y gives the formula's value). */
+#define VSDE_LIK_POISSON 1
+#define VSDE_LIK_NEGATIVE_BINOMIAL 2
+int vsde_count_elbo_tail_fwd(int B, int K, int S, int O, int P, const float *x_obs, const float *obs_values, const float *obs_matrix,
+                             int lik_kind, double scale, double dispersion, const float *row_const, const float *theta,
+                             int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std,
+                             const uint8_t *theta_positive_mask_host, const float *sde_lp, const float *gen_lp, const float *log_jac,
+                             float *out6, void *stream);
+int vsde_count_elbo_tail_bwd(int B, int K, int S, int O, int P, const float *x_obs, const float *obs_values, const float *obs_matrix,
+                             int lik_kind, double scale, double dispersion, const float *row_const, const float *theta,
+                             int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std,
+                             const uint8_t *theta_positive_mask_host, const float *g_out6, float *g_x_obs, float *g_theta,
+                             float *g_post_mean, float *g_post_log_std, float *g_sde, float *g_gen, float *g_jac, void *stream);
+
 /* Importance log-weights of posterior draws (VariationalPosterior.log_evidence): per sample b the ELBO integrand
  *   log_w[b] = obs + sum_t (sde_t - gen_t + jac_t) + prior - post
  * of vsde_elbo_path_terms + vsde_elbo_tail_fwd before their batch means, in one pass.  z[B][T+1][S] latent paths (softplus on
@@ -457,6 +483,13 @@ int vsde_log_weights(int kind, int B, int T, int S, int K, int O, int P, const f
                      const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std,
                      const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host,
                      const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
+/* vsde_log_weights with a count observation term (see vsde_count_elbo_tail_fwd). */
+int vsde_count_log_weights(int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol,
+                           const float *drift, const float *diffusion, const float *theta, const int *obs_rows,
+                           const float *obs_values, const float *obs_matrix, int lik_kind, double scale, double dispersion,
+                           const float *row_const, int prior_type, double prior_mean, double prior_std, const float *post_mean,
+                           const float *post_log_std, const uint8_t *state_positive_mask_host,
+                           const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
 /* Merge the first n entries of log_w into the running fp64 state (device memory, 6 doubles; start from
  * [-inf, 0, 0, 0, 0, 0]):  [M, sum exp(lw - M), sum exp(2 (lw - M)), sum lw, n, n_nonfinite], M the running max.  One
  * single-workgroup launch per chunk, no host synchronisation, bitwise deterministic.  NaN / +inf entries count in n_nonfinite
@@ -514,6 +547,13 @@ int vsde_crn_log_weights(const vsde_crn_network *net, int B, int T, int S, int K
                          const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std,
                          const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host,
                          const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
+/* vsde_crn_log_weights with a count observation term (see vsde_count_elbo_tail_fwd). */
+int vsde_crn_count_log_weights(const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z,
+                               const float *means, const float *chol, const float *theta, const int *obs_rows,
+                               const float *obs_values, const float *obs_matrix, int lik_kind, double scale, double dispersion,
+                               const float *row_const, int prior_type, double prior_mean, double prior_std, const float *post_mean,
+                               const float *post_log_std, const uint8_t *state_positive_mask_host,
+                               const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
 
 /* Rate laws of a reaction network (ReactionNetworkSDE(rate_laws=..., rate_constants=...)).  Reaction j follows law[j]:
  *   VSDE_CRN_LAW_MASS_ACTION      h_j = k_j prod_i x_i^r_ji                     (modifier / hill_n ignored)
@@ -559,6 +599,14 @@ int vsde_crn_kinetic_log_weights(const vsde_crn_network *net, const vsde_crn_kin
                                  double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean,
                                  const float *post_log_std, const uint8_t *state_positive_mask_host,
                                  const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream);
+/* vsde_crn_kinetic_log_weights with a count observation term (see vsde_count_elbo_tail_fwd). */
+int vsde_crn_kinetic_count_log_weights(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K, int O,
+                                       int P, int R_eff, const float *z, const float *means, const float *chol, const float *theta,
+                                       const float *rates, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                       int lik_kind, double scale, double dispersion, const float *row_const, int prior_type,
+                                       double prior_mean, double prior_std, const float *post_mean, const float *post_log_std,
+                                       const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host,
+                                       double time_step, float *log_w, void *stream);
 
 /* Bootstrap particle filter: log p^(y | theta_m) of the Euler-Maruyama-discretised built-in SDE with the Gaussian observation
  * term of vsde_elbo_tail_fwd, for M parameter vectors at once (viforsdes_amd/inference/particle_filter.py is the specification).
@@ -594,6 +642,28 @@ int vsde_crn_kinetic_particle_filter(const vsde_crn_network *net, const vsde_crn
                                      const float *obs_matrix, double variance, const uint32_t *key, double time_step,
                                      const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
                                      float *filtered_mean, float *filtered_std, float *particles, int *ancestors, void *stream);
+
+/* The bootstrap filter with a count observation term (see vsde_count_elbo_tail_fwd): vsde_particle_filter where only the log-weight
+ * at an observation differs, lw_j = row_const[k] + sum_o deviance term of (y_ko, lambda_o(x_j)), NaN as -inf; propagation, noise
+ * stream, increments, moments and resampling are the same code.  Particle limits: as vsde_particle_filter. */
+int vsde_count_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
+                               const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind, double scale,
+                               double dispersion, const float *row_const, const uint32_t *key, double time_step,
+                               const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
+                               float *filtered_mean, float *filtered_std, float *particles, int *ancestors, void *stream);
+int vsde_crn_count_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
+                                   const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                   int lik_kind, double scale, double dispersion, const float *row_const, const uint32_t *key,
+                                   double time_step, const uint8_t *positive_mask_host, float *log_likelihood, float *increments,
+                                   float *ess, float *filtered_mean, float *filtered_std, float *particles, int *ancestors,
+                                   void *stream);
+int vsde_crn_kinetic_count_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P,
+                                           int K, int O, const float *x0, const float *rates, const int *obs_rows,
+                                           const float *obs_values, const float *obs_matrix, int lik_kind, double scale,
+                                           double dispersion, const float *row_const, const uint32_t *key, double time_step,
+                                           const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
+                                           float *filtered_mean, float *filtered_std, float *particles, int *ancestors,
+                                           void *stream);
 
 /* Guided particle filter (proposal = "bridge": the modified diffusion bridge, viforsdes_amd/inference/particle_filter.py is the
  * specification): vsde_particle_filter with every Euler step drawn from a Gaussian pulled towards the next observation and the

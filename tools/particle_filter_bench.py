@@ -14,7 +14,12 @@ Lotka-Volterra example at the classical values 0.5, 0.0025, 0.3 with its own obs
 repeated over ``--m`` filters with one key, so the spread of ``log p^`` over the filters is the estimator's own noise -- its
 standard deviation and the time per kernel launch, for both proposals, and the ratio of the times.
 
-    python tools/particle_filter_bench.py [--m 1024] [--n 1024] [--reps 200] [--torch-reps 2] [--proposal bootstrap|bridge|both]"""
+``--likelihood poisson`` / ``negbin`` (dispersion ``--dispersion``, default 10) puts a count likelihood on both cases (the
+Lotka-Volterra observations rounded to integers) and runs the count instantiations of the kernel (vsde_count_particle_filter); the
+bridge proposal needs the Gaussian one.  ``--noise`` adds the one-theta record for the bootstrap proposal alone.
+
+    python tools/particle_filter_bench.py [--m 1024] [--n 1024] [--reps 200] [--torch-reps 2] [--proposal bootstrap|bridge|both]
+                                          [--likelihood gaussian|poisson|negbin] [--dispersion 10] [--noise]"""
 import argparse
 import json
 import os
@@ -24,7 +29,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from viforsdes_amd import GaussianObservationLikelihood, Observations, ReactionNetworkSDE, particle_filter  # noqa: E402
+from viforsdes_amd import (GaussianObservationLikelihood, NegativeBinomialObservationLikelihood, Observations,  # noqa: E402
+                           PoissonObservationLikelihood, ReactionNetworkSDE, particle_filter)
 from viforsdes_amd.inference import particle_filter as pf  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -43,12 +49,14 @@ def timed(fn, warmup, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def noise(sde, obs, like, theta, dt, N, pos, a):
-    """Time per kernel launch and the standard deviation of log p^ over ``--m`` filters of ONE theta, for both proposals."""
+def noise(sde, obs, like, theta, dt, N, pos, a, proposals=("bootstrap", "bridge")):
+    """Time per kernel launch and the standard deviation of log p^ over ``--m`` filters of ONE theta, for ``proposals``."""
     obs, theta = obs.to(DEV), theta.to(DEV).expand(a.m, -1).contiguous()
     key = torch.tensor([2468, 1357], dtype=torch.int32, device=DEV)
-    out = {"M": a.m, "N": N, "theta": [round(float(v), 6) for v in theta[0]], "variance": float(like.variance)}
-    for proposal in ("bootstrap", "bridge"):
+    out = {"M": a.m, "N": N, "theta": [round(float(v), 6) for v in theta[0]], "likelihood": type(like).__name__}
+    if hasattr(like, "variance"):
+        out["variance"] = float(like.variance)
+    for proposal in proposals:
         run = lambda: particle_filter(sde, obs, like, theta, dt, n_particles=N, positive_dims=pos, key=key, proposal=proposal)
         t1 = timed(run, a.warmup, a.reps)
         t2 = timed(run, 0, a.reps)
@@ -60,7 +68,8 @@ def noise(sde, obs, like, theta, dt, N, pos, a):
                          "finite_fraction": float(ok.double().mean()),
                          "min_particle_ess": round(float(res.effective_sample_size.min()), 1),
                          "median_min_particle_ess": round(float(res.effective_sample_size.min(dim=1).values.median()), 1)}
-    out["time_ratio_bridge_over_bootstrap"] = round(out["bridge"]["kernel_ms"] / out["bootstrap"]["kernel_ms"], 2)
+    if "bridge" in out and "bootstrap" in out:
+        out["time_ratio_bridge_over_bootstrap"] = round(out["bridge"]["kernel_ms"] / out["bootstrap"]["kernel_ms"], 2)
     return out
 
 
@@ -102,7 +111,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--torch-reps", type=int, default=2)
     ap.add_argument("--proposal", choices=["bootstrap", "bridge", "both"], default="bootstrap")
+    ap.add_argument("--likelihood", choices=["gaussian", "poisson", "negbin"], default="gaussian")
+    ap.add_argument("--dispersion", type=float, default=10.0)
+    ap.add_argument("--noise", action="store_true", help="add the one-theta record for the bootstrap proposal alone")
     a = ap.parse_args()
+    if a.likelihood != "gaussian" and a.proposal != "bootstrap":
+        ap.error("the bridge proposal needs --likelihood gaussian")
     from viforsdes_amd.examples.sdes import lv_problem
     g = torch.Generator().manual_seed(0)
     lv, lv_obs, lv_like, _, _, lv_dt, lv_pos, _ = lv_problem()
@@ -113,13 +127,21 @@ def main():
                            values=torch.tensor([[95.0, 5.0], [85.0, 8.0], [72.0, 11.0], [60.0, 12.0], [50.0, 11.0]]))
     sir_th = torch.tensor([0.004, 0.15]) * (1.0 + 0.1 * torch.rand(a.m, 2, generator=g))
     sir_like = GaussianObservationLikelihood(variance=1.0)
-    rec = {"tool": "particle_filter_bench", "device": torch.cuda.get_device_name(DEV), "proposal": a.proposal}
+    if a.likelihood != "gaussian":
+        lv_obs = Observations(times=lv_obs.times, values=torch.round(lv_obs.values))
+        lv_like = sir_like = (PoissonObservationLikelihood() if a.likelihood == "poisson"
+                              else NegativeBinomialObservationLikelihood(dispersion=a.dispersion))
+    rec = {"tool": "particle_filter_bench", "device": torch.cuda.get_device_name(DEV), "proposal": a.proposal,
+           "likelihood": a.likelihood}
     if a.proposal == "both":
         rec["lv_noise"] = noise(lv, lv_obs, lv_like, torch.tensor([[0.5, 0.0025, 0.3]]), lv_dt, a.n, lv_pos, a)
         rec["sir_noise"] = noise(sir, sir_obs, sir_like, torch.tensor([[0.004, 0.15]]), 0.1, a.n, [0, 1], a)
     else:
         rec["lv"] = compare(lv, lv_obs, lv_like, lv_th, lv_dt, a.n, lv_pos, a)
         rec["sir"] = compare(sir, sir_obs, sir_like, sir_th, 0.1, a.n, [0, 1], a)
+        if a.noise:
+            rec["lv_noise"] = noise(lv, lv_obs, lv_like, torch.tensor([[0.5, 0.0025, 0.3]]), lv_dt, a.n, lv_pos, a, (a.proposal,))
+            rec["sir_noise"] = noise(sir, sir_obs, sir_like, torch.tensor([[0.004, 0.15]]), 0.1, a.n, [0, 1], a, (a.proposal,))
     print(json.dumps(rec))
 
 

@@ -11,7 +11,8 @@ import os as _os
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 from .config import AmpDtype, EncoderConfig, HeadConfig, PretrainConfig, TrainingConfig, YamlConfig
-from .core.observations import GaussianObservationLikelihood, ObservationLikelihood, Observations
+from .core.observations import (GaussianObservationLikelihood, NegativeBinomialObservationLikelihood, ObservationLikelihood,
+                                Observations, PoissonObservationLikelihood)
 from .core.priors import Prior, PriorType
 from .core.reaction_network import Hill, MichaelisMenten, ReactionNetworkSDE
 from .core.sde import SDE, FunctionalSDE, make_sde
@@ -20,7 +21,8 @@ from .inference.particle_filter import ParticleFilterResult, particle_filter
 from .posterior.variational_posterior import EvidenceEstimate, ParameterReweighting, PosteriorPredictive, VariationalPosterior
 
 __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "TrainingConfig", "YamlConfig",
-           "GaussianObservationLikelihood", "ObservationLikelihood", "Observations", "Prior", "PriorType", "SDE",
+           "GaussianObservationLikelihood", "NegativeBinomialObservationLikelihood", "PoissonObservationLikelihood",
+           "ObservationLikelihood", "Observations", "Prior", "PriorType", "SDE",
            "FunctionalSDE", "Hill", "MichaelisMenten", "ReactionNetworkSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior",
            "EvidenceEstimate", "PosteriorPredictive", "ParameterReweighting", "ParticleFilterResult", "particle_filter"]
 __version__ = "0.1.0"

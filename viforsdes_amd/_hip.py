@@ -52,7 +52,10 @@ EXPORTS = (
     "vsde_head_forward_workspace_bytes", "vsde_head_forward",
     "vsde_head_backward_workspace_bytes", "vsde_head_backward",
     "vsde_elbo_path_terms", "vsde_elbo_path_terms_bwd", "vsde_elbo_tail_fwd", "vsde_elbo_tail_bwd",
-    "vsde_log_weights", "vsde_log_weight_accumulate",
+    "vsde_count_elbo_tail_fwd", "vsde_count_elbo_tail_bwd",
+    "vsde_log_weights", "vsde_log_weight_accumulate", "vsde_count_log_weights", "vsde_crn_count_log_weights",
+    "vsde_crn_kinetic_count_log_weights", "vsde_count_particle_filter", "vsde_crn_count_particle_filter",
+    "vsde_crn_kinetic_count_particle_filter",
     "vsde_profile_enable", "vsde_profile_elapsed_ms", "vsde_debug_force_v1", "vsde_debug_head_mp", "vsde_head_mfma_range_exceeded",
     "vsde_ln_modulate_fwd", "vsde_ln_modulate_bwd", "vsde_gated_residual_fwd", "vsde_gated_residual_bwd",
     "vsde_swiglu_fwd", "vsde_swiglu_bwd", "vsde_gate_merge_fwd", "vsde_gate_merge_bwd",
@@ -431,6 +434,19 @@ def forecast(kind: str, x_start, theta, n_steps: int, out_steps, key, time_step:
     return out
 
 
+def _observation_term(variance, n_rows: int, dev):
+    """(prefix of the entry point's name, its arguments) for the observation term of a tail / log-weight / filter call:
+    ``variance`` is the Gaussian variance (a number) or the ``CountKernelTerms`` (lik_kind, scale, dispersion, row_const [K]) of a
+    Poisson / negative-binomial likelihood, which select the ``vsde_*count_*`` form of the entry point."""
+    if not isinstance(variance, tuple):
+        return "", (ctypes.c_double(variance),)
+    lik_kind, scale, dispersion, row_const = variance
+    if not isinstance(row_const, torch.Tensor) or row_const.device != dev or row_const.numel() != n_rows:
+        raise ValueError(f"count likelihood: row constants [{n_rows}] on {dev} expected")
+    row_const = _f32c(row_const)
+    return "count_", (ctypes.c_int(int(lik_kind)), ctypes.c_double(scale), ctypes.c_double(dispersion), _ptr(row_const))
+
+
 PF_MAX_STATE, PF_MAX_OBS, PF_MAX_PARTICLES = 16, 16, 1024
 PF_GUIDED_MAX_STATE, PF_GUIDED_MAX_OBS = 4, 4
 
@@ -475,9 +491,12 @@ def _particle_filter(entry: str, want_lw: bool, kind, x0, theta, obs_rows, obs_v
         extra = ()
         if want_lw:
             extra = (torch.empty(M, K, N, **f32) if keep else None,)
-        _call(*_sde_entry(lib, entry, kind, network), ctypes.c_int(M), ctypes.c_int(N), ctypes.c_int(S),
+        prefix, term = _observation_term(variance, K, dev)
+        if prefix and want_lw:
+            raise ValueError("the guided particle filter needs a Gaussian observation term")
+        _call(*_sde_entry(lib, prefix + entry, kind, network), ctypes.c_int(M), ctypes.c_int(N), ctypes.c_int(S),
               ctypes.c_int(theta.shape[1]), ctypes.c_int(K), ctypes.c_int(O), _ptr(x0), _ptr(theta), _ptr(obs_rows), _ptr(obs_values),
-              _ptr(obs_matrix), ctypes.c_double(variance), _ptr(key), ctypes.c_double(time_step), _mask_bytes(positive_dims, S),
+              _ptr(obs_matrix), *term, _ptr(key), ctypes.c_double(time_step), _mask_bytes(positive_dims, S),
               _ptr(loglik), _ptr(incr), _ptr(ess), _ptr(mean), _ptr(std), _ptr(particles), _ptr(ancestors),
               *[_ptr(t) for t in extra], _stream(dev))
     return (loglik, incr, ess, mean, std, particles, ancestors) + extra
@@ -487,7 +506,8 @@ def particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, vari
                     n_particles: int, positive_dims=(), network=None, return_particles: bool = False):
     """Bootstrap particle filters of a built-in model SDE (``kind`` in SDE_KINDS), one per row of theta [M, P] (the effective
     constants [M, 2R] for a CrnKineticRoute) from the start states x0 [M, S], against obs_values [K, O] at the grid rows obs_rows
-    (int32 device tensor [K]) with a Gaussian observation term (obs_matrix [O, S] or None); noise and resampling uniforms come from
+    (int32 device tensor [K]) with a Gaussian observation term (obs_matrix [O, S] or None; ``variance``: a number) or a count term
+    (``variance``: the likelihood's ``CountKernelTerms``: vsde_count_particle_filter); noise and resampling uniforms come from
     the Philox stream of ``key`` (2 int32 words on the device).  See include/vsde_hip.h: vsde_particle_filter.  Returns
     (log_likelihood [M], increments [M, K], effective_sample_size [M, K], filtered_mean [M, K, S], filtered_std [M, K, S],
     particles [M, K, N, S] or None, ancestors [M, K, N] int32 or None)."""
@@ -504,10 +524,12 @@ def guided_particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matri
 
 
 def _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean, post_log_std, theta_positive_dims):
+    """(prefix of the entry point's name, the leading arguments); ``variance``: see ``_observation_term``."""
     B, K, S = x_obs.shape
     O, P = obs_values.shape[1], theta.shape[1]
-    return (ctypes.c_int(B), ctypes.c_int(K), ctypes.c_int(S), ctypes.c_int(O), ctypes.c_int(P), _ptr(x_obs), _ptr(obs_values),
-            _ptr(obs_matrix), ctypes.c_double(variance), _ptr(theta), ctypes.c_int(prior_type), ctypes.c_double(prior_mean),
+    prefix, term = _observation_term(variance, K, x_obs.device)
+    return prefix, (ctypes.c_int(B), ctypes.c_int(K), ctypes.c_int(S), ctypes.c_int(O), ctypes.c_int(P), _ptr(x_obs), _ptr(obs_values),
+            _ptr(obs_matrix), *term, _ptr(theta), ctypes.c_int(prior_type), ctypes.c_double(prior_mean),
             ctypes.c_double(prior_std), _ptr(post_mean), _ptr(post_log_std), _mask_bytes(theta_positive_dims, P))
 
 
@@ -521,9 +543,9 @@ def elbo_tail_fwd(x_obs, obs_values, obs_matrix, variance: float, theta, prior_t
     obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
     with torch.cuda.device(dev):
         out = torch.empty(6, device=dev, dtype=torch.float32)
-        _call(lib.vsde_elbo_tail_fwd, *_tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
-                                                  post_mean, post_log_std, theta_positive_dims),
-              _ptr(sde_lp), _ptr(gen_lp), _ptr(log_jac), _ptr(out), _stream(dev))
+        prefix, args = _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean,
+                                  post_log_std, theta_positive_dims)
+        _call(getattr(lib, f"vsde_{prefix}elbo_tail_fwd"), *args, _ptr(sde_lp), _ptr(gen_lp), _ptr(log_jac), _ptr(out), _stream(dev))
     return out
 
 
@@ -540,9 +562,9 @@ def elbo_tail_bwd(x_obs, obs_values, obs_matrix, variance: float, theta, prior_t
         g_x = torch.empty_like(x_obs); g_theta = torch.empty_like(theta)
         g_mean = torch.empty_like(post_mean); g_ls = torch.empty_like(post_log_std)
         g_paths = torch.empty(3, B, device=dev, dtype=torch.float32)
-        _call(lib.vsde_elbo_tail_bwd, *_tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
-                                                  post_mean, post_log_std, theta_positive_dims),
-              _ptr(g_out), _ptr(g_x), _ptr(g_theta), _ptr(g_mean), _ptr(g_ls), _ptr(g_paths[0]), _ptr(g_paths[1]), _ptr(g_paths[2]),
+        prefix, args = _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean,
+                                  post_log_std, theta_positive_dims)
+        _call(getattr(lib, f"vsde_{prefix}elbo_tail_bwd"), *args, _ptr(g_out), _ptr(g_x), _ptr(g_theta), _ptr(g_mean), _ptr(g_ls), _ptr(g_paths[0]), _ptr(g_paths[1]), _ptr(g_paths[2]),
               _stream(dev))
     return g_x, g_theta, g_mean, g_ls, g_paths[0], g_paths[1], g_paths[2]
 
@@ -570,7 +592,8 @@ def log_weights(kind: str | None, z, means, chol, drift, diffusion, theta, obs_r
         raise ValueError("log_weights: drift [B, T, S] and diffusion [B, T, S, S] are required without a built-in kind")
     dims = (ctypes.c_int(B), ctypes.c_int(T1 - 1), ctypes.c_int(S), ctypes.c_int(K), ctypes.c_int(O), ctypes.c_int(P),
             _ptr(z), _ptr(means), _ptr(chol))
-    tail = (_ptr(theta), _ptr(obs_rows), _ptr(obs_values), _ptr(obs_matrix), ctypes.c_double(variance),
+    prefix, term = _observation_term(variance, K, dev)
+    tail = (_ptr(theta), _ptr(obs_rows), _ptr(obs_values), _ptr(obs_matrix), *term,
             ctypes.c_int(prior_type), ctypes.c_double(prior_mean), ctypes.c_double(prior_std), _ptr(post_mean),
             _ptr(post_log_std), _mask_bytes(state_positive_dims, S), _mask_bytes(theta_positive_dims, P),
             ctypes.c_double(time_step))
@@ -580,14 +603,14 @@ def log_weights(kind: str | None, z, means, chol, drift, diffusion, theta, obs_r
             if rates is None or rates.ndim != 2 or rates.shape[0] != B:
                 raise ValueError("log_weights: a reaction network with rate laws needs its effective constants rates [B, 2R]")
             rates = _f32c(rates)
-            fn, net, kin = _sde_entry(lib, "log_weights", kind, network)
+            fn, net, kin = _sde_entry(lib, prefix + "log_weights", kind, network)
             _call(fn, net, kin, *dims[:6], ctypes.c_int(rates.shape[1]), *dims[6:], _ptr(theta), _ptr(rates), *tail[1:],
                   _ptr(out), _stream(dev))
         elif kind == "reaction_network":
-            fn, net = _sde_entry(lib, "log_weights", kind, network)
+            fn, net = _sde_entry(lib, prefix + "log_weights", kind, network)
             _call(fn, net, *dims, *tail, _ptr(out), _stream(dev))
         else:
-            _call(lib.vsde_log_weights, ctypes.c_int(0 if kind is None else SDE_KINDS[kind]), *dims, _ptr(drift), _ptr(diffusion),
+            _call(getattr(lib, f"vsde_{prefix}log_weights"), ctypes.c_int(0 if kind is None else SDE_KINDS[kind]), *dims, _ptr(drift), _ptr(diffusion),
                   *tail, _ptr(out), _stream(dev))
     return out
 

@@ -180,7 +180,7 @@ static uint32_t mask_bits(const uint8_t *m, int S) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The [B]-sized tail of the ELBO (inference/evidence_lower_bound.py:52-83 of the reference): Gaussian observation log-density
+// The [B]-sized tail of the ELBO (inference/evidence_lower_bound.py:52-83 of the reference): Gaussian (or, CNT, count) observation log-density
 // at the observed grid points (core/observations.py:57-74), iid Normal / LogNormal prior (core/priors.py:46-60), mean-field
 // (Log)Normal posterior log q(theta) (models/sde_parameter_posterior.py:44-66), and the batch means
 //   out = [ mean_b(obs + sde - gen + jac + prior - post), mean obs, mean sde, mean gen, mean prior, mean post ].
@@ -227,11 +227,14 @@ struct XObsRows {
 };
 
 // observation term of path b, its state at observation k read as x(k, i); when GX, also d obs_lp / d x_obs scaled by w
-template <bool GX, class X> __device__ __forceinline__ float tail_obs(const TailParams &p, int b, float w, const X &x) {
+// CNT: the count term c (vsde_sde_coef.h: count_term) in place of the Gaussian one
+template <bool GX, bool CNT, class X>
+__device__ __forceinline__ float tail_obs(const TailParams &p, const CountLik &c, int b, float w, const X &x) {
     float lp = 0.f;
     for (int k = 0; k < p.K; ++k) {
         float *gx = GX ? p.g_x_obs + ((int64_t)b * p.K + k) * p.S : nullptr;
         if (GX) for (int i = 0; i < p.S; ++i) gx[i] = 0.f;
+        if constexpr (CNT) lp += c.row_const[k];
         for (int o = 0; o < p.O; ++o) {
             float pred;
             if (p.obs_matrix) {
@@ -240,10 +243,12 @@ template <bool GX, class X> __device__ __forceinline__ float tail_obs(const Tail
             } else {
                 pred = x(k, o);
             }
+            [[maybe_unused]] float dterm = 0.f;   // count term: d term / d pred
             const float r = p.obs_values[k * p.O + o] - pred;
-            lp += -0.5f * r * r * p.inv_var + p.log_norm;
+            if constexpr (CNT) lp += count_term<GX>(c, p.obs_values[k * p.O + o], pred, dterm);
+            else lp += -0.5f * r * r * p.inv_var + p.log_norm;
             if (GX) {
-                const float gr = w * r * p.inv_var;   // d lp / d pred
+                const float gr = CNT ? w * dterm : w * r * p.inv_var;   // d lp / d pred
                 if (p.obs_matrix) for (int i = 0; i < p.S; ++i) gx[i] += gr * p.obs_matrix[o * p.S + i];
                 else gx[o] += gr;
             }
@@ -256,9 +261,10 @@ template <bool GX, class X> __device__ __forceinline__ float tail_obs(const Tail
 // log-weight kernel evaluate exactly this)
 struct TailTerms { float obs, prior, post; };
 
-template <class X> __device__ __forceinline__ TailTerms tail_terms(const TailParams &p, int b, const X &x) {
+template <bool CNT, class X>
+__device__ __forceinline__ TailTerms tail_terms(const TailParams &p, const CountLik &c, int b, const X &x) {
     TailTerms r;
-    r.obs = tail_obs<false>(p, b, 0.f, x);
+    r.obs = tail_obs<false, CNT>(p, c, b, 0.f, x);
     float prior = 0.f, post = 0.f;
     for (int i = 0; i < p.P; ++i) {
         const float th = p.theta[(int64_t)b * p.P + i];
@@ -274,12 +280,12 @@ template <class X> __device__ __forceinline__ TailTerms tail_terms(const TailPar
     return r;
 }
 
-__global__ void __launch_bounds__(256) elbo_tail_fwd_kernel(TailParams p) {
+template <bool CNT> __global__ void __launch_bounds__(256) elbo_tail_fwd_kernel(TailParams p, CountLik c) {
     __shared__ float red[256][6];
     const int tid = threadIdx.x;
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int b = tid; b < p.B; b += 256) {
-        const TailTerms tt = tail_terms(p, b, XObsRows{p, b});
+        const TailTerms tt = tail_terms<CNT>(p, c, b, XObsRows{p, b});
         const float obs = tt.obs, prior = tt.prior, post = tt.post;
         const float s = p.sde_lp[b], g = p.gen_lp[b];
         acc[0] += obs + s - g + p.jac[b] + prior - post;
@@ -289,7 +295,7 @@ __global__ void __launch_bounds__(256) elbo_tail_fwd_kernel(TailParams p) {
     if (tid < 6) p.out[tid] = acc[tid] / (float)p.B;
 }
 
-__global__ void __launch_bounds__(256) elbo_tail_bwd_kernel(TailParams p) {
+template <bool CNT> __global__ void __launch_bounds__(256) elbo_tail_bwd_kernel(TailParams p, CountLik c) {
     __shared__ float red[256][2 * kTailMaxDim];
     const int tid = threadIdx.x;
     const float ib = 1.f / (float)p.B, g0 = p.g_out[0];
@@ -299,7 +305,7 @@ __global__ void __launch_bounds__(256) elbo_tail_bwd_kernel(TailParams p) {
 #pragma unroll
     for (int i = 0; i < 2 * kTailMaxDim; ++i) gq[i] = 0.f;
     for (int b = tid; b < p.B; b += 256) {
-        tail_obs<true>(p, b, w_obs, XObsRows{p, b});
+        tail_obs<true, CNT>(p, c, b, w_obs, XObsRows{p, b});
         p.g_sde[b] = w_sde; p.g_gen[b] = w_gen; p.g_jac[b] = w_jac;
 #pragma unroll
         for (int i = 0; i < kTailMaxDim; ++i) {
@@ -322,6 +328,12 @@ __global__ void __launch_bounds__(256) elbo_tail_bwd_kernel(TailParams p) {
     }
     tail_block_sum<2 * kTailMaxDim>(red, gq, tid);
     if (tid < p.P) { p.g_post_mean[tid] = gq[tid]; p.g_post_log_std[tid] = gq[kTailMaxDim + tid]; }
+}
+
+// the count arguments of a vsde_*count_* entry point (NULL: the Gaussian form); checked after the shared checks
+struct CountArgs { int lik_kind; double scale, dispersion; const float *row_const; };
+static int count_fill(CountLik &c, const CountArgs *ca, int K) {
+    return ca ? count_lik(c, ca->lik_kind, ca->scale, ca->dispersion, ca->row_const, K) : 0;
 }
 
 static int tail_fill(TailParams &p, int B, int K, int S, int O, int P, const float *x_obs, const float *obs_values,
@@ -376,8 +388,8 @@ template <int S> struct XObsLatent {
     }
 };
 
-template <int KIND, int S, int NR = EmDims<KIND>::P, bool KIN = false>
-__global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p) {
+template <int KIND, int S, int NR = EmDims<KIND>::P, bool KIN = false, bool CNT = false>
+__global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p, CountLik c) {
     constexpr int PK = KIND == 3 ? 2 * S : KIND == 4 ? (KIN ? 2 * NR : NR) : 3;
     const int b = blockIdx.x;
     float th[PK];
@@ -432,23 +444,26 @@ __global__ void __launch_bounds__(256) log_weight_kernel(LogWeightParams p) {
     if (threadIdx.x == 0) {
         float path = 0.f;
         for (int i = 0; i < (int)(blockDim.x >> 6); ++i) path += red[i];
-        const TailTerms tt = tail_terms(p.tail, b, XObsLatent<S>{p, b});
+        const TailTerms tt = tail_terms<CNT>(p.tail, c, b, XObsLatent<S>{p, b});
         p.log_w[b] = tt.obs + path + tt.prior - tt.post;
     }
 }
 
+// c: the count observation term (its Gaussian instantiation when c is NULL)
 template <int KIND, int S, int NR = EmDims<KIND>::P, bool KIN = false>
-static int launch_log_weights(const LogWeightParams &p, hipStream_t s) {
-    hipLaunchKernelGGL((log_weight_kernel<KIND, S, NR, KIN>), dim3(p.tail.B), dim3(256), 0, s, p);
+static int launch_log_weights(const LogWeightParams &p, hipStream_t s, const CountLik *c = nullptr) {
+    if (c) hipLaunchKernelGGL((log_weight_kernel<KIND, S, NR, KIN, true>), dim3(p.tail.B), dim3(256), 0, s, p, *c);
+    else hipLaunchKernelGGL((log_weight_kernel<KIND, S, NR, KIN, false>), dim3(p.tail.B), dim3(256), 0, s, p, CountLik{});
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 // kinds 0 (caller's coefficients) and 3 (linear-diagonal) at any S in 1..16
-template <int KIND, int S = 1> static int dispatch_log_weights(int s_dim, const LogWeightParams &p, hipStream_t s) {
-    if (s_dim == S) return launch_log_weights<KIND, S>(p, s);
+template <int KIND, int S = 1>
+static int dispatch_log_weights(int s_dim, const LogWeightParams &p, hipStream_t s, const CountLik *c = nullptr) {
+    if (s_dim == S) return launch_log_weights<KIND, S>(p, s, c);
     if constexpr (S < kTailMaxDim) {
-        return dispatch_log_weights<KIND, S + 1>(s_dim, p, s);
+        return dispatch_log_weights<KIND, S + 1>(s_dim, p, s, c);
     } else {
         set_error("state_dim %d not supported by the log-weight kernel (1..%d)", s_dim, kTailMaxDim);
         return VSDE_E_STATE;
@@ -545,18 +560,63 @@ extern "C" int vsde_elbo_path_terms_bwd(int B, int T, int S, const float *z, con
     return dispatch_elbo(S, p, true, (hipStream_t)stream);
 }
 
+static int tail_fwd(const CountArgs *ca, int B, int K, int S, int O, int P, const float *x_obs, const float *obs_values,
+                    const float *obs_matrix, double variance, const float *theta, int prior_type, double prior_mean,
+                    double prior_std, const float *post_mean, const float *post_log_std,
+                    const uint8_t *theta_positive_mask_host, const float *sde_lp, const float *gen_lp,
+                    const float *log_jac, float *out6, void *stream) {
+    TailParams p = {};
+    CountLik c = {};
+    int rc = tail_fill(p, B, K, S, O, P, x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean,
+                       post_log_std, theta_positive_mask_host, sde_lp, gen_lp, log_jac);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(out6, VSDE_E_BADARG, "NULL output");
+    if ((rc = count_fill(c, ca, K))) return rc;
+    p.out = out6;
+    if (ca) hipLaunchKernelGGL(elbo_tail_fwd_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, c);
+    else hipLaunchKernelGGL(elbo_tail_fwd_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, c);
+    VSDE_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" int vsde_elbo_tail_fwd(int B, int K, int S, int O, int P, const float *x_obs, const float *obs_values,
                                   const float *obs_matrix, double variance, const float *theta, int prior_type, double prior_mean,
                                   double prior_std, const float *post_mean, const float *post_log_std,
                                   const uint8_t *theta_positive_mask_host, const float *sde_lp, const float *gen_lp,
                                   const float *log_jac, float *out6, void *stream) {
+    return tail_fwd(nullptr, B, K, S, O, P, x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
+                    post_mean, post_log_std, theta_positive_mask_host, sde_lp, gen_lp, log_jac, out6, stream);
+}
+
+extern "C" int vsde_count_elbo_tail_fwd(int B, int K, int S, int O, int P, const float *x_obs, const float *obs_values,
+                                        const float *obs_matrix, int lik_kind, double scale, double dispersion,
+                                        const float *row_const, const float *theta, int prior_type, double prior_mean,
+                                        double prior_std, const float *post_mean, const float *post_log_std,
+                                        const uint8_t *theta_positive_mask_host, const float *sde_lp, const float *gen_lp,
+                                        const float *log_jac, float *out6, void *stream) {
+    const CountArgs ca = {lik_kind, scale, dispersion, row_const};
+    return tail_fwd(&ca, B, K, S, O, P, x_obs, obs_values, obs_matrix, 1.0, theta, prior_type, prior_mean, prior_std, post_mean,
+                    post_log_std, theta_positive_mask_host, sde_lp, gen_lp, log_jac, out6, stream);
+}
+
+static int tail_bwd(const CountArgs *ca, int B, int K, int S, int O, int P, const float *x_obs, const float *obs_values,
+                    const float *obs_matrix, double variance, const float *theta, int prior_type, double prior_mean,
+                    double prior_std, const float *post_mean, const float *post_log_std,
+                    const uint8_t *theta_positive_mask_host, const float *g_out6, float *g_x_obs, float *g_theta,
+                    float *g_post_mean, float *g_post_log_std, float *g_sde, float *g_gen, float *g_jac, void *stream) {
     TailParams p = {};
+    CountLik c = {};
+    // the path-term inputs are not read by the backward: any non-NULL pointer satisfies the shared argument check
     int rc = tail_fill(p, B, K, S, O, P, x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean,
-                       post_log_std, theta_positive_mask_host, sde_lp, gen_lp, log_jac);
+                       post_log_std, theta_positive_mask_host, theta, theta, theta);
     if (rc) return rc;
-    VSDE_CHECK_ARG(out6, VSDE_E_BADARG, "NULL output");
-    p.out = out6;
-    hipLaunchKernelGGL(elbo_tail_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
+    VSDE_CHECK_ARG(g_out6 && (K == 0 || g_x_obs) && g_theta && g_post_mean && g_post_log_std && g_sde && g_gen && g_jac, VSDE_E_BADARG,
+                   "NULL argument");
+    p.g_out = g_out6; p.g_x_obs = g_x_obs; p.g_theta = g_theta; p.g_post_mean = g_post_mean; p.g_post_log_std = g_post_log_std;
+    if ((rc = count_fill(c, ca, K))) return rc;
+    p.g_sde = g_sde; p.g_gen = g_gen; p.g_jac = g_jac;
+    if (ca) hipLaunchKernelGGL(elbo_tail_bwd_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, c);
+    else hipLaunchKernelGGL(elbo_tail_bwd_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, p, c);
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -566,27 +626,26 @@ extern "C" int vsde_elbo_tail_bwd(int B, int K, int S, int O, int P, const float
                                   double prior_std, const float *post_mean, const float *post_log_std,
                                   const uint8_t *theta_positive_mask_host, const float *g_out6, float *g_x_obs, float *g_theta,
                                   float *g_post_mean, float *g_post_log_std, float *g_sde, float *g_gen, float *g_jac, void *stream) {
-    TailParams p = {};
-    // the path-term inputs are not read by the backward: any non-NULL pointer satisfies the shared argument check
-    int rc = tail_fill(p, B, K, S, O, P, x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean,
-                       post_log_std, theta_positive_mask_host, theta, theta, theta);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(g_out6 && (K == 0 || g_x_obs) && g_theta && g_post_mean && g_post_log_std && g_sde && g_gen && g_jac, VSDE_E_BADARG,
-                   "NULL argument");
-    p.g_out = g_out6; p.g_x_obs = g_x_obs; p.g_theta = g_theta; p.g_post_mean = g_post_mean; p.g_post_log_std = g_post_log_std;
-    p.g_sde = g_sde; p.g_gen = g_gen; p.g_jac = g_jac;
-    hipLaunchKernelGGL(elbo_tail_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
-    VSDE_CHECK_HIP(hipGetLastError());
-    return 0;
+    return tail_bwd(nullptr, B, K, S, O, P, x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
+                    post_mean, post_log_std, theta_positive_mask_host, g_out6, g_x_obs, g_theta, g_post_mean, g_post_log_std, g_sde,
+                    g_gen, g_jac, stream);
+}
+
+extern "C" int vsde_count_elbo_tail_bwd(int B, int K, int S, int O, int P, const float *x_obs, const float *obs_values,
+                                        const float *obs_matrix, int lik_kind, double scale, double dispersion,
+                                        const float *row_const, const float *theta, int prior_type, double prior_mean,
+                                        double prior_std, const float *post_mean, const float *post_log_std,
+                                        const uint8_t *theta_positive_mask_host, const float *g_out6, float *g_x_obs,
+                                        float *g_theta, float *g_post_mean, float *g_post_log_std, float *g_sde, float *g_gen,
+                                        float *g_jac, void *stream) {
+    const CountArgs ca = {lik_kind, scale, dispersion, row_const};
+    return tail_bwd(&ca, B, K, S, O, P, x_obs, obs_values, obs_matrix, 1.0, theta, prior_type, prior_mean, prior_std, post_mean,
+                    post_log_std, theta_positive_mask_host, g_out6, g_x_obs, g_theta, g_post_mean, g_post_log_std, g_sde, g_gen,
+                    g_jac, stream);
 }
 
 
-extern "C" int vsde_log_weights(int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means,
-                                const float *chol, const float *drift, const float *diffusion, const float *theta,
-                                const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
-                                int prior_type, double prior_mean, double prior_std, const float *post_mean,
-                                const float *post_log_std, const uint8_t *state_positive_mask_host,
-                                const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+static int log_weights_impl(const CountArgs *ca, int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *drift, const float *diffusion, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
     VSDE_CHECK_ARG(B > 0 && T > 0 && S > 0 && K >= 0, VSDE_E_BADARG, "bad log-weight dims B=%d T=%d S=%d K=%d", B, T, S, K);
     VSDE_CHECK_ARG(S <= kTailMaxDim, VSDE_E_STATE, "state_dim %d not supported by the log-weight kernel (1..%d)", S, kTailMaxDim);
     VSDE_CHECK_ARG(kind >= 0 && kind <= 3, VSDE_E_BADARG, "unknown SDE kind %d (0 = caller's coefficients, 1..3 built in)", kind);
@@ -601,15 +660,26 @@ extern "C" int vsde_log_weights(int kind, int B, int T, int S, int K, int O, int
     int rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
                        post_mean, post_log_std, theta_positive_mask_host, z, z, z);
     if (rc) return rc;
+    CountLik c = {};
+    if ((rc = count_fill(c, ca, K))) return rc;
     p.T = T; p.z = z; p.means = means; p.chol = chol; p.drift = drift; p.diffusion = diffusion; p.obs_rows = obs_rows;
     p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
     hipStream_t s = (hipStream_t)stream;
     switch (kind) {
-        case 1: return launch_log_weights<1, 1>(p, s);
-        case 2: return launch_log_weights<2, 2>(p, s);
-        case 3: return dispatch_log_weights<3>(S, p, s);
-        default: return dispatch_log_weights<0>(S, p, s);
+        case 1: return launch_log_weights<1, 1>(p, s, ca ? &c : nullptr);
+        case 2: return launch_log_weights<2, 2>(p, s, ca ? &c : nullptr);
+        case 3: return dispatch_log_weights<3>(S, p, s, ca ? &c : nullptr);
+        default: return dispatch_log_weights<0>(S, p, s, ca ? &c : nullptr);
     }
+}
+
+extern "C" int vsde_log_weights(int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *drift, const float *diffusion, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+    return log_weights_impl(nullptr, kind, B, T, S, K, O, P, z, means, chol, drift, diffusion, theta, obs_rows, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
+}
+
+extern "C" int vsde_count_log_weights(int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *drift, const float *diffusion, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind, double scale, double dispersion, const float *row_const, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+    const CountArgs ca = {lik_kind, scale, dispersion, row_const};
+    return log_weights_impl(&ca, kind, B, T, S, K, O, P, z, means, chol, drift, diffusion, theta, obs_rows, obs_values, obs_matrix, 1.0, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
 }
 
 extern "C" int vsde_log_weight_accumulate(int n, const float *log_w, double *state6, void *stream) {
@@ -620,12 +690,7 @@ extern "C" int vsde_log_weight_accumulate(int n, const float *log_w, double *sta
     return 0;
 }
 
-extern "C" int vsde_crn_log_weights(const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z,
-                                    const float *means, const float *chol, const float *theta, const int *obs_rows,
-                                    const float *obs_values, const float *obs_matrix, double variance, int prior_type,
-                                    double prior_mean, double prior_std, const float *post_mean, const float *post_log_std,
-                                    const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host,
-                                    double time_step, float *log_w, void *stream) {
+static int crn_log_weights_impl(const CountArgs *ca, const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
     LogWeightParams p = {};
     int rc = crn_net(net, S, P, p.net);
     if (rc) return rc;
@@ -635,20 +700,25 @@ extern "C" int vsde_crn_log_weights(const vsde_crn_network *net, int B, int T, i
     rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
                    post_mean, post_log_std, theta_positive_mask_host, z, z, z);
     if (rc) return rc;
+    CountLik c = {};
+    if ((rc = count_fill(c, ca, K))) return rc;
     p.T = T; p.z = z; p.means = means; p.chol = chol; p.obs_rows = obs_rows;
     p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
     return crn_dispatch(S, P, [&](auto ns, auto nr) {
-        return launch_log_weights<4, decltype(ns)::value, decltype(nr)::value>(p, (hipStream_t)stream);
+        return launch_log_weights<4, decltype(ns)::value, decltype(nr)::value>(p, (hipStream_t)stream, ca ? &c : nullptr);
     });
 }
 
-extern "C" int vsde_crn_kinetic_log_weights(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K,
-                                            int O, int P, int R_eff, const float *z, const float *means, const float *chol,
-                                            const float *theta, const float *rates, const int *obs_rows, const float *obs_values,
-                                            const float *obs_matrix, double variance, int prior_type, double prior_mean,
-                                            double prior_std, const float *post_mean, const float *post_log_std,
-                                            const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host,
-                                            double time_step, float *log_w, void *stream) {
+extern "C" int vsde_crn_log_weights(const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+    return crn_log_weights_impl(nullptr, net, B, T, S, K, O, P, z, means, chol, theta, obs_rows, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
+}
+
+extern "C" int vsde_crn_count_log_weights(const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind, double scale, double dispersion, const float *row_const, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+    const CountArgs ca = {lik_kind, scale, dispersion, row_const};
+    return crn_log_weights_impl(&ca, net, B, T, S, K, O, P, z, means, chol, theta, obs_rows, obs_values, obs_matrix, 1.0, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
+}
+
+static int crn_kinetic_log_weights_impl(const CountArgs *ca, const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K, int O, int P, int R_eff, const float *z, const float *means, const float *chol, const float *theta, const float *rates, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
     LogWeightParams p = {};
     int rc = crn_net(net, S, R_eff, p.net, true);
     if (rc) return rc;
@@ -660,9 +730,20 @@ extern "C" int vsde_crn_kinetic_log_weights(const vsde_crn_network *net, const v
     rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
                    post_mean, post_log_std, theta_positive_mask_host, z, z, z);
     if (rc) return rc;
+    CountLik c = {};
+    if ((rc = count_fill(c, ca, K))) return rc;
     p.T = T; p.z = z; p.means = means; p.chol = chol; p.obs_rows = obs_rows; p.rates = rates;
     p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
     return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
-        return launch_log_weights<4, decltype(ns)::value, decltype(nr)::value, true>(p, (hipStream_t)stream);
+        return launch_log_weights<4, decltype(ns)::value, decltype(nr)::value, true>(p, (hipStream_t)stream, ca ? &c : nullptr);
     });
+}
+
+extern "C" int vsde_crn_kinetic_log_weights(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K, int O, int P, int R_eff, const float *z, const float *means, const float *chol, const float *theta, const float *rates, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+    return crn_kinetic_log_weights_impl(nullptr, net, kin, B, T, S, K, O, P, R_eff, z, means, chol, theta, rates, obs_rows, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
+}
+
+extern "C" int vsde_crn_kinetic_count_log_weights(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K, int O, int P, int R_eff, const float *z, const float *means, const float *chol, const float *theta, const float *rates, const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind, double scale, double dispersion, const float *row_const, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+    const CountArgs ca = {lik_kind, scale, dispersion, row_const};
+    return crn_kinetic_log_weights_impl(&ca, net, kin, B, T, S, K, O, P, R_eff, z, means, chol, theta, rates, obs_rows, obs_values, obs_matrix, 1.0, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
 }

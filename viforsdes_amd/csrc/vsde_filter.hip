@@ -1,5 +1,5 @@
 // Bootstrap particle filter of the built-in SDEs (gfx950): log p^(y | theta) of the Euler-Maruyama-discretised model with a
-// Gaussian observation term, for M parameter vectors at once (viforsdes_amd/inference/particle_filter.py is the specification).
+// Gaussian or (template argument CNT) a Poisson / negative-binomial observation term, for M parameter vectors at once (viforsdes_amd/inference/particle_filter.py is the specification).
 // One launch runs whole filters: a workgroup per theta, a thread per particle; the particle's state, theta and the running
 // log-likelihood stay in registers from the first Euler step to the last.  Neither noise nor trajectory is stored: the normals come
 // from the forecast kernel's Philox stream (vsde_sde_step.h: fc_normals) with path index b = m N + j.
@@ -43,6 +43,8 @@ struct PfParams {
     // guided variant only (at the end: the bootstrap kernels read their arguments at the offsets they always had)
     float var;
     float *log_weights;
+    // count observation term (CNT instantiations only)
+    CountLik cl;
 };
 
 __device__ __forceinline__ float pf_wave_max(float v) {
@@ -275,9 +277,12 @@ __device__ __forceinline__ void pf_propagate_guided(const PfParams &p, float *x,
 // workgroup = filter m (theta_m), thread = particle j.  NS: the state dim (kind 3: one instantiation per dim: a run-time dim under
 // `i < S` guards costs a hoisted 64-lane mask per guard and pushes the S = 16 kernel into scratch); NR: reaction bound
 // NO: 0 = bootstrap; > 0 = the guided variant for O <= NO observed dims
-template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false, int NO = 0>
+// CNT: the count observation term (Poisson / negative binomial, a workgroup-uniform choice inside count_term) in place of the
+// Gaussian one; bootstrap only.  A compile-time argument: the Gaussian instantiations are the code they were
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false, int NO = 0, bool CNT = false>
 __global__ void __launch_bounds__(pf_max_n(KIND, NS, NO > 0)) pf_kernel(PfParams p) {
     constexpr bool GUIDED = NO > 0;
+    static_assert(!(GUIDED && CNT), "the bridge proposal is derived from a Gaussian observation term");
     constexpr int P = KIND == 3 ? (GUIDED ? 2 * NS : 1) : KIN ? 2 * NR : NR;
     extern __shared__ __attribute__((aligned(16))) float pf_lds[];
     constexpr int S = NS, RS = S | 1;
@@ -311,7 +316,22 @@ __global__ void __launch_bounds__(pf_max_n(KIND, NS, NO > 0)) pf_kernel(PfParams
         // Gaussian log-weight (the observation term of the ELBO tail kernel); NaN counts as -inf
         const float *yk = p.obs_values + (int64_t)k * p.O;
         float lw = 0.f;
-        if (p.obs_matrix) {
+        if constexpr (CNT) {
+            // count log-weight: the deviance terms plus the row's constant (the terms of y alone)
+            [[maybe_unused]] float unused;
+            lw = p.cl.row_const[k];
+            if (p.obs_matrix) {
+                for (int o = 0; o < p.O; ++o) {
+                    float pred = 0.f;
+#pragma unroll
+                    for (int i = 0; i < NS; ++i) pred += p.obs_matrix[o * S + i] * x[i];
+                    lw += count_term<false>(p.cl, yk[o], pred, unused);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NS; ++i) lw += count_term<false>(p.cl, yk[i], x[i], unused);
+            }
+        } else if (p.obs_matrix) {
             for (int o = 0; o < p.O; ++o) {
                 float pred = 0.f;
 #pragma unroll
@@ -459,6 +479,18 @@ static int pf_fill(PfParams &p, int M, int N, int S, int P, int K, int O, const 
     p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
     p.inv_var = (float)(1.0 / variance); p.log_norm = (float)(-0.5 * log(2.0 * M_PI * variance)); p.log_n = (float)log((double)N);
     return 0;
+}
+
+// the count entry points: the checks of pf_fill (its variance check sees 1), then their own
+static int pf_fill_count(PfParams &p, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
+                         const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind, double scale,
+                         double dispersion, const float *row_const, const uint32_t *key, double time_step,
+                         const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
+                         float *filtered_mean, float *filtered_std, float *particles, int *ancestors) {
+    int rc = pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, 1.0, key, time_step, positive_mask_host,
+                     log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
+    if (rc) return rc;
+    return count_lik(p.cl, lik_kind, scale, dispersion, row_const, K);
 }
 
 // the guided entry points: their own limits first, then the checks of pf_fill
@@ -629,5 +661,76 @@ extern "C" int vsde_crn_kinetic_guided_particle_filter(const vsde_crn_network *n
     p.net = n;
     return pf_crn_dispatch_guided(S, n.R, [&](auto ns, auto nr) {
         return pf_launch_guided<4, decltype(ns)::value, decltype(nr)::value, true>(p, stream);
+    });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The bootstrap filter with a count observation term: the entry points above with the CNT instantiations
+extern "C" int vsde_count_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
+                                          const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind,
+                                          double scale, double dispersion, const float *row_const, const uint32_t *key,
+                                          double time_step, const uint8_t *positive_mask_host, float *log_likelihood,
+                                          float *increments, float *ess, float *filtered_mean, float *filtered_std,
+                                          float *particles, int *ancestors, void *stream) {
+    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);
+    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim");
+    PfParams p = {};
+    int rc = pf_fill_count(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, lik_kind, scale, dispersion, row_const,
+                           key, time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std,
+                           particles, ancestors);
+    if (rc) return rc;
+    if (kind == 1) return pf_launch(pf_kernel<1, 1, EmDims<1>::P, false, 0, true>, p, stream);
+    if (kind == 2) return pf_launch(pf_kernel<2, 2, EmDims<2>::P, false, 0, true>, p, stream);
+    switch (S) {
+#define VSDE_PF_DIAG(n) case n: return pf_launch(pf_kernel<3, n, EmDims<3>::P, false, 0, true>, p, stream)
+        VSDE_PF_DIAG(1); VSDE_PF_DIAG(2); VSDE_PF_DIAG(3); VSDE_PF_DIAG(4); VSDE_PF_DIAG(5); VSDE_PF_DIAG(6); VSDE_PF_DIAG(7); VSDE_PF_DIAG(8);
+        VSDE_PF_DIAG(9); VSDE_PF_DIAG(10); VSDE_PF_DIAG(11); VSDE_PF_DIAG(12); VSDE_PF_DIAG(13); VSDE_PF_DIAG(14); VSDE_PF_DIAG(15);
+        default: VSDE_PF_DIAG(16);
+#undef VSDE_PF_DIAG
+    }
+}
+
+extern "C" int vsde_crn_count_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
+                                              const float *theta, const int *obs_rows, const float *obs_values,
+                                              const float *obs_matrix, int lik_kind, double scale, double dispersion,
+                                              const float *row_const, const uint32_t *key, double time_step,
+                                              const uint8_t *positive_mask_host, float *log_likelihood, float *increments,
+                                              float *ess, float *filtered_mean, float *filtered_std, float *particles,
+                                              int *ancestors, void *stream) {
+    PfParams p = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n);
+    if (rc) return rc;
+    rc = pf_fill_count(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, lik_kind, scale, dispersion, row_const, key,
+                       time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles,
+                       ancestors);
+    if (rc) return rc;
+    p.net = n;
+    return crn_dispatch(S, P, [&](auto ns, auto nr) {
+        return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value, false, 0, true>, p, stream, pf_max_n(4, decltype(ns)::value));
+    });
+}
+
+extern "C" int vsde_crn_kinetic_count_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S,
+                                                      int P, int K, int O, const float *x0, const float *rates, const int *obs_rows,
+                                                      const float *obs_values, const float *obs_matrix, int lik_kind, double scale,
+                                                      double dispersion, const float *row_const, const uint32_t *key,
+                                                      double time_step, const uint8_t *positive_mask_host, float *log_likelihood,
+                                                      float *increments, float *ess, float *filtered_mean, float *filtered_std,
+                                                      float *particles, int *ancestors, void *stream) {
+    PfParams p = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n, true);
+    if (!rc) rc = crn_kinetics(kin, S, n);
+    if (rc) return rc;
+    rc = pf_fill_count(p, M, N, S, P, K, O, x0, rates, obs_rows, obs_values, obs_matrix, lik_kind, scale, dispersion, row_const, key,
+                       time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles,
+                       ancestors);
+    if (rc) return rc;
+    p.net = n;
+    return crn_dispatch(S, n.R, [&](auto ns, auto nr) {
+        return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value, true, 0, true>, p, stream, pf_max_n(4, decltype(ns)::value));
     });
 }

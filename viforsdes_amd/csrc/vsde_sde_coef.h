@@ -19,6 +19,56 @@ __device__ __forceinline__ float floor_nan(float y) { return y < kEmFloor ? kEmF
 
 constexpr int kCrnMaxS = VSDE_CRN_MAX_SPECIES, kCrnMaxR = VSDE_CRN_MAX_REACTIONS;
 
+// Count observation terms (core/observations.py: PoissonObservationLikelihood / NegativeBinomialObservationLikelihood), shared by
+// the ELBO tail, the log-weight and the particle-filter kernels.  lambda = max(scale pred, kRateFloor) with torch.clamp's rules (NaN
+// propagates, the gradient is 0 where scale pred < floor).  The terms of y alone (lgamma's, r log r, y log y) arrive as one float
+// per observation row (row_const [K], made in fp64 by the caller); the kernel adds the deviance form, which is O((lambda - y)^2 / y)
+// near lambda = y where the raw form cancels y log(lambda) against a constant of the same size:
+//   Poisson  y log(lambda / y) - (lambda - y)                                       (y = 0: -lambda)
+//   NB       y log(lambda / y) - (r + y) log((r + lambda) / (r + y))                (y = 0: -r log((r + lambda) / r))
+// with log(a / b) = log1p((a - b) / b) while a is within a factor 2 of b (a - b is then exact).
+constexpr float kRateFloor = 1e-6f;   // core/observations.py: RATE_FLOOR
+struct CountLik {
+    int kind;                  // VSDE_LIK_POISSON / VSDE_LIK_NEGATIVE_BINOMIAL
+    float scale, r;            // r: the dispersion (NB only)
+    const float *row_const;    // [K]
+};
+
+// the count entry points' own argument checks (K: the number of observation rows)
+static inline int count_lik(CountLik &c, int lik_kind, double scale, double dispersion, const float *row_const, int K) {
+    VSDE_CHECK_ARG(lik_kind == VSDE_LIK_POISSON || lik_kind == VSDE_LIK_NEGATIVE_BINOMIAL, VSDE_E_BADARG,
+                   "unknown count likelihood %d (1 = Poisson, 2 = negative binomial)", lik_kind);
+    VSDE_CHECK_ARG(scale > 0, VSDE_E_BADARG, "count likelihood: scale must be positive");
+    VSDE_CHECK_ARG(lik_kind != VSDE_LIK_NEGATIVE_BINOMIAL || dispersion > 0, VSDE_E_BADARG,
+                   "negative binomial: dispersion must be positive");
+    VSDE_CHECK_ARG(row_const || K == 0, VSDE_E_BADARG, "count likelihood: NULL row constants");
+    c.kind = lik_kind; c.scale = (float)scale; c.r = lik_kind == VSDE_LIK_NEGATIVE_BINOMIAL ? (float)dispersion : 1.f;
+    c.row_const = row_const;
+    return 0;
+}
+
+__device__ __forceinline__ float log_ratio(float a, float b) {
+    const float d = a - b;
+    return fabsf(d) < 0.5f * b ? log1pf(d / b) : logf(a / b);
+}
+
+// the deviance term of one observed count y at the linear prediction pred; dlam: d term / d pred (0 where the floor binds)
+template <bool GRAD> __device__ __forceinline__ float count_term(const CountLik &c, float y, float pred, float &dpred) {
+    const float sp = c.scale * pred;
+    const float lam = sp < kRateFloor ? kRateFloor : sp;
+    float t;
+    if (c.kind == VSDE_LIK_POISSON) {
+        t = y > 0.f ? y * log_ratio(lam, y) - (lam - y) : -lam;
+        if (GRAD) dpred = sp < kRateFloor ? 0.f : c.scale * (y - lam) / lam;
+    } else {
+        const float ry = c.r + y;
+        t = -ry * log_ratio(c.r + lam, ry);
+        if (y > 0.f) t += y * log_ratio(lam, y);
+        if (GRAD) dpred = sp < kRateFloor ? 0.f : c.scale * c.r * (y - lam) / (lam * (c.r + lam));
+    }
+    return t;
+}
+
 // state / parameter dims of the fixed-size kinds (kind 3 takes them at run time; the value here is its per-dimension slice; kind 4
 // takes S and the reaction bound NR as template arguments of its kernels, R <= NR at run time: P = NR sizes its theta array)
 template <int KIND> struct EmDims {

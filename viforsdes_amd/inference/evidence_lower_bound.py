@@ -112,12 +112,14 @@ class _ElboTail(torch.autograd.Function):
 
 def _fused_tail_config(observations: Observations, observation_likelihood, prior, sde_parameter_posterior, x: Tensor,
                        sde_parameters: Tensor):
-    """Arguments of the fused tail kernel when every piece is one of the package's own closed forms, else None."""
-    from ..core.observations import GaussianObservationLikelihood
+    """Arguments of the fused tail kernel when every piece is one of the package's own closed forms, else None.  The third entry
+    is the Gaussian likelihood's variance, or the ``CountKernelTerms`` of a Poisson / negative-binomial one."""
+    from ..core.observations import COUNT_LIKELIHOODS, GaussianObservationLikelihood
     from ..core.priors import PriorType
     if not (HIP_TAIL and x.is_cuda and x.dtype == torch.float32 and sde_parameters.dtype == torch.float32):
         return None
-    if type(observation_likelihood) is not GaussianObservationLikelihood or type(prior) is not Prior \
+    count = type(observation_likelihood) in COUNT_LIKELIHOODS
+    if not (count or type(observation_likelihood) is GaussianObservationLikelihood) or type(prior) is not Prior \
             or type(sde_parameter_posterior) is not SDEParameterPosterior:
         return None
     H = observation_likelihood.obs_matrix
@@ -127,7 +129,8 @@ def _fused_tail_config(observations: Observations, observation_likelihood, prior
     theta_pos = getattr(sde_parameter_posterior, "_positive_dims", None)
     if theta_pos is None:
         return None
-    return (observations.values, None if H is None else H.to(x), float(observation_likelihood.variance),
+    term = observation_likelihood.kernel_terms(observations.values) if count else float(observation_likelihood.variance)
+    return (observations.values, None if H is None else H.to(x), term,
             1 if prior.type == PriorType.LOG_NORMAL else 0, float(prior.mean), float(prior.std), tuple(theta_pos))
 
 

@@ -3,7 +3,8 @@ model, for a batch of parameter vectors at once.  It is the yardstick that does 
 likelihoods, a pseudo-marginal sampler, and the theta-only check of a fit (``VariationalPosterior.reweight_parameters``).
 
 The torch code below is the specification and runs anywhere (any SDE, any likelihood, CPU or GPU).  Built-in SDEs with a
-``GaussianObservationLikelihood`` on the GPU in fp32 and ``n_particles`` a multiple of 64 up to 1024 (512 for a reaction network
+``GaussianObservationLikelihood`` (or, for the bootstrap proposal, a ``PoissonObservationLikelihood`` /
+``NegativeBinomialObservationLikelihood``) on the GPU in fp32 and ``n_particles`` a multiple of 64 up to 1024 (512 for a reaction network
 of 5..8 species) run as ONE kernel (csrc/vsde_filter.hip: a workgroup per theta, a thread per particle) that reproduces it; every
 other case falls back to the torch route silently, as ``forecast_states`` does.
 
@@ -61,7 +62,7 @@ import torch
 from torch import Tensor
 
 from ..core.euler_maruyama import _floor_vector
-from ..core.observations import GaussianObservationLikelihood, ObservationLikelihood, Observations
+from ..core.observations import COUNT_LIKELIHOODS, GaussianObservationLikelihood, ObservationLikelihood, Observations
 from ..core.sde import SDE, builtin_sde_route, kernel_theta
 
 HIP_FILTER = True   # set False to force the torch route (A/B tests)
@@ -213,8 +214,9 @@ def particle_filter(sde: SDE, observations: Observations, observation_likelihood
             kind, network = route
             H = observation_likelihood.obs_matrix
             rows = torch.round(obs.times / time_step).to(torch.int32)
-            args = (kind, x0, kernel_theta(network, theta), rows, obs.values, None if H is None else H.to(theta),
-                    float(observation_likelihood.variance), key.to(torch.int32) if key.dtype != torch.int32 else key,
+            count = type(observation_likelihood) in COUNT_LIKELIHOODS
+            term = observation_likelihood.kernel_terms(obs.values) if count else float(observation_likelihood.variance)
+            args = (kind, x0, kernel_theta(network, theta), rows, obs.values, None if H is None else H.to(theta), term, key.to(torch.int32) if key.dtype != torch.int32 else key,
                     float(time_step), n_particles, pos)
             if bridge:
                 return ParticleFilterResult(*_hip.guided_particle_filter(*args, network=network, return_particles=return_particles))
@@ -226,7 +228,8 @@ def particle_filter(sde: SDE, observations: Observations, observation_likelihood
 
 
 def _gaussian_log_weights(like, values, particles):
-    """``lw [M, K, N]`` of the bootstrap kernel's stored particles [M, K, N, S]: the observation term, NaN as -inf."""
+    """``lw [M, K, N]`` of the bootstrap kernel's stored particles [M, K, N, S]: the observation term (any likelihood), NaN as
+    -inf."""
     M, K, N, S = particles.shape
     y = values[None, :, None, :].expand(M, K, N, -1).reshape(M * K * N, -1)
     lw = like.log_prob(y, particles.reshape(M * K * N, S)).reshape(M, K, N)
@@ -237,7 +240,8 @@ def _kernel_route(sde, obs, like, theta, n_particles, proposal="bootstrap"):
     """``builtin_sde_route(sde)`` when the filter kernel takes the call, else None."""
     if not (HIP_FILTER and theta.is_cuda and theta.dtype == torch.float32 and obs.values.dtype == torch.float32):
         return None
-    if type(like) is not GaussianObservationLikelihood:
+    count = type(like) in COUNT_LIKELIHOODS
+    if not (count or type(like) is GaussianObservationLikelihood) or (count and proposal != "bootstrap"):
         return None
     kind, network = builtin_sde_route(sde)
     if kind is None:

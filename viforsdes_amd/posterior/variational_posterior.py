@@ -324,7 +324,7 @@ class VariationalPosterior:
         SDE; the positive state dims are clamped at 1e-6 as in ``euler_maruyama``).  Paths are drawn ``chunk_size`` at a time,
         as in ``log_evidence``: the first chunk eagerly, the others by replaying a captured sampling call that this call owns
         (``sample()``'s graphs are not touched).  Then one forecast key, then the observation noise, are drawn.
-        ``observation_likelihood`` needs a ``sample(state)`` method (``GaussianObservationLikelihood`` has one).
+        ``observation_likelihood`` needs a ``sample(state)`` method (the package's Gaussian, Poisson and negative-binomial ones have one).
         ``mixed_precision``: run the encoder under bf16 autocast, as ``sample()`` does."""
         from .. import _hip
         from ..core.forecast import forecast_states
