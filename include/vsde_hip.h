@@ -143,7 +143,8 @@ int vsde_elbo_path_terms(int B, int T, int S, const float *z, const float *x, co
 
 /* Adjoint of vsde_elbo_path_terms for upstream per-sample gradients g_sde/g_gen/g_jac [B].
  * Outputs are fully overwritten: g_z, g_x [B][T+1][S]; g_means, g_drift [B][T][S];
- * g_chol, g_diffusion [B][T][S][S]. */
+ * g_chol, g_diffusion [B][T][S][S].  B <= 65535 (one grid row per path): a larger batch is an argument error
+ * before any launch -- split it over several calls. */
 int vsde_elbo_path_terms_bwd(int B, int T, int S, const float *z, const float *x,
                              const float *means, const float *chol, const float *drift,
                              const float *diffusion, const uint8_t *positive_mask_host,

@@ -9,6 +9,7 @@
 namespace vsde {
 
 constexpr float kLog2Pi = 1.8378770664093453f;
+constexpr int kElboBwdMaxPaths = 65535;   // elbo_path_terms_bwd_kernel: one gridDim.y row per path
 
 struct ElboParams {
     int B, T;
@@ -552,6 +553,9 @@ extern "C" int vsde_elbo_path_terms_bwd(int B, int T, int S, const float *z, con
     VSDE_CHECK_ARG(B > 0 && T > 0 && S > 0, VSDE_E_BADARG, "bad dims B=%d T=%d S=%d", B, T, S);
     VSDE_CHECK_ARG(z && x && means && chol && drift && diffusion && g_sde && g_gen && g_jac && g_z && g_x && g_means && g_chol &&
                        g_drift && g_diffusion, VSDE_E_BADARG, "NULL argument");
+    // the backward puts b on gridDim.y
+    VSDE_CHECK_ARG(B <= kElboBwdMaxPaths, VSDE_E_BADARG, "ELBO path-term backward supports at most %d paths per call (got %d)",
+                   kElboBwdMaxPaths, B);
     ElboParams p = {};
     p.B = B; p.T = T; p.z = z; p.x = x; p.means = means; p.chol = chol; p.drift = drift; p.diffusion = diffusion;
     p.pos_mask = mask_bits(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
