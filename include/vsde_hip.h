@@ -693,6 +693,49 @@ int vsde_crn_kinetic_guided_particle_filter(const vsde_crn_network *net, const v
                                             float *increments, float *ess, float *filtered_mean, float *filtered_std,
                                             float *particles, int *ancestors, float *log_weights, void *stream);
 
+/* Replay of a filter's genealogy: D smoothed paths x_{0:T} | y, theta_m per filter from what vsde_particle_filter /
+ * vsde_count_particle_filter stored (viforsdes_amd/inference/particle_smoother.py is the specification).  particles[M][K][N][S] and
+ * ancestors[M][K][N] are that call's outputs, and kind / descriptors, M, N, S, P, K, O, x0, theta (rates), obs_rows, key, time_step
+ * and positive_mask_host must be that call's too; last_slot[M][D] (device int32) is the slot of each draw at the LAST observation
+ * (the caller draws it from the final weights), -1 for a filter without a smoothing sample; T = obs_rows[K-1], the steps of a path.
+ *   One launch, one thread per (k, m, d): lineage[m][d][K-1] = last_slot[m][d], lineage[m][d][k-1] = ancestors[m][k-1][lineage[m][d][k]]
+ * (written when lineage is not NULL), and segment k, the grid steps obs_rows[k-1] .. obs_rows[k] - 1 (from 0 for k = 0), is run
+ * again from particles[m][k-1][lineage[m][d][k-1]] (x0[m] for k = 0) with the normals of path b = m N + lineage[m][d][k], the step
+ * and 1e-6 clamp of vsde_particle_filter: the state after step t goes to paths[m][d][t+1][S], paths[m][d][0] = x0[m].  The replay of
+ * a bootstrap filter does not depend on the observation term, so the count filters share these entry points.  A draw with
+ * last_slot < 0: lineage -1, paths NaN.  A segment whose rows decrease or pass T is not written.
+ *   VSDE_E_BADARG before any HIP call: the checks of vsde_particle_filter on N, S, O, K; D < 1, T < 0, M D K >= 2^31, a NULL
+ * argument other than lineage.  No particle limit below 1024 applies: a replay thread is not tied to a particle. */
+int vsde_filter_replay(int kind, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0, const float *theta,
+                       const int *obs_rows, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                       const float *particles, const int *ancestors, const int *last_slot, float *paths, int *lineage, void *stream);
+int vsde_crn_filter_replay(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
+                           const float *theta, const int *obs_rows, const uint32_t *key, double time_step,
+                           const uint8_t *positive_mask_host, const float *particles, const int *ancestors, const int *last_slot,
+                           float *paths, int *lineage, void *stream);
+int vsde_crn_kinetic_filter_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P, int K, int O,
+                                   int D, int T, const float *x0, const float *rates, const int *obs_rows, const uint32_t *key,
+                                   double time_step, const uint8_t *positive_mask_host, const float *particles, const int *ancestors,
+                                   const int *last_slot, float *paths, int *lineage, void *stream);
+
+/* vsde_filter_replay for what vsde_guided_particle_filter stored: segment k repeats the bridge steps towards obs_values[k] (n =
+ * obs_rows[k] - t steps ahead), so obs_values[K][O], obs_matrix[O][S] or NULL and variance must be that call's as well.  S <= 4 and
+ * O <= 4 (VSDE_E_BADARG otherwise, before any HIP call). */
+int vsde_guided_filter_replay(int kind, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0, const float *theta,
+                              const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                              const uint32_t *key, double time_step, const uint8_t *positive_mask_host, const float *particles,
+                              const int *ancestors, const int *last_slot, float *paths, int *lineage, void *stream);
+int vsde_crn_guided_filter_replay(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
+                                  const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                  double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                  const float *particles, const int *ancestors, const int *last_slot, float *paths, int *lineage,
+                                  void *stream);
+int vsde_crn_kinetic_guided_filter_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P, int K,
+                                          int O, int D, int T, const float *x0, const float *rates, const int *obs_rows,
+                                          const float *obs_values, const float *obs_matrix, double variance, const uint32_t *key,
+                                          double time_step, const uint8_t *positive_mask_host, const float *particles,
+                                          const int *ancestors, const int *last_slot, float *paths, int *lineage, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

@@ -18,11 +18,14 @@ from .core.reaction_network import Hill, MichaelisMenten, ReactionNetworkSDE
 from .core.sde import SDE, FunctionalSDE, make_sde
 from .infer import InferenceConfig, infer
 from .inference.particle_filter import ParticleFilterResult, particle_filter
-from .posterior.variational_posterior import EvidenceEstimate, ParameterReweighting, PosteriorPredictive, VariationalPosterior
+from .inference.particle_smoother import SmoothedPaths, particle_smoother
+from .posterior.variational_posterior import (EvidenceEstimate, ParameterReweighting, PathReweighting, PosteriorPredictive,
+                                              VariationalPosterior)
 
 __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "TrainingConfig", "YamlConfig",
            "GaussianObservationLikelihood", "NegativeBinomialObservationLikelihood", "PoissonObservationLikelihood",
            "ObservationLikelihood", "Observations", "Prior", "PriorType", "SDE",
            "FunctionalSDE", "Hill", "MichaelisMenten", "ReactionNetworkSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior",
-           "EvidenceEstimate", "PosteriorPredictive", "ParameterReweighting", "ParticleFilterResult", "particle_filter"]
+           "EvidenceEstimate", "PosteriorPredictive", "ParameterReweighting", "ParticleFilterResult", "particle_filter",
+           "PathReweighting", "SmoothedPaths", "particle_smoother"]
 __version__ = "0.1.0"

@@ -70,6 +70,8 @@ EXPORTS = (
     "vsde_crn_kinetic_euler_maruyama_fwd", "vsde_crn_kinetic_euler_maruyama_bwd", "vsde_crn_kinetic_forecast",
     "vsde_crn_kinetic_log_weights", "vsde_particle_filter", "vsde_crn_particle_filter", "vsde_crn_kinetic_particle_filter",
     "vsde_guided_particle_filter", "vsde_crn_guided_particle_filter", "vsde_crn_kinetic_guided_particle_filter",
+    "vsde_filter_replay", "vsde_crn_filter_replay", "vsde_crn_kinetic_filter_replay",
+    "vsde_guided_filter_replay", "vsde_crn_guided_filter_replay", "vsde_crn_kinetic_guided_filter_replay",
     "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
@@ -521,6 +523,63 @@ def guided_particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matri
     arguments, and the same 7 outputs followed by log_weights [M, K, N] or None."""
     return _particle_filter("guided_particle_filter", True, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key,
                             time_step, n_particles, positive_dims, network, return_particles)
+
+
+def _filter_replay(entry: str, kind, x0, theta, obs_rows, model, key, time_step, particles, ancestors, last_slot, n_steps,
+                   positive_dims, network):
+    lib = load()
+    dev = _require_hip(x0, theta, obs_rows, key, particles, ancestors, last_slot, *model[:2])
+    x0, theta, particles = _f32c(x0), _f32c(theta), _f32c(particles)
+    if obs_rows.dtype != torch.int32 or obs_rows.ndim != 1 or key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2:
+        raise ValueError("filter_replay: obs_rows must be an int32 [K] tensor and key two int32 words")
+    if ancestors.dtype != torch.int32 or last_slot.dtype != torch.int32:
+        raise ValueError("filter_replay: ancestors and last_slot must be int32 tensors")
+    obs_rows, key, ancestors, last_slot = obs_rows.contiguous(), key.contiguous(), ancestors.contiguous(), last_slot.contiguous()
+    K = obs_rows.shape[0]
+    if x0.ndim != 2 or theta.ndim != 2 or theta.shape[0] != x0.shape[0] or particles.ndim != 4 or last_slot.ndim != 2 \
+            or tuple(particles.shape[:2]) != (x0.shape[0], K) or particles.shape[3] != x0.shape[1] \
+            or tuple(ancestors.shape) != tuple(particles.shape[:3]) or last_slot.shape[0] != x0.shape[0]:
+        raise ValueError(f"filter_replay: x0 [M, S], theta [M, P], obs_rows [K], particles [M, K, N, S], ancestors [M, K, N], "
+                         f"last_slot [M, D] expected, got {tuple(x0.shape)}, {tuple(theta.shape)}, {tuple(obs_rows.shape)}, "
+                         f"{tuple(particles.shape)}, {tuple(ancestors.shape)}, {tuple(last_slot.shape)}")
+    M, S = x0.shape
+    N, D = particles.shape[2], last_slot.shape[1]
+    T = int(obs_rows[-1]) if n_steps is None and K else int(n_steps or 0)
+    obs_values, obs_matrix, variance = model
+    O, extra = S, ()
+    if entry.startswith("guided"):
+        obs_values = _f32c(obs_values)
+        obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
+        if obs_values.ndim != 2 or obs_values.shape[0] != K or (obs_matrix is not None and tuple(obs_matrix.shape) != (obs_values.shape[1], S)):
+            raise ValueError(f"filter_replay: obs_values [{K}, O] and obs_matrix [O, {S}] expected")
+        O, extra = obs_values.shape[1], (_ptr(obs_values), _ptr(obs_matrix), ctypes.c_double(variance))
+    with torch.cuda.device(dev):
+        ok = D >= 1 and T >= 0    # bad sizes are the entry point's to refuse: allocate nothing for them
+        paths = torch.empty(M, D, T + 1, S, device=dev, dtype=torch.float32) if ok else None
+        lineage = torch.empty(M, D, K, device=dev, dtype=torch.int32) if ok else None
+        _call(*_sde_entry(lib, entry, kind, network), ctypes.c_int(M), ctypes.c_int(N), ctypes.c_int(S), ctypes.c_int(theta.shape[1]),
+              ctypes.c_int(K), ctypes.c_int(O), ctypes.c_int(D), ctypes.c_int(T), _ptr(x0), _ptr(theta), _ptr(obs_rows), *extra,
+              _ptr(key), ctypes.c_double(time_step), _mask_bytes(positive_dims, S), _ptr(particles), _ptr(ancestors),
+              _ptr(last_slot), _ptr(paths), _ptr(lineage), _stream(dev))
+    return paths, lineage
+
+
+def filter_replay(kind: str, x0, theta, obs_rows, key, time_step: float, particles, ancestors, last_slot, positive_dims=(),
+                  network=None, n_steps: Optional[int] = None):
+    """Smoothed paths from a bootstrap filter's genealogy (include/vsde_hip.h: vsde_filter_replay): ``kind``, x0, theta, obs_rows,
+    key, time_step, positive_dims and network as given to ``particle_filter``, its particles [M, K, N, S] and ancestors [M, K, N],
+    and last_slot [M, D] (int32; -1: no sample), the slot of each draw at the last observation.  ``n_steps``: obs_rows[K-1] when
+    the caller knows it (saves reading it back from the device).  Returns (paths [M, D, T+1, S], lineage [M, D, K] int32)."""
+    return _filter_replay("filter_replay", kind, x0, theta, obs_rows, (None, None, None), key, time_step, particles, ancestors,
+                          last_slot, n_steps, positive_dims, network)
+
+
+def guided_filter_replay(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, key, time_step: float, particles,
+                         ancestors, last_slot, positive_dims=(), network=None, n_steps: Optional[int] = None):
+    """``filter_replay`` for the stored particles of ``guided_particle_filter`` (vsde_guided_filter_replay; S <= 4, O <= 4): the
+    bridge steps need the observations, obs_matrix and variance of that call as well."""
+    return _filter_replay("guided_filter_replay", kind, x0, theta, obs_rows, (obs_values, obs_matrix, variance), key, time_step,
+                          particles, ancestors, last_slot, n_steps, positive_dims, network)
 
 
 def _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean, post_log_std, theta_positive_dims):

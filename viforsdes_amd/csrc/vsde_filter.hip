@@ -11,6 +11,8 @@
 // modified-diffusion-bridge step of the specification (pf_bridge_step) and carries the log-ratio model / proposal in one more
 // register to the observation; everything from the log-weight on is the same code.
 // LDS (dynamic): N cumulative sums + N (S | 1) state floats + 16 x 18 reduction slots: 73 KiB at N = 1024, S = 16.
+// The particle smoother's replay kernel (rp_kernel, at the end of the namespace) runs single segments of a filter again from the
+// stored particles and ancestors, through the same pf_propagate / pf_propagate_guided with a store hook.
 #include "vsde_sde_step.h"
 
 namespace vsde {
@@ -72,10 +74,16 @@ __device__ __forceinline__ void pf_block_sum(float *v, float *red, int lane, int
     __syncthreads();
 }
 
+// Store hook of pf_propagate / pf_propagate_guided: st(t, i, v) sees dim i of the state after grid step t.  The filter keeps no
+// trajectory: its hook is empty, so its instantiations are the code they were; the replay kernel (rp_kernel) stores the state
+struct PfNoStore {
+    __device__ __forceinline__ void operator()(int, int, float) const {}
+};
+
 // Euler-Maruyama steps t0 .. t1 - 1 (global grid steps, t1 > t0) of one particle, path index b of the noise stream
-template <int KIND, int NS, int NR, bool KIN, int P>
+template <int KIND, int NS, int NR, bool KIN, int P, class ST = PfNoStore>
 __device__ __forceinline__ void pf_propagate(const PfParams &p, float *x, const float *th, int t0, int t1, uint32_t b, uint32_t k0,
-                                             uint32_t k1, int m) {
+                                             uint32_t k1, int m, ST st = ST()) {
     if constexpr (KIND == 3) {
         // independent scalar SDEs: one dim at a time, so only 4 normals are alive (theta_i is uniform: scalar loads)
 #pragma unroll
@@ -94,6 +102,7 @@ __device__ __forceinline__ void pf_propagate(const PfParams &p, float *x, const 
                             float y;
                             em_step<3>(&xi, th2, &z[q], p.dt, p.sqdt, &y);
                             xi = pos ? floor_nan(y) : y;
+                            st(t, i, xi);
                         }
                     }
                 }
@@ -116,6 +125,8 @@ __device__ __forceinline__ void pf_propagate(const PfParams &p, float *x, const 
                     else em_step<KIND>(x, th, e, p.dt, p.sqdt, y);
 #pragma unroll
                     for (int i = 0; i < NS; ++i) x[i] = ((p.pos_mask >> i) & 1u) ? floor_nan(y[i]) : y[i];
+#pragma unroll
+                    for (int i = 0; i < NS; ++i) st(t, i, x[i]);
                 }
             }
         }
@@ -254,9 +265,9 @@ __device__ __forceinline__ void pf_bridge_step(const PfParams &p, float *x, cons
 }
 
 // guided steps t0 .. t1 - 1 of one particle towards the observation yk at grid row t1
-template <int KIND, int NS, int NR, bool KIN, int NO>
+template <int KIND, int NS, int NR, bool KIN, int NO, class ST = PfNoStore>
 __device__ __forceinline__ void pf_propagate_guided(const PfParams &p, float *x, const float *th, int t0, int t1, uint32_t b,
-                                                    uint32_t k0, uint32_t k1, const float *yk, float &lr) {
+                                                    uint32_t k0, uint32_t k1, const float *yk, float &lr, ST st = ST()) {
     for (int blk = t0 >> 2; blk <= (t1 - 1) >> 2; ++blk) {
         float z[NS][4];
 #pragma unroll
@@ -269,6 +280,8 @@ __device__ __forceinline__ void pf_propagate_guided(const PfParams &p, float *x,
 #pragma unroll
                 for (int i = 0; i < NS; ++i) zq[i] = z[i][q];
                 pf_bridge_step<KIND, NS, NR, KIN, NO>(p, x, th, zq, yk, (float)(t1 - t), lr);
+#pragma unroll
+                for (int i = 0; i < NS; ++i) st(t, i, x[i]);
             }
         }
     }
@@ -534,6 +547,140 @@ template <class F> static int pf_crn_dispatch_guided(int S, int R, F &&f) {
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Replay of the filter's genealogy (viforsdes_amd/inference/particle_smoother.py is the specification): D posterior paths per filter
+// from the stored particles and ancestors.  A thread per (observation k, filter m, draw d), k slowest, so the lanes of a wave run
+// segments of the same length: it walks its draw's lineage from the last observation down to k through `ancestors` (at most K
+// loads), starts from the stored particle its lineage had at observation k - 1 (x0 for k = 0) and repeats the grid steps
+// obs_rows[k-1] .. obs_rows[k] - 1 with the noise of its slot at k: pf_propagate / pf_propagate_guided with a store hook, so step,
+// clamp and Philox block structure are the filter's own.  A thread is not tied to a particle: 256-thread workgroups (512 VGPRs a
+// lane) keep every instantiation out of scratch.
+constexpr int kRpThreads = 256;
+
+struct RpParams {
+    int D, T;
+    const float *particles;
+    const int *ancestors, *last_slot;
+    float *paths;
+    int *lineage;
+};
+
+// the state after grid step t goes to row t + 1 of the draw's path [T + 1][S]
+struct RpStore {
+    float *path;
+    int S;
+    __device__ __forceinline__ void operator()(int t, int i, float v) const { path[(int64_t)(t + 1) * S + i] = v; }
+};
+
+template <int KIND, int NS = EmDims<KIND>::S, int NR = EmDims<KIND>::P, bool KIN = false, int NO = 0>
+__global__ void __launch_bounds__(kRpThreads) rp_kernel(PfParams p, RpParams r) {
+    constexpr bool GUIDED = NO > 0;
+    constexpr int P = KIND == 3 ? (GUIDED ? 2 * NS : 1) : KIN ? 2 * NR : NR;
+    constexpr int S = NS;
+    const int64_t md = (int64_t)p.M * r.D, g = (int64_t)blockIdx.x * kRpThreads + threadIdx.x;
+    if (g >= md * p.K) return;
+    const int k = (int)(g / md), N = p.N;
+    const int64_t q = g - (int64_t)k * md;   // m D + d
+    const int m = (int)(q / r.D);
+    const int t0 = k ? p.rows[k - 1] : 0, t1 = p.rows[k];
+    if (t0 < 0 || t1 < t0 || t1 > r.T) return;   // rows that decrease or pass the paths' T: nothing is written
+    float *path = r.paths + q * ((int64_t)r.T + 1) * S;
+    int slot = r.last_slot[q];
+    if (slot < 0 || slot >= N) {
+        // a dead filter has no smoothing sample
+        for (int t = k ? t0 + 1 : 0; t <= t1; ++t)
+#pragma unroll
+            for (int i = 0; i < NS; ++i) path[(int64_t)t * S + i] = __builtin_nanf("");
+        if (r.lineage) r.lineage[q * p.K + k] = -1;
+        return;
+    }
+    // ancestors are slots of the same filter; the clamp keeps a corrupt entry inside its row
+    const int *anc = r.ancestors + (int64_t)m * p.K * N;
+    for (int kk = p.K - 1; kk > k; --kk) slot = min(max(anc[(int64_t)(kk - 1) * N + slot], 0), N - 1);
+    if (r.lineage) r.lineage[q * p.K + k] = slot;
+    float x[NS], th[P];
+    if (k == 0) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) path[i] = x[i] = p.x0[(int64_t)m * S + i];
+    } else {
+        const int prev = min(max(anc[(int64_t)(k - 1) * N + slot], 0), N - 1);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) x[i] = r.particles[(((int64_t)m * p.K + k - 1) * N + prev) * S + i];
+    }
+    if (t1 == t0) return;
+    if constexpr (KIND == 3 && GUIDED) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            th[i] = p.theta[(int64_t)m * p.P + i];
+            th[NS + i] = softplus_f(p.theta[(int64_t)m * p.P + NS + i]) + 1e-3f;
+        }
+    } else if constexpr (KIND == 3) th[0] = 0.f;
+    else if constexpr (KIN) crn_load_rates<NR>(th, p.theta, m, p.net.R, true);
+    else em_load_theta<KIND, P>(th, p.theta, m, p.P, true);
+    const uint32_t b = (uint32_t)m * (uint32_t)N + (uint32_t)slot, k0 = p.key[0], k1 = p.key[1];
+    const RpStore st{path, S};
+    if constexpr (GUIDED) {
+        float lr = 0.f;
+        pf_propagate_guided<KIND, NS, NR, KIN, NO>(p, x, th, t0, t1, b, k0, k1, p.obs_values + (int64_t)k * p.O, lr, st);
+    } else {
+        pf_propagate<KIND, NS, NR, KIN, P>(p, x, th, t0, t1, b, k0, k1, m, st);
+    }
+}
+
+// argument checks of the replay entry points (before any HIP call; the wording of pf_fill) and the parameter blocks
+static int rp_fill(PfParams &p, RpParams &r, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
+                   const float *theta, const int *obs_rows, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                   const float *particles, const int *ancestors, const int *last_slot, float *paths, int *lineage) {
+    VSDE_CHECK_ARG(M >= 1 && K >= 1, VSDE_E_BADARG, "bad particle-filter dims M=%d K=%d", M, K);
+    VSDE_CHECK_ARG(N >= kWave && N <= kPfMaxN && N % kWave == 0, VSDE_E_BADARG,
+                   "particle filter: %d particles (a multiple of %d up to %d supported)", N, kWave, kPfMaxN);
+    VSDE_CHECK_ARG((int64_t)M * N < ((int64_t)1 << 32), VSDE_E_BADARG, "particle filter: M N = %lld paths (below 2^32 supported)",
+                   (long long)M * N);
+    VSDE_CHECK_ARG(S >= 1 && S <= kPfMaxS, VSDE_E_BADARG, "particle filter: state_dim %d (1..%d supported)", S, kPfMaxS);
+    VSDE_CHECK_ARG(O >= 1 && O <= kPfMaxO, VSDE_E_BADARG, "particle filter: obs_dim %d (1..%d supported)", O, kPfMaxO);
+    VSDE_CHECK_ARG(D >= 1, VSDE_E_BADARG, "filter replay: %d draws per filter (>= 1 supported)", D);
+    VSDE_CHECK_ARG(T >= 0, VSDE_E_BADARG, "filter replay: %d grid steps", T);
+    VSDE_CHECK_ARG((int64_t)M * D * K < ((int64_t)1 << 31), VSDE_E_BADARG, "filter replay: M D K = %lld segments (below 2^31 supported)",
+                   (long long)M * D * K);
+    VSDE_CHECK_ARG(time_step > 0, VSDE_E_BADARG, "bad variance / time_step");
+    VSDE_CHECK_ARG(x0 && theta && obs_rows && key && particles && ancestors && last_slot && paths, VSDE_E_BADARG, "NULL argument");
+    p.M = M; p.N = N; p.S = S; p.P = P; p.K = K; p.O = O;
+    p.x0 = x0; p.theta = theta; p.rows = obs_rows; p.key = key;
+    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+    r.D = D; r.T = T; r.particles = particles; r.ancestors = ancestors; r.last_slot = last_slot; r.paths = paths; r.lineage = lineage;
+    return 0;
+}
+
+// the guided replay: the guided filter's limits first, then the checks of rp_fill and the observation model of the proposal
+static int rp_fill_guided(PfParams &p, RpParams &r, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
+                          const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                          const uint32_t *key, double time_step, const uint8_t *positive_mask_host, const float *particles,
+                          const int *ancestors, const int *last_slot, float *paths, int *lineage) {
+    VSDE_CHECK_ARG(S >= 1 && S <= kPfGuidedMaxS, VSDE_E_BADARG, "guided particle filter: state_dim %d (1..%d supported)", S, kPfGuidedMaxS);
+    VSDE_CHECK_ARG(O >= 1 && O <= kPfGuidedMaxO, VSDE_E_BADARG, "guided particle filter: obs_dim %d (1..%d supported)", O, kPfGuidedMaxO);
+    VSDE_CHECK_ARG(obs_matrix || O == S, VSDE_E_BADARG, "without an observation matrix obs_dim must equal state_dim (%d vs %d)", O, S);
+    VSDE_CHECK_ARG(variance > 0, VSDE_E_BADARG, "bad variance / time_step");
+    int rc = rp_fill(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, key, time_step, positive_mask_host, particles, ancestors,
+                     last_slot, paths, lineage);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(obs_values, VSDE_E_BADARG, "NULL argument");
+    p.obs_values = obs_values; p.obs_matrix = obs_matrix; p.var = (float)variance;
+    return 0;
+}
+
+template <class Kern> static int rp_launch(Kern kern, const PfParams &p, const RpParams &r, void *stream) {
+    const int64_t threads = (int64_t)p.M * r.D * p.K;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((threads + kRpThreads - 1) / kRpThreads)), dim3(kRpThreads), 0, (hipStream_t)stream, p, r);
+    VSDE_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+template <int KIND, int NS, int NR, bool KIN> static int rp_launch_guided(const PfParams &p, const RpParams &r, void *stream) {
+    if (p.O <= 2) return rp_launch(rp_kernel<KIND, NS, NR, KIN, 2>, p, r, stream);
+    return rp_launch(rp_kernel<KIND, NS, NR, KIN, 4>, p, r, stream);
+}
+
 }  // namespace vsde
 
 using namespace vsde;
@@ -732,5 +879,132 @@ extern "C" int vsde_crn_kinetic_count_particle_filter(const vsde_crn_network *ne
     p.net = n;
     return crn_dispatch(S, n.R, [&](auto ns, auto nr) {
         return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value, true, 0, true>, p, stream, pf_max_n(4, decltype(ns)::value));
+    });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Replay of the filter's genealogy: posterior paths from the particles and ancestors the entry points above stored
+#define VSDE_RP_KIND_CHECKS                                                                                                          \
+    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);                                    \
+    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");        \
+    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");            \
+    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim")
+
+extern "C" int vsde_filter_replay(int kind, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0, const float *theta,
+                                  const int *obs_rows, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                  const float *particles, const int *ancestors, const int *last_slot, float *paths, int *lineage,
+                                  void *stream) {
+    VSDE_RP_KIND_CHECKS;
+    PfParams p = {};
+    RpParams r = {};
+    int rc = rp_fill(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, key, time_step, positive_mask_host, particles, ancestors,
+                     last_slot, paths, lineage);
+    if (rc) return rc;
+    if (kind == 1) return rp_launch(rp_kernel<1>, p, r, stream);
+    if (kind == 2) return rp_launch(rp_kernel<2>, p, r, stream);
+    switch (S) {
+#define VSDE_RP_DIAG(n) case n: return rp_launch(rp_kernel<3, n>, p, r, stream)
+        VSDE_RP_DIAG(1); VSDE_RP_DIAG(2); VSDE_RP_DIAG(3); VSDE_RP_DIAG(4); VSDE_RP_DIAG(5); VSDE_RP_DIAG(6); VSDE_RP_DIAG(7); VSDE_RP_DIAG(8);
+        VSDE_RP_DIAG(9); VSDE_RP_DIAG(10); VSDE_RP_DIAG(11); VSDE_RP_DIAG(12); VSDE_RP_DIAG(13); VSDE_RP_DIAG(14); VSDE_RP_DIAG(15);
+        default: VSDE_RP_DIAG(16);
+#undef VSDE_RP_DIAG
+    }
+}
+
+extern "C" int vsde_crn_filter_replay(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, int D, int T,
+                                      const float *x0, const float *theta, const int *obs_rows, const uint32_t *key, double time_step,
+                                      const uint8_t *positive_mask_host, const float *particles, const int *ancestors,
+                                      const int *last_slot, float *paths, int *lineage, void *stream) {
+    PfParams p = {};
+    RpParams r = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n);
+    if (rc) return rc;
+    rc = rp_fill(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, key, time_step, positive_mask_host, particles, ancestors, last_slot,
+                 paths, lineage);
+    if (rc) return rc;
+    p.net = n;
+    return crn_dispatch(S, P, [&](auto ns, auto nr) { return rp_launch(rp_kernel<4, decltype(ns)::value, decltype(nr)::value>, p, r, stream); });
+}
+
+extern "C" int vsde_crn_kinetic_filter_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P,
+                                              int K, int O, int D, int T, const float *x0, const float *rates, const int *obs_rows,
+                                              const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                              const float *particles, const int *ancestors, const int *last_slot, float *paths,
+                                              int *lineage, void *stream) {
+    PfParams p = {};
+    RpParams r = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n, true);
+    if (!rc) rc = crn_kinetics(kin, S, n);
+    if (rc) return rc;
+    rc = rp_fill(p, r, M, N, S, P, K, O, D, T, x0, rates, obs_rows, key, time_step, positive_mask_host, particles, ancestors, last_slot,
+                 paths, lineage);
+    if (rc) return rc;
+    p.net = n;
+    return crn_dispatch(S, n.R, [&](auto ns, auto nr) {
+        return rp_launch(rp_kernel<4, decltype(ns)::value, decltype(nr)::value, true>, p, r, stream);
+    });
+}
+
+extern "C" int vsde_guided_filter_replay(int kind, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
+                                         const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                         double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                         const float *particles, const int *ancestors, const int *last_slot, float *paths,
+                                         int *lineage, void *stream) {
+    VSDE_RP_KIND_CHECKS;
+    PfParams p = {};
+    RpParams r = {};
+    int rc = rp_fill_guided(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
+                            positive_mask_host, particles, ancestors, last_slot, paths, lineage);
+    if (rc) return rc;
+    if (kind == 1) return rp_launch_guided<1, 1, EmDims<1>::P, false>(p, r, stream);
+    if (kind == 2) return rp_launch_guided<2, 2, EmDims<2>::P, false>(p, r, stream);
+    switch (S) {
+        case 1: return rp_launch_guided<3, 1, EmDims<3>::P, false>(p, r, stream);
+        case 2: return rp_launch_guided<3, 2, EmDims<3>::P, false>(p, r, stream);
+        case 3: return rp_launch_guided<3, 3, EmDims<3>::P, false>(p, r, stream);
+        default: return rp_launch_guided<3, 4, EmDims<3>::P, false>(p, r, stream);
+    }
+}
+#undef VSDE_RP_KIND_CHECKS
+
+extern "C" int vsde_crn_guided_filter_replay(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, int D, int T,
+                                             const float *x0, const float *theta, const int *obs_rows, const float *obs_values,
+                                             const float *obs_matrix, double variance, const uint32_t *key, double time_step,
+                                             const uint8_t *positive_mask_host, const float *particles, const int *ancestors,
+                                             const int *last_slot, float *paths, int *lineage, void *stream) {
+    PfParams p = {};
+    RpParams r = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n);
+    if (rc) return rc;
+    rc = rp_fill_guided(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
+                        positive_mask_host, particles, ancestors, last_slot, paths, lineage);
+    if (rc) return rc;
+    p.net = n;
+    return pf_crn_dispatch_guided(S, P, [&](auto ns, auto nr) {
+        return rp_launch_guided<4, decltype(ns)::value, decltype(nr)::value, false>(p, r, stream);
+    });
+}
+
+extern "C" int vsde_crn_kinetic_guided_filter_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S,
+                                                     int P, int K, int O, int D, int T, const float *x0, const float *rates,
+                                                     const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                                     double variance, const uint32_t *key, double time_step,
+                                                     const uint8_t *positive_mask_host, const float *particles, const int *ancestors,
+                                                     const int *last_slot, float *paths, int *lineage, void *stream) {
+    PfParams p = {};
+    RpParams r = {};
+    CrnNet n;
+    int rc = crn_net(net, S, P, n, true);
+    if (!rc) rc = crn_kinetics(kin, S, n);
+    if (rc) return rc;
+    rc = rp_fill_guided(p, r, M, N, S, P, K, O, D, T, x0, rates, obs_rows, obs_values, obs_matrix, variance, key, time_step,
+                        positive_mask_host, particles, ancestors, last_slot, paths, lineage);
+    if (rc) return rc;
+    p.net = n;
+    return pf_crn_dispatch_guided(S, n.R, [&](auto ns, auto nr) {
+        return rp_launch_guided<4, decltype(ns)::value, decltype(nr)::value, true>(p, r, stream);
     });
 }

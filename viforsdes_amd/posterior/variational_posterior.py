@@ -164,6 +164,45 @@ class ParameterReweighting:
     log_weights: Optional[Tensor] = None
 
 
+@dataclass(frozen=True)
+class PathReweighting:
+    """Importance sample of the exact joint posterior ``p(theta, x_{0:T} | y)`` of the Euler-Maruyama-discretised model
+    (``VariationalPosterior.smooth_paths``): ``n_samples`` draws theta ~ q, one smoothed path per theta from the genealogy of the
+    particle filter that estimated ``p^(y | theta)`` (``particle_smoother``), and the weights ``p(theta) p^(y | theta) / q(theta)`` of
+    ``ParameterReweighting`` -- proper for the pair, because the path comes from the same filter that made ``p^``.  No network enters:
+    set ``path_mean`` / ``path_std`` beside ``summary().diffusion_path_mean`` / ``diffusion_path_std``.
+
+    * ``log_evidence``, ``standard_error``, ``effective_sample_size``, ``n_samples``, ``n_nonfinite``,
+      ``filter_effective_sample_size [n]``: as in ``ParameterReweighting`` (the same numbers under the same seed);
+    * ``times [T+1]``: the grid; ``path_mean``, ``path_std`` ``[T+1, S]`` and ``path_quantiles`` (each ``[T+1, S]``) of the paths
+      under the normalised weights, by the weighted-quantile rule of ``ParameterReweighting``; NaN where no estimate exists;
+    * ``paths [n, T+1, S]``, ``sde_parameters [n, P]``, ``log_weights [n]`` (float64) when asked for, else None.  The path of a
+      draw whose filter died is NaN and its weight zero."""
+    log_evidence: float
+    standard_error: float
+    effective_sample_size: float
+    n_samples: int
+    n_nonfinite: int
+    filter_effective_sample_size: Tensor
+    times: Tensor
+    path_mean: Tensor
+    path_std: Tensor
+    path_quantiles: Quantiles
+    paths: Optional[Tensor] = None
+    sde_parameters: Optional[Tensor] = None
+    log_weights: Optional[Tensor] = None
+
+
+def _weighted_quantiles(values: Tensor, wn: Tensor) -> Tensor:
+    """``[levels, C]``: per column of ``values [n, C]`` the smallest value whose cumulative normalised weight ``wn [n]``, in sorted
+    order, reaches each of QUANTILE_LEVELS."""
+    order = torch.argsort(values, dim=0)
+    cdf = torch.cumsum(wn[order], dim=0)                                    # [n, C]: cumulative weight in each column's sorted order
+    levels = torch.tensor(QUANTILE_LEVELS, device=values.device, dtype=values.dtype)
+    first = (cdf[None, :, :] < levels[:, None, None]).sum(dim=1).clamp(max=values.shape[0] - 1)    # [levels, C]
+    return torch.gather(torch.gather(values, 0, order), 0, first)
+
+
 class VariationalPosteriorCheckpoint(BaseModel):
     model_config = ConfigDict(frozen=True, arbitrary_types_allowed=True)
     model_state: dict[str, Tensor]
@@ -442,14 +481,75 @@ class VariationalPosterior:
         wn = w / s1
         mean = (wn[:, None] * th).sum(dim=0)
         std = (wn[:, None] * (th - mean) ** 2).sum(dim=0).sqrt()
-        order = torch.argsort(th, dim=0)
-        cdf = torch.cumsum(wn[order], dim=0)                                    # [n, P]: cumulative weight in each dim's sorted order
-        levels = torch.tensor(QUANTILE_LEVELS, device=th.device, dtype=th.dtype)
-        first = (cdf[None, :, :] < levels[:, None, None]).sum(dim=1).clamp(max=n_samples - 1)    # [levels, P]
-        quant = torch.gather(torch.gather(th, 0, order), 0, first)
+        quant = _weighted_quantiles(th, wn)
         return ParameterReweighting(
             m + math.log(s1) - math.log(n_samples), math.sqrt(max(1.0 / ess - 1.0 / n_samples, 0.0)), ess, n_samples, 0,
             mean.to(theta.dtype), std.to(theta.dtype), Quantiles(*quant.to(theta.dtype).unbind(0)), v_mean, v_std, min_ess, *draws)
+
+    @torch.no_grad()
+    def smooth_paths(self, sde: SDE, observation_likelihood: ObservationLikelihood, n_samples: int = 1024, n_particles: int = 512,
+                     chunk_size: int = 256, proposal: str = "bootstrap", return_draws: bool = True) -> PathReweighting:
+        """Are the variational paths any good?  ``reweight_parameters`` with one smoothed path per theta draw
+        (``particle_smoother``: the path is traced through the genealogy of the very filter that estimated ``p^(y | theta)``), so
+        the weighted draws are a proper importance sample of the exact joint posterior ``p(theta, x_{0:T} | y)``: ``path_mean`` /
+        ``path_std`` / ``path_quantiles`` are what ``summary().diffusion_path_mean`` / ``diffusion_path_std`` should match, and
+        neither the encoder nor the head enters.  It consumes torch's generator exactly as ``reweight_parameters`` does (theta, then
+        one key per chunk), so under the same seed both return the same ``log_evidence``.  It runs on a CPU posterior too (the
+        torch routes) and touches none of ``sample()``'s caches or graphs.  ``proposal`` as in ``reweight_parameters``."""
+        from ..inference import particle_filter as _pf
+        from ..inference import particle_smoother as _ps
+        if proposal not in _pf.PROPOSALS:
+            raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
+        if n_samples < 1 or chunk_size < 1 or n_particles < 1:
+            raise ValueError(f"n_samples, n_particles and chunk_size must be >= 1 (got {n_samples}, {n_particles}, {chunk_size})")
+        q = self.model.sde_parameter_posterior
+        S, P = self.state_space.dim, q.sde_param_dim
+        if sde.state_dim != S or sde.sde_param_dim != P:
+            raise ValueError(f"sde has state_dim {sde.state_dim}, sde_param_dim {sde.sde_param_dim}; the posterior has {S}, {P}")
+        self.model.eval()
+        with self.exponential_moving_average.apply():
+            theta = q.rsample(n_samples)
+            log_q = q.log_prob(theta).double()
+        log_prior = self.prior.log_prob(theta)
+        if log_prior.ndim > 1:
+            log_prior = log_prior.sum(dim=-1)
+        x0 = self.observations.values[0]
+        loglik = torch.empty(n_samples, device=theta.device, dtype=theta.dtype)
+        min_ess = torch.empty(n_samples, device=theta.device, dtype=theta.dtype)
+        paths = None
+        for lo in range(0, n_samples, chunk_size):
+            res = _ps.particle_smoother(sde, self.observations, observation_likelihood, theta[lo:lo + chunk_size], self.time_step,
+                                        n_particles=n_particles, n_draws=1, initial_state=x0,
+                                        positive_dims=self.state_space.positive_dims, proposal=proposal)
+            if paths is None:
+                paths = torch.empty(n_samples, *res.paths.shape[2:], device=theta.device, dtype=res.paths.dtype)
+            loglik[lo:lo + chunk_size] = res.log_likelihood
+            min_ess[lo:lo + chunk_size] = res.effective_sample_size.min(dim=1).values
+            paths[lo:lo + chunk_size] = res.paths[:, 0]
+        T1 = paths.shape[1]
+        times = torch.arange(T1, device=theta.device, dtype=theta.dtype) * self.time_step
+        log_w = log_prior.double() + loglik.double() - log_q
+        bad = int((torch.isnan(log_w) | torch.isposinf(log_w)).sum())
+        draws = (paths, theta, log_w) if return_draws else (None, None, None)
+        nan_x = torch.full((T1, S), float("nan"), device=theta.device, dtype=paths.dtype)
+        nan_q = Quantiles(*([nan_x] * len(QUANTILE_LEVELS)))
+        m = float(log_w.max()) if bad == 0 else float("nan")
+        if bad > 0 or m == float("-inf"):    # as reweight_parameters: NaN weights, or all weights zero
+            head = (float("nan"),) * 3 if bad > 0 else (float("-inf"), float("inf"), 0.0)
+            return PathReweighting(*head, n_samples, bad, min_ess, times, nan_x, nan_x, nan_q, *draws)
+        w = torch.exp(log_w - m)
+        s1, s2 = float(w.sum()), float((w * w).sum())
+        ess = s1 * s1 / s2
+        wn = w / s1
+        keep = wn > 0                                        # a dead filter's NaN path has weight zero: it enters no estimate
+        x, wk = paths[keep].double().reshape(int(keep.sum()), T1 * S), wn[keep]
+        mean = (wk[:, None] * x).sum(dim=0)
+        std = (wk[:, None] * (x - mean) ** 2).sum(dim=0).sqrt()
+        quant = _weighted_quantiles(x, wk)
+        shape = lambda v: v.to(paths.dtype).reshape(T1, S)
+        return PathReweighting(
+            m + math.log(s1) - math.log(n_samples), math.sqrt(max(1.0 / ess - 1.0 / n_samples, 0.0)), ess, n_samples, 0, min_ess,
+            times, shape(mean), shape(std), Quantiles(*(shape(v) for v in quant.unbind(0))), *draws)
 
     def summary(self, n_samples: int = 1000, mixed_precision: bool = False) -> VariationalPosteriorSummary:
         s = self.sample(n_samples, mixed_precision)
