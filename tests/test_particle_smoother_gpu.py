@@ -142,8 +142,11 @@ def test_bootstrap_replay_matches_float64_segments(name, rows, N, D):
         assert (paths[:, :, 1:] == sref.FLOOR).any()                # filters 0 and 4 start at the floor: the clamp was exercised
 
 
+# the rate-law network and the linear-diagonal model (S = 3 through a dense [4, 3] H: the O <= 4 instantiation) at the smallest size:
+# with ou / lv / sir every route of the guided replay's dispatch is launched
 @pytest.mark.parametrize("name,N,D", [pytest.param(name, N, D, id=f"{name}-{N}-D{D}")
-                                      for name in ("ou", "lv", "sir") for N in (64, 1024) for D in (1, 96)])
+                                      for name in ("ou", "lv", "sir") for N in (64, 1024) for D in (1, 96)]
+                         + [pytest.param(name, 64, D, id=f"{name}-64-D{D}") for name in ("autoreg", "lindiag3") for D in (1, 96)])
 def test_guided_replay_matches_float64_bridge_segments(name, N, D):
     paths = _check(name, None, N, D, "bridge")
     if name in ("lv", "sir") and D == 96:

@@ -331,12 +331,6 @@ template <bool CNT> __global__ void __launch_bounds__(256) elbo_tail_bwd_kernel(
     if (tid < p.P) { p.g_post_mean[tid] = gq[tid]; p.g_post_log_std[tid] = gq[kTailMaxDim + tid]; }
 }
 
-// the count arguments of a vsde_*count_* entry point (NULL: the Gaussian form); checked after the shared checks
-struct CountArgs { int lik_kind; double scale, dispersion; const float *row_const; };
-static int count_fill(CountLik &c, const CountArgs *ca, int K) {
-    return ca ? count_lik(c, ca->lik_kind, ca->scale, ca->dispersion, ca->row_const, K) : 0;
-}
-
 static int tail_fill(TailParams &p, int B, int K, int S, int O, int P, const float *x_obs, const float *obs_values,
                      const float *obs_matrix, double variance, const float *theta, int prior_type, double prior_mean,
                      double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *theta_positive_mask_host,
@@ -457,18 +451,6 @@ static int launch_log_weights(const LogWeightParams &p, hipStream_t s, const Cou
     else hipLaunchKernelGGL((log_weight_kernel<KIND, S, NR, KIN, false>), dim3(p.tail.B), dim3(256), 0, s, p, CountLik{});
     VSDE_CHECK_HIP(hipGetLastError());
     return 0;
-}
-
-// kinds 0 (caller's coefficients) and 3 (linear-diagonal) at any S in 1..16
-template <int KIND, int S = 1>
-static int dispatch_log_weights(int s_dim, const LogWeightParams &p, hipStream_t s, const CountLik *c = nullptr) {
-    if (s_dim == S) return launch_log_weights<KIND, S>(p, s, c);
-    if constexpr (S < kTailMaxDim) {
-        return dispatch_log_weights<KIND, S + 1>(s_dim, p, s, c);
-    } else {
-        set_error("state_dim %d not supported by the log-weight kernel (1..%d)", s_dim, kTailMaxDim);
-        return VSDE_E_STATE;
-    }
 }
 
 // Streamed reduction of log-weights into a running fp64 state
@@ -649,41 +631,43 @@ extern "C" int vsde_count_elbo_tail_bwd(int B, int K, int S, int O, int P, const
 }
 
 
-static int log_weights_impl(const CountArgs *ca, int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *drift, const float *diffusion, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+// rt.kind 0: the caller's drift / diffusion tensors; 1..4: the route's own.  P is the dim of theta (prior / posterior terms) and PM
+// the route's parameter dim: P, or with rate laws the effective constants' 2R (`rates`; NULL on the other routes)
+static int log_weights_impl(const CountArgs *ca, const SdeRoute &rt, int B, int T, int S, int K, int O, int P, int PM, const float *z, const float *means, const float *chol, const float *drift, const float *diffusion, const float *theta, const float *rates, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
+    LogWeightParams p = {};
+    // a network's descriptors fix S, so their checks come first; the built-in kinds' relations come after the kernel's own dims
+    // (S beyond its 16: VSDE_E_STATE)
+    int rc = rt.descriptors ? crn_route_net(rt, S, PM, p.net) : 0;
+    if (rc) return rc;
     VSDE_CHECK_ARG(B > 0 && T > 0 && S > 0 && K >= 0, VSDE_E_BADARG, "bad log-weight dims B=%d T=%d S=%d K=%d", B, T, S, K);
     VSDE_CHECK_ARG(S <= kTailMaxDim, VSDE_E_STATE, "state_dim %d not supported by the log-weight kernel (1..%d)", S, kTailMaxDim);
-    VSDE_CHECK_ARG(kind >= 0 && kind <= 3, VSDE_E_BADARG, "unknown SDE kind %d (0 = caller's coefficients, 1..3 built in)", kind);
-    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim");
-    VSDE_CHECK_ARG(kind != 0 || (drift && diffusion), VSDE_E_BADARG, "kind 0 needs the drift and diffusion tensors");
-    VSDE_CHECK_ARG(z && means && chol && log_w && (K == 0 || obs_rows) && time_step > 0, VSDE_E_BADARG,
+    VSDE_CHECK_ARG(rt.descriptors || (rt.kind >= 0 && rt.kind <= 3), VSDE_E_BADARG, "unknown SDE kind %d (0 = caller's coefficients, 1..3 built in)", rt.kind);
+    if (!rt.descriptors && rt.kind && (rc = kind_check(rt.kind, S, PM))) return rc;
+    VSDE_CHECK_ARG(rt.kind != 0 || (drift && diffusion), VSDE_E_BADARG, "kind 0 needs the drift and diffusion tensors");
+    VSDE_CHECK_ARG(z && means && chol && (rates || rt.descriptors < 2) && log_w && (K == 0 || obs_rows) && time_step > 0, VSDE_E_BADARG,
                    "NULL argument / bad time_step");
-    LogWeightParams p = {};
     // the tail's x_obs and path-term inputs are not read here (the states come from z): any non-NULL pointer passes its check
-    int rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
-                       post_mean, post_log_std, theta_positive_mask_host, z, z, z);
+    rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
+                   post_mean, post_log_std, theta_positive_mask_host, z, z, z);
     if (rc) return rc;
     CountLik c = {};
     if ((rc = count_fill(c, ca, K))) return rc;
-    p.T = T; p.z = z; p.means = means; p.chol = chol; p.drift = drift; p.diffusion = diffusion; p.obs_rows = obs_rows;
+    p.T = T; p.z = z; p.means = means; p.chol = chol; p.drift = drift; p.diffusion = diffusion; p.obs_rows = obs_rows; p.rates = rates;
     p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
-    hipStream_t s = (hipStream_t)stream;
-    switch (kind) {
-        case 1: return launch_log_weights<1, 1>(p, s, ca ? &c : nullptr);
-        case 2: return launch_log_weights<2, 2>(p, s, ca ? &c : nullptr);
-        case 3: return dispatch_log_weights<3>(S, p, s, ca ? &c : nullptr);
-        default: return dispatch_log_weights<0>(S, p, s, ca ? &c : nullptr);
-    }
+    const auto launch = [&](auto kind, auto ns, auto nr, auto kin) {
+        return launch_log_weights<decltype(kind)::value, decltype(ns)::value, decltype(nr)::value, decltype(kin)::value>(p, (hipStream_t)stream, ca ? &c : nullptr);
+    };
+    if (rt.kind == 0) return dispatch_dim<kTailMaxDim>(S, [&](auto ns) { return launch(IntC<0>{}, ns, IntC<EmDims<0>::P>{}, std::false_type{}); });
+    return route_dispatch<kTailMaxDim>(rt, S, p.net.R, launch);
 }
 
 extern "C" int vsde_log_weights(int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *drift, const float *diffusion, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
-    return log_weights_impl(nullptr, kind, B, T, S, K, O, P, z, means, chol, drift, diffusion, theta, obs_rows, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
+    return log_weights_impl(nullptr, SdeRoute{kind}, B, T, S, K, O, P, P, z, means, chol, drift, diffusion, theta, nullptr, obs_rows, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
 }
 
 extern "C" int vsde_count_log_weights(int kind, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *drift, const float *diffusion, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind, double scale, double dispersion, const float *row_const, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
     const CountArgs ca = {lik_kind, scale, dispersion, row_const};
-    return log_weights_impl(&ca, kind, B, T, S, K, O, P, z, means, chol, drift, diffusion, theta, obs_rows, obs_values, obs_matrix, 1.0, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
+    return log_weights_impl(&ca, SdeRoute{kind}, B, T, S, K, O, P, P, z, means, chol, drift, diffusion, theta, nullptr, obs_rows, obs_values, obs_matrix, 1.0, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
 }
 
 extern "C" int vsde_log_weight_accumulate(int n, const float *log_w, double *state6, void *stream) {
@@ -694,60 +678,20 @@ extern "C" int vsde_log_weight_accumulate(int n, const float *log_w, double *sta
     return 0;
 }
 
-static int crn_log_weights_impl(const CountArgs *ca, const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
-    LogWeightParams p = {};
-    int rc = crn_net(net, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0 && K >= 0, VSDE_E_BADARG, "bad log-weight dims B=%d T=%d S=%d K=%d", B, T, S, K);
-    VSDE_CHECK_ARG(z && means && chol && log_w && (K == 0 || obs_rows) && time_step > 0, VSDE_E_BADARG,
-                   "NULL argument / bad time_step");
-    rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
-                   post_mean, post_log_std, theta_positive_mask_host, z, z, z);
-    if (rc) return rc;
-    CountLik c = {};
-    if ((rc = count_fill(c, ca, K))) return rc;
-    p.T = T; p.z = z; p.means = means; p.chol = chol; p.obs_rows = obs_rows;
-    p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
-    return crn_dispatch(S, P, [&](auto ns, auto nr) {
-        return launch_log_weights<4, decltype(ns)::value, decltype(nr)::value>(p, (hipStream_t)stream, ca ? &c : nullptr);
-    });
-}
-
 extern "C" int vsde_crn_log_weights(const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
-    return crn_log_weights_impl(nullptr, net, B, T, S, K, O, P, z, means, chol, theta, obs_rows, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
+    return log_weights_impl(nullptr, crn_route(net), B, T, S, K, O, P, P, z, means, chol, nullptr, nullptr, theta, nullptr, obs_rows, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
 }
 
 extern "C" int vsde_crn_count_log_weights(const vsde_crn_network *net, int B, int T, int S, int K, int O, int P, const float *z, const float *means, const float *chol, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind, double scale, double dispersion, const float *row_const, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
     const CountArgs ca = {lik_kind, scale, dispersion, row_const};
-    return crn_log_weights_impl(&ca, net, B, T, S, K, O, P, z, means, chol, theta, obs_rows, obs_values, obs_matrix, 1.0, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
-}
-
-static int crn_kinetic_log_weights_impl(const CountArgs *ca, const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K, int O, int P, int R_eff, const float *z, const float *means, const float *chol, const float *theta, const float *rates, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
-    LogWeightParams p = {};
-    int rc = crn_net(net, S, R_eff, p.net, true);
-    if (rc) return rc;
-    rc = crn_kinetics(kin, S, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0 && K >= 0, VSDE_E_BADARG, "bad log-weight dims B=%d T=%d S=%d K=%d", B, T, S, K);
-    VSDE_CHECK_ARG(z && means && chol && rates && log_w && (K == 0 || obs_rows) && time_step > 0, VSDE_E_BADARG,
-                   "NULL argument / bad time_step");
-    rc = tail_fill(p.tail, B, K, S, O, P, z, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std,
-                   post_mean, post_log_std, theta_positive_mask_host, z, z, z);
-    if (rc) return rc;
-    CountLik c = {};
-    if ((rc = count_fill(c, ca, K))) return rc;
-    p.T = T; p.z = z; p.means = means; p.chol = chol; p.obs_rows = obs_rows; p.rates = rates;
-    p.state_pos = mask_bits(state_positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step); p.log_w = log_w;
-    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
-        return launch_log_weights<4, decltype(ns)::value, decltype(nr)::value, true>(p, (hipStream_t)stream, ca ? &c : nullptr);
-    });
+    return log_weights_impl(&ca, crn_route(net), B, T, S, K, O, P, P, z, means, chol, nullptr, nullptr, theta, nullptr, obs_rows, obs_values, obs_matrix, 1.0, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
 }
 
 extern "C" int vsde_crn_kinetic_log_weights(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K, int O, int P, int R_eff, const float *z, const float *means, const float *chol, const float *theta, const float *rates, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
-    return crn_kinetic_log_weights_impl(nullptr, net, kin, B, T, S, K, O, P, R_eff, z, means, chol, theta, rates, obs_rows, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
+    return log_weights_impl(nullptr, crn_route(net, kin), B, T, S, K, O, P, R_eff, z, means, chol, nullptr, nullptr, theta, rates, obs_rows, obs_values, obs_matrix, variance, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
 }
 
 extern "C" int vsde_crn_kinetic_count_log_weights(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int K, int O, int P, int R_eff, const float *z, const float *means, const float *chol, const float *theta, const float *rates, const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind, double scale, double dispersion, const float *row_const, int prior_type, double prior_mean, double prior_std, const float *post_mean, const float *post_log_std, const uint8_t *state_positive_mask_host, const uint8_t *theta_positive_mask_host, double time_step, float *log_w, void *stream) {
     const CountArgs ca = {lik_kind, scale, dispersion, row_const};
-    return crn_kinetic_log_weights_impl(&ca, net, kin, B, T, S, K, O, P, R_eff, z, means, chol, theta, rates, obs_rows, obs_values, obs_matrix, 1.0, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
+    return log_weights_impl(&ca, crn_route(net, kin), B, T, S, K, O, P, R_eff, z, means, chol, nullptr, nullptr, theta, rates, obs_rows, obs_values, obs_matrix, 1.0, prior_type, prior_mean, prior_std, post_mean, post_log_std, state_positive_mask_host, theta_positive_mask_host, time_step, log_w, stream);
 }

@@ -469,11 +469,13 @@ __global__ void __launch_bounds__(pf_max_n(KIND, NS, NO > 0)) pf_kernel(PfParams
     if (j == 0) p.loglik[m] = loglik;
 }
 
-// argument checks shared by the three entry points (before any HIP call) and the parameter block
-static int pf_fill(PfParams &p, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta, const int *obs_rows,
-                   const float *obs_values, const float *obs_matrix, double variance, const uint32_t *key, double time_step,
-                   const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess, float *filtered_mean,
-                   float *filtered_std, float *particles, int *ancestors) {
+// the dims and the time step of a filter, checked alike for the filter and for the replay of its genealogy (guided: the bridge
+// proposal's own limits first)
+static int pf_check(bool guided, int M, int N, int S, int K, int O, double time_step) {
+    VSDE_CHECK_ARG(!guided || (S >= 1 && S <= kPfGuidedMaxS), VSDE_E_BADARG, "guided particle filter: state_dim %d (1..%d supported)", S,
+                   kPfGuidedMaxS);
+    VSDE_CHECK_ARG(!guided || (O >= 1 && O <= kPfGuidedMaxO), VSDE_E_BADARG, "guided particle filter: obs_dim %d (1..%d supported)", O,
+                   kPfGuidedMaxO);
     VSDE_CHECK_ARG(M >= 1 && K >= 1, VSDE_E_BADARG, "bad particle-filter dims M=%d K=%d", M, K);
     VSDE_CHECK_ARG(N >= kWave && N <= kPfMaxN && N % kWave == 0, VSDE_E_BADARG,
                    "particle filter: %d particles (a multiple of %d up to %d supported)", N, kWave, kPfMaxN);
@@ -481,46 +483,27 @@ static int pf_fill(PfParams &p, int M, int N, int S, int P, int K, int O, const 
                    (long long)M * N);
     VSDE_CHECK_ARG(S >= 1 && S <= kPfMaxS, VSDE_E_BADARG, "particle filter: state_dim %d (1..%d supported)", S, kPfMaxS);
     VSDE_CHECK_ARG(O >= 1 && O <= kPfMaxO, VSDE_E_BADARG, "particle filter: obs_dim %d (1..%d supported)", O, kPfMaxO);
+    VSDE_CHECK_ARG(time_step > 0, VSDE_E_BADARG, "bad variance / time_step");
+    return 0;
+}
+
+// the Gaussian observation model: the filter's weights and the bridge proposal; the count entry points pass variance 1
+static int pf_obs(PfParams &p, int S, int O, const float *obs_values, const float *obs_matrix, double variance) {
     VSDE_CHECK_ARG(obs_matrix || O == S, VSDE_E_BADARG, "without an observation matrix obs_dim must equal state_dim (%d vs %d)", O, S);
-    VSDE_CHECK_ARG(variance > 0 && time_step > 0, VSDE_E_BADARG, "bad variance / time_step");
-    VSDE_CHECK_ARG(x0 && theta && obs_rows && obs_values && key && log_likelihood && increments && ess && filtered_mean && filtered_std,
-                   VSDE_E_BADARG, "NULL argument");
-    p.M = M; p.N = N; p.S = S; p.P = P; p.K = K; p.O = O;
-    p.x0 = x0; p.theta = theta; p.obs_values = obs_values; p.obs_matrix = obs_matrix; p.rows = obs_rows; p.key = key;
-    p.loglik = log_likelihood; p.incr = increments; p.ess = ess; p.mean = filtered_mean; p.std = filtered_std;
-    p.particles = particles; p.ancestors = ancestors;
+    VSDE_CHECK_ARG(variance > 0, VSDE_E_BADARG, "bad variance / time_step");
+    p.obs_values = obs_values; p.obs_matrix = obs_matrix; p.var = (float)variance;
+    p.inv_var = (float)(1.0 / variance); p.log_norm = (float)(-0.5 * log(2.0 * M_PI * variance));
+    return 0;
+}
+
+// what the filter and the replay read alike
+static void pf_fill(PfParams &p, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta, const int *obs_rows,
+                    const uint32_t *key, double time_step, const uint8_t *positive_mask_host) {
+    p.M = M; p.N = N; p.S = S; p.P = P; p.K = K; p.O = O; p.x0 = x0; p.theta = theta; p.rows = obs_rows; p.key = key;
     p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    p.inv_var = (float)(1.0 / variance); p.log_norm = (float)(-0.5 * log(2.0 * M_PI * variance)); p.log_n = (float)log((double)N);
-    return 0;
 }
 
-// the count entry points: the checks of pf_fill (its variance check sees 1), then their own
-static int pf_fill_count(PfParams &p, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
-                         const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind, double scale,
-                         double dispersion, const float *row_const, const uint32_t *key, double time_step,
-                         const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
-                         float *filtered_mean, float *filtered_std, float *particles, int *ancestors) {
-    int rc = pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, 1.0, key, time_step, positive_mask_host,
-                     log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
-    if (rc) return rc;
-    return count_lik(p.cl, lik_kind, scale, dispersion, row_const, K);
-}
-
-// the guided entry points: their own limits first, then the checks of pf_fill
-static int pf_fill_guided(PfParams &p, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
-                          const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance, const uint32_t *key,
-                          double time_step, const uint8_t *positive_mask_host, float *log_likelihood, float *increments, float *ess,
-                          float *filtered_mean, float *filtered_std, float *particles, int *ancestors, float *log_weights) {
-    VSDE_CHECK_ARG(S >= 1 && S <= kPfGuidedMaxS, VSDE_E_BADARG, "guided particle filter: state_dim %d (1..%d supported)", S, kPfGuidedMaxS);
-    VSDE_CHECK_ARG(O >= 1 && O <= kPfGuidedMaxO, VSDE_E_BADARG, "guided particle filter: obs_dim %d (1..%d supported)", O, kPfGuidedMaxO);
-    int rc = pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step, positive_mask_host,
-                     log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
-    if (rc) return rc;
-    p.var = (float)variance; p.log_weights = log_weights;
-    return 0;
-}
-
-template <class Kern> static int pf_launch(Kern kern, const PfParams &p, void *stream, int max_n = kPfMaxN) {
+template <class Kern> static int pf_launch(Kern kern, const PfParams &p, void *stream, int max_n) {
     VSDE_CHECK_ARG(p.N <= max_n, VSDE_E_BADARG, "particle filter: %d particles (up to %d supported at state_dim %d of this SDE)", p.N,
                    max_n, p.S);
     const size_t lds = ((size_t)p.N * ((p.S | 1) + 1) + kPfRed) * sizeof(float);
@@ -531,20 +514,39 @@ template <class Kern> static int pf_launch(Kern kern, const PfParams &p, void *s
     return 0;
 }
 
-// the guided instantiation of (KIND, NS, NR, KIN) for the call's observation dim: the bound NO is 2 or 4
-template <int KIND, int NS, int NR, bool KIN> static int pf_launch_guided(const PfParams &p, void *stream) {
-    if (p.O <= 2) return pf_launch(pf_kernel<KIND, NS, NR, KIN, 2>, p, stream, pf_max_n(KIND, NS, true));
-    return pf_launch(pf_kernel<KIND, NS, NR, KIN, 4>, p, stream, pf_max_n(KIND, NS, true));
-}
-
-// crn_dispatch for the guided filter's S <= 4 (checked by pf_fill_guided)
-template <class F> static int pf_crn_dispatch_guided(int S, int R, F &&f) {
-    switch (S) {
-        case 1: return crn_dispatch_r<1>(R, f);
-        case 2: return crn_dispatch_r<2>(R, f);
-        case 3: return crn_dispatch_r<3>(R, f);
-        default: return crn_dispatch_r<4>(R, f);
-    }
+// One body for the vsde_*particle_filter entry points: any route, bootstrap or guided (the bridge proposal; log_weights is its
+// optional output), Gaussian or (ca, bootstrap only) count observation term.  Every check comes before the first HIP call.
+static int particle_filter(const SdeRoute &rt, bool guided, const CountArgs *ca, int M, int N, int S, int P, int K, int O,
+                           const float *x0, const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                           double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                           float *log_likelihood, float *increments, float *ess, float *filtered_mean, float *filtered_std,
+                           float *particles, int *ancestors, float *log_weights, void *stream) {
+    PfParams p = {};
+    int rc = route_check(rt, S, P, p.net);
+    if (!rc) rc = pf_check(guided, M, N, S, K, O, time_step);
+    if (!rc) rc = pf_obs(p, S, O, obs_values, obs_matrix, variance);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(x0 && theta && obs_rows && obs_values && key && log_likelihood && increments && ess && filtered_mean && filtered_std,
+                   VSDE_E_BADARG, "NULL argument");
+    if ((rc = count_fill(p.cl, ca, K))) return rc;
+    pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, key, time_step, positive_mask_host);
+    p.loglik = log_likelihood; p.incr = increments; p.ess = ess; p.mean = filtered_mean; p.std = filtered_std;
+    p.particles = particles; p.ancestors = ancestors; p.log_weights = log_weights; p.log_n = (float)log((double)N);
+    // the instantiation of (KIND, NS, NR, KIN) for the call: guided at the bound NO = 2 or 4 of its observation dim (S <= 4), or
+    // bootstrap with either observation term
+    if (guided)
+        return route_dispatch<kPfGuidedMaxS, kPfGuidedMaxS>(rt, S, p.net.R, [&](auto kind, auto ns, auto nr, auto kin) {
+            constexpr int KIND = decltype(kind)::value, NS = decltype(ns)::value, NR = decltype(nr)::value, max_n = pf_max_n(KIND, NS, true);
+            constexpr bool KIN = decltype(kin)::value;
+            if (O <= 2) return pf_launch(pf_kernel<KIND, NS, NR, KIN, 2>, p, stream, max_n);
+            return pf_launch(pf_kernel<KIND, NS, NR, KIN, 4>, p, stream, max_n);
+        });
+    return route_dispatch<kPfMaxS>(rt, S, p.net.R, [&](auto kind, auto ns, auto nr, auto kin) {
+        constexpr int KIND = decltype(kind)::value, NS = decltype(ns)::value, NR = decltype(nr)::value, max_n = pf_max_n(KIND, NS);
+        constexpr bool KIN = decltype(kin)::value;
+        if (ca) return pf_launch(pf_kernel<KIND, NS, NR, KIN, 0, true>, p, stream, max_n);
+        return pf_launch(pf_kernel<KIND, NS, NR, KIN, 0, false>, p, stream, max_n);
+    });
 }
 
 
@@ -628,85 +630,55 @@ __global__ void __launch_bounds__(kRpThreads) rp_kernel(PfParams p, RpParams r) 
     }
 }
 
-// argument checks of the replay entry points (before any HIP call; the wording of pf_fill) and the parameter blocks
-static int rp_fill(PfParams &p, RpParams &r, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
-                   const float *theta, const int *obs_rows, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
-                   const float *particles, const int *ancestors, const int *last_slot, float *paths, int *lineage) {
-    VSDE_CHECK_ARG(M >= 1 && K >= 1, VSDE_E_BADARG, "bad particle-filter dims M=%d K=%d", M, K);
-    VSDE_CHECK_ARG(N >= kWave && N <= kPfMaxN && N % kWave == 0, VSDE_E_BADARG,
-                   "particle filter: %d particles (a multiple of %d up to %d supported)", N, kWave, kPfMaxN);
-    VSDE_CHECK_ARG((int64_t)M * N < ((int64_t)1 << 32), VSDE_E_BADARG, "particle filter: M N = %lld paths (below 2^32 supported)",
-                   (long long)M * N);
-    VSDE_CHECK_ARG(S >= 1 && S <= kPfMaxS, VSDE_E_BADARG, "particle filter: state_dim %d (1..%d supported)", S, kPfMaxS);
-    VSDE_CHECK_ARG(O >= 1 && O <= kPfMaxO, VSDE_E_BADARG, "particle filter: obs_dim %d (1..%d supported)", O, kPfMaxO);
+// One body for the vsde_*filter_replay entry points: any route, plain or guided (the bridge proposal reads the observation model
+// again; the plain forwarders pass none).  Every check comes before the first HIP call.
+static int filter_replay(const SdeRoute &rt, bool guided, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
+                         const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                         const uint32_t *key, double time_step, const uint8_t *positive_mask_host, const float *particles,
+                         const int *ancestors, const int *last_slot, float *paths, int *lineage, void *stream) {
+    PfParams p = {};
+    int rc = route_check(rt, S, P, p.net);
+    if (!rc) rc = pf_check(guided, M, N, S, K, O, time_step);
+    if (!rc && guided) rc = pf_obs(p, S, O, obs_values, obs_matrix, variance);
+    if (rc) return rc;
     VSDE_CHECK_ARG(D >= 1, VSDE_E_BADARG, "filter replay: %d draws per filter (>= 1 supported)", D);
     VSDE_CHECK_ARG(T >= 0, VSDE_E_BADARG, "filter replay: %d grid steps", T);
     VSDE_CHECK_ARG((int64_t)M * D * K < ((int64_t)1 << 31), VSDE_E_BADARG, "filter replay: M D K = %lld segments (below 2^31 supported)",
                    (long long)M * D * K);
-    VSDE_CHECK_ARG(time_step > 0, VSDE_E_BADARG, "bad variance / time_step");
-    VSDE_CHECK_ARG(x0 && theta && obs_rows && key && particles && ancestors && last_slot && paths, VSDE_E_BADARG, "NULL argument");
-    p.M = M; p.N = N; p.S = S; p.P = P; p.K = K; p.O = O;
-    p.x0 = x0; p.theta = theta; p.rows = obs_rows; p.key = key;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    r.D = D; r.T = T; r.particles = particles; r.ancestors = ancestors; r.last_slot = last_slot; r.paths = paths; r.lineage = lineage;
-    return 0;
-}
-
-// the guided replay: the guided filter's limits first, then the checks of rp_fill and the observation model of the proposal
-static int rp_fill_guided(PfParams &p, RpParams &r, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
-                          const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
-                          const uint32_t *key, double time_step, const uint8_t *positive_mask_host, const float *particles,
-                          const int *ancestors, const int *last_slot, float *paths, int *lineage) {
-    VSDE_CHECK_ARG(S >= 1 && S <= kPfGuidedMaxS, VSDE_E_BADARG, "guided particle filter: state_dim %d (1..%d supported)", S, kPfGuidedMaxS);
-    VSDE_CHECK_ARG(O >= 1 && O <= kPfGuidedMaxO, VSDE_E_BADARG, "guided particle filter: obs_dim %d (1..%d supported)", O, kPfGuidedMaxO);
-    VSDE_CHECK_ARG(obs_matrix || O == S, VSDE_E_BADARG, "without an observation matrix obs_dim must equal state_dim (%d vs %d)", O, S);
-    VSDE_CHECK_ARG(variance > 0, VSDE_E_BADARG, "bad variance / time_step");
-    int rc = rp_fill(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, key, time_step, positive_mask_host, particles, ancestors,
-                     last_slot, paths, lineage);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(obs_values, VSDE_E_BADARG, "NULL argument");
-    p.obs_values = obs_values; p.obs_matrix = obs_matrix; p.var = (float)variance;
-    return 0;
-}
-
-template <class Kern> static int rp_launch(Kern kern, const PfParams &p, const RpParams &r, void *stream) {
-    const int64_t threads = (int64_t)p.M * r.D * p.K;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((threads + kRpThreads - 1) / kRpThreads)), dim3(kRpThreads), 0, (hipStream_t)stream, p, r);
-    VSDE_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-template <int KIND, int NS, int NR, bool KIN> static int rp_launch_guided(const PfParams &p, const RpParams &r, void *stream) {
-    if (p.O <= 2) return rp_launch(rp_kernel<KIND, NS, NR, KIN, 2>, p, r, stream);
-    return rp_launch(rp_kernel<KIND, NS, NR, KIN, 4>, p, r, stream);
+    VSDE_CHECK_ARG(x0 && theta && obs_rows && key && particles && ancestors && last_slot && paths && (obs_values || !guided),
+                   VSDE_E_BADARG, "NULL argument");
+    pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, key, time_step, positive_mask_host);
+    const RpParams r = {D, T, particles, ancestors, last_slot, paths, lineage};
+    const auto launch = [&](auto kern) {
+        const int64_t threads = (int64_t)M * D * K;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((threads + kRpThreads - 1) / kRpThreads)), dim3(kRpThreads), 0, (hipStream_t)stream, p, r);
+        VSDE_CHECK_HIP(hipGetLastError());
+        return 0;
+    };
+    if (guided)
+        return route_dispatch<kPfGuidedMaxS, kPfGuidedMaxS>(rt, S, p.net.R, [&](auto kind, auto ns, auto nr, auto kin) {
+            constexpr int KIND = decltype(kind)::value, NS = decltype(ns)::value, NR = decltype(nr)::value;
+            if (O <= 2) return launch(rp_kernel<KIND, NS, NR, decltype(kin)::value, 2>);
+            return launch(rp_kernel<KIND, NS, NR, decltype(kin)::value, 4>);
+        });
+    return route_dispatch<kPfMaxS>(rt, S, p.net.R, [&](auto kind, auto ns, auto nr, auto kin) {
+        return launch(rp_kernel<decltype(kind)::value, decltype(ns)::value, decltype(nr)::value, decltype(kin)::value>);
+    });
 }
 
 }  // namespace vsde
 
 using namespace vsde;
 
+// The exported functions: each builds its route and forwards to the one body of its operation
 extern "C" int vsde_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
                                     const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
                                     const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
                                     float *log_likelihood, float *increments, float *ess, float *filtered_mean, float *filtered_std,
                                     float *particles, int *ancestors, void *stream) {
-    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);
-    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim");
-    PfParams p = {};
-    int rc = pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step, positive_mask_host,
-                     log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
-    if (rc) return rc;
-    if (kind == 1) return pf_launch(pf_kernel<1>, p, stream);
-    if (kind == 2) return pf_launch(pf_kernel<2>, p, stream);
-    switch (S) {
-#define VSDE_PF_DIAG(n) case n: return pf_launch(pf_kernel<3, n>, p, stream)
-        VSDE_PF_DIAG(1); VSDE_PF_DIAG(2); VSDE_PF_DIAG(3); VSDE_PF_DIAG(4); VSDE_PF_DIAG(5); VSDE_PF_DIAG(6); VSDE_PF_DIAG(7); VSDE_PF_DIAG(8);
-        VSDE_PF_DIAG(9); VSDE_PF_DIAG(10); VSDE_PF_DIAG(11); VSDE_PF_DIAG(12); VSDE_PF_DIAG(13); VSDE_PF_DIAG(14); VSDE_PF_DIAG(15);
-        default: VSDE_PF_DIAG(16);
-#undef VSDE_PF_DIAG
-    }
+    return particle_filter(SdeRoute{kind}, false, nullptr, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance,
+                           key, time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std,
+                           particles, ancestors, nullptr, stream);
 }
 
 extern "C" int vsde_crn_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
@@ -714,15 +686,9 @@ extern "C" int vsde_crn_particle_filter(const vsde_crn_network *net, int M, int 
                                         double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
                                         float *log_likelihood, float *increments, float *ess, float *filtered_mean,
                                         float *filtered_std, float *particles, int *ancestors, void *stream) {
-    PfParams p = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n);
-    if (rc) return rc;
-    rc = pf_fill(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step, positive_mask_host,
-                 log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
-    if (rc) return rc;
-    p.net = n;
-    return crn_dispatch(S, P, [&](auto ns, auto nr) { return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value>, p, stream, pf_max_n(4, decltype(ns)::value)); });
+    return particle_filter(crn_route(net), false, nullptr, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance,
+                           key, time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std,
+                           particles, ancestors, nullptr, stream);
 }
 
 extern "C" int vsde_crn_kinetic_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P,
@@ -731,18 +697,9 @@ extern "C" int vsde_crn_kinetic_particle_filter(const vsde_crn_network *net, con
                                                 const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
                                                 float *log_likelihood, float *increments, float *ess, float *filtered_mean,
                                                 float *filtered_std, float *particles, int *ancestors, void *stream) {
-    PfParams p = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n, true);
-    if (!rc) rc = crn_kinetics(kin, S, n);
-    if (rc) return rc;
-    rc = pf_fill(p, M, N, S, P, K, O, x0, rates, obs_rows, obs_values, obs_matrix, variance, key, time_step, positive_mask_host,
-                 log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors);
-    if (rc) return rc;
-    p.net = n;
-    return crn_dispatch(S, n.R, [&](auto ns, auto nr) {
-        return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value, true>, p, stream, pf_max_n(4, decltype(ns)::value));
-    });
+    return particle_filter(crn_route(net, kin), false, nullptr, M, N, S, P, K, O, x0, rates, obs_rows, obs_values, obs_matrix,
+                           variance, key, time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std,
+                           particles, ancestors, nullptr, stream);
 }
 
 extern "C" int vsde_guided_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
@@ -750,23 +707,9 @@ extern "C" int vsde_guided_particle_filter(int kind, int M, int N, int S, int P,
                                            const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
                                            float *log_likelihood, float *increments, float *ess, float *filtered_mean,
                                            float *filtered_std, float *particles, int *ancestors, float *log_weights, void *stream) {
-    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);
-    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim");
-    PfParams p = {};
-    int rc = pf_fill_guided(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
-                            positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors,
-                            log_weights);
-    if (rc) return rc;
-    if (kind == 1) return pf_launch_guided<1, 1, EmDims<1>::P, false>(p, stream);
-    if (kind == 2) return pf_launch_guided<2, 2, EmDims<2>::P, false>(p, stream);
-    switch (S) {
-        case 1: return pf_launch_guided<3, 1, EmDims<3>::P, false>(p, stream);
-        case 2: return pf_launch_guided<3, 2, EmDims<3>::P, false>(p, stream);
-        case 3: return pf_launch_guided<3, 3, EmDims<3>::P, false>(p, stream);
-        default: return pf_launch_guided<3, 4, EmDims<3>::P, false>(p, stream);
-    }
+    return particle_filter(SdeRoute{kind}, true, nullptr, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance,
+                           key, time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std,
+                           particles, ancestors, log_weights, stream);
 }
 
 extern "C" int vsde_crn_guided_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
@@ -775,18 +718,9 @@ extern "C" int vsde_crn_guided_particle_filter(const vsde_crn_network *net, int 
                                                const uint8_t *positive_mask_host, float *log_likelihood, float *increments,
                                                float *ess, float *filtered_mean, float *filtered_std, float *particles,
                                                int *ancestors, float *log_weights, void *stream) {
-    PfParams p = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n);
-    if (rc) return rc;
-    rc = pf_fill_guided(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
-                        positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors,
-                        log_weights);
-    if (rc) return rc;
-    p.net = n;
-    return pf_crn_dispatch_guided(S, P, [&](auto ns, auto nr) {
-        return pf_launch_guided<4, decltype(ns)::value, decltype(nr)::value, false>(p, stream);
-    });
+    return particle_filter(crn_route(net), true, nullptr, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, variance,
+                           key, time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std,
+                           particles, ancestors, log_weights, stream);
 }
 
 extern "C" int vsde_crn_kinetic_guided_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S,
@@ -796,47 +730,22 @@ extern "C" int vsde_crn_kinetic_guided_particle_filter(const vsde_crn_network *n
                                                        float *log_likelihood, float *increments, float *ess, float *filtered_mean,
                                                        float *filtered_std, float *particles, int *ancestors, float *log_weights,
                                                        void *stream) {
-    PfParams p = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n, true);
-    if (!rc) rc = crn_kinetics(kin, S, n);
-    if (rc) return rc;
-    rc = pf_fill_guided(p, M, N, S, P, K, O, x0, rates, obs_rows, obs_values, obs_matrix, variance, key, time_step,
-                        positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles, ancestors,
-                        log_weights);
-    if (rc) return rc;
-    p.net = n;
-    return pf_crn_dispatch_guided(S, n.R, [&](auto ns, auto nr) {
-        return pf_launch_guided<4, decltype(ns)::value, decltype(nr)::value, true>(p, stream);
-    });
+    return particle_filter(crn_route(net, kin), true, nullptr, M, N, S, P, K, O, x0, rates, obs_rows, obs_values, obs_matrix,
+                           variance, key, time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std,
+                           particles, ancestors, log_weights, stream);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The bootstrap filter with a count observation term: the entry points above with the CNT instantiations
+// The bootstrap filter with a count observation term: the CNT instantiations
 extern "C" int vsde_count_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
                                           const int *obs_rows, const float *obs_values, const float *obs_matrix, int lik_kind,
                                           double scale, double dispersion, const float *row_const, const uint32_t *key,
                                           double time_step, const uint8_t *positive_mask_host, float *log_likelihood,
                                           float *increments, float *ess, float *filtered_mean, float *filtered_std,
                                           float *particles, int *ancestors, void *stream) {
-    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);
-    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim");
-    PfParams p = {};
-    int rc = pf_fill_count(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, lik_kind, scale, dispersion, row_const,
-                           key, time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std,
-                           particles, ancestors);
-    if (rc) return rc;
-    if (kind == 1) return pf_launch(pf_kernel<1, 1, EmDims<1>::P, false, 0, true>, p, stream);
-    if (kind == 2) return pf_launch(pf_kernel<2, 2, EmDims<2>::P, false, 0, true>, p, stream);
-    switch (S) {
-#define VSDE_PF_DIAG(n) case n: return pf_launch(pf_kernel<3, n, EmDims<3>::P, false, 0, true>, p, stream)
-        VSDE_PF_DIAG(1); VSDE_PF_DIAG(2); VSDE_PF_DIAG(3); VSDE_PF_DIAG(4); VSDE_PF_DIAG(5); VSDE_PF_DIAG(6); VSDE_PF_DIAG(7); VSDE_PF_DIAG(8);
-        VSDE_PF_DIAG(9); VSDE_PF_DIAG(10); VSDE_PF_DIAG(11); VSDE_PF_DIAG(12); VSDE_PF_DIAG(13); VSDE_PF_DIAG(14); VSDE_PF_DIAG(15);
-        default: VSDE_PF_DIAG(16);
-#undef VSDE_PF_DIAG
-    }
+    const CountArgs ca = {lik_kind, scale, dispersion, row_const};
+    return particle_filter(SdeRoute{kind}, false, &ca, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, 1.0, key,
+                           time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles,
+                           ancestors, nullptr, stream);
 }
 
 extern "C" int vsde_crn_count_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
@@ -846,18 +755,10 @@ extern "C" int vsde_crn_count_particle_filter(const vsde_crn_network *net, int M
                                               const uint8_t *positive_mask_host, float *log_likelihood, float *increments,
                                               float *ess, float *filtered_mean, float *filtered_std, float *particles,
                                               int *ancestors, void *stream) {
-    PfParams p = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n);
-    if (rc) return rc;
-    rc = pf_fill_count(p, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, lik_kind, scale, dispersion, row_const, key,
-                       time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles,
-                       ancestors);
-    if (rc) return rc;
-    p.net = n;
-    return crn_dispatch(S, P, [&](auto ns, auto nr) {
-        return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value, false, 0, true>, p, stream, pf_max_n(4, decltype(ns)::value));
-    });
+    const CountArgs ca = {lik_kind, scale, dispersion, row_const};
+    return particle_filter(crn_route(net), false, &ca, M, N, S, P, K, O, x0, theta, obs_rows, obs_values, obs_matrix, 1.0, key,
+                           time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles,
+                           ancestors, nullptr, stream);
 }
 
 extern "C" int vsde_crn_kinetic_count_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S,
@@ -867,64 +768,27 @@ extern "C" int vsde_crn_kinetic_count_particle_filter(const vsde_crn_network *ne
                                                       double time_step, const uint8_t *positive_mask_host, float *log_likelihood,
                                                       float *increments, float *ess, float *filtered_mean, float *filtered_std,
                                                       float *particles, int *ancestors, void *stream) {
-    PfParams p = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n, true);
-    if (!rc) rc = crn_kinetics(kin, S, n);
-    if (rc) return rc;
-    rc = pf_fill_count(p, M, N, S, P, K, O, x0, rates, obs_rows, obs_values, obs_matrix, lik_kind, scale, dispersion, row_const, key,
-                       time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles,
-                       ancestors);
-    if (rc) return rc;
-    p.net = n;
-    return crn_dispatch(S, n.R, [&](auto ns, auto nr) {
-        return pf_launch(pf_kernel<4, decltype(ns)::value, decltype(nr)::value, true, 0, true>, p, stream, pf_max_n(4, decltype(ns)::value));
-    });
+    const CountArgs ca = {lik_kind, scale, dispersion, row_const};
+    return particle_filter(crn_route(net, kin), false, &ca, M, N, S, P, K, O, x0, rates, obs_rows, obs_values, obs_matrix, 1.0, key,
+                           time_step, positive_mask_host, log_likelihood, increments, ess, filtered_mean, filtered_std, particles,
+                           ancestors, nullptr, stream);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
 // Replay of the filter's genealogy: posterior paths from the particles and ancestors the entry points above stored
-#define VSDE_RP_KIND_CHECKS                                                                                                          \
-    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);                                    \
-    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");        \
-    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");            \
-    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim")
-
 extern "C" int vsde_filter_replay(int kind, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0, const float *theta,
                                   const int *obs_rows, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
                                   const float *particles, const int *ancestors, const int *last_slot, float *paths, int *lineage,
                                   void *stream) {
-    VSDE_RP_KIND_CHECKS;
-    PfParams p = {};
-    RpParams r = {};
-    int rc = rp_fill(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, key, time_step, positive_mask_host, particles, ancestors,
-                     last_slot, paths, lineage);
-    if (rc) return rc;
-    if (kind == 1) return rp_launch(rp_kernel<1>, p, r, stream);
-    if (kind == 2) return rp_launch(rp_kernel<2>, p, r, stream);
-    switch (S) {
-#define VSDE_RP_DIAG(n) case n: return rp_launch(rp_kernel<3, n>, p, r, stream)
-        VSDE_RP_DIAG(1); VSDE_RP_DIAG(2); VSDE_RP_DIAG(3); VSDE_RP_DIAG(4); VSDE_RP_DIAG(5); VSDE_RP_DIAG(6); VSDE_RP_DIAG(7); VSDE_RP_DIAG(8);
-        VSDE_RP_DIAG(9); VSDE_RP_DIAG(10); VSDE_RP_DIAG(11); VSDE_RP_DIAG(12); VSDE_RP_DIAG(13); VSDE_RP_DIAG(14); VSDE_RP_DIAG(15);
-        default: VSDE_RP_DIAG(16);
-#undef VSDE_RP_DIAG
-    }
+    return filter_replay(SdeRoute{kind}, false, M, N, S, P, K, O, D, T, x0, theta, obs_rows, nullptr, nullptr, 1.0, key, time_step,
+                         positive_mask_host, particles, ancestors, last_slot, paths, lineage, stream);
 }
 
 extern "C" int vsde_crn_filter_replay(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, int D, int T,
                                       const float *x0, const float *theta, const int *obs_rows, const uint32_t *key, double time_step,
                                       const uint8_t *positive_mask_host, const float *particles, const int *ancestors,
                                       const int *last_slot, float *paths, int *lineage, void *stream) {
-    PfParams p = {};
-    RpParams r = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n);
-    if (rc) return rc;
-    rc = rp_fill(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, key, time_step, positive_mask_host, particles, ancestors, last_slot,
-                 paths, lineage);
-    if (rc) return rc;
-    p.net = n;
-    return crn_dispatch(S, P, [&](auto ns, auto nr) { return rp_launch(rp_kernel<4, decltype(ns)::value, decltype(nr)::value>, p, r, stream); });
+    return filter_replay(crn_route(net), false, M, N, S, P, K, O, D, T, x0, theta, obs_rows, nullptr, nullptr, 1.0, key, time_step,
+                         positive_mask_host, particles, ancestors, last_slot, paths, lineage, stream);
 }
 
 extern "C" int vsde_crn_kinetic_filter_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P,
@@ -932,19 +796,8 @@ extern "C" int vsde_crn_kinetic_filter_replay(const vsde_crn_network *net, const
                                               const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
                                               const float *particles, const int *ancestors, const int *last_slot, float *paths,
                                               int *lineage, void *stream) {
-    PfParams p = {};
-    RpParams r = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n, true);
-    if (!rc) rc = crn_kinetics(kin, S, n);
-    if (rc) return rc;
-    rc = rp_fill(p, r, M, N, S, P, K, O, D, T, x0, rates, obs_rows, key, time_step, positive_mask_host, particles, ancestors, last_slot,
-                 paths, lineage);
-    if (rc) return rc;
-    p.net = n;
-    return crn_dispatch(S, n.R, [&](auto ns, auto nr) {
-        return rp_launch(rp_kernel<4, decltype(ns)::value, decltype(nr)::value, true>, p, r, stream);
-    });
+    return filter_replay(crn_route(net, kin), false, M, N, S, P, K, O, D, T, x0, rates, obs_rows, nullptr, nullptr, 1.0, key,
+                         time_step, positive_mask_host, particles, ancestors, last_slot, paths, lineage, stream);
 }
 
 extern "C" int vsde_guided_filter_replay(int kind, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
@@ -952,40 +805,17 @@ extern "C" int vsde_guided_filter_replay(int kind, int M, int N, int S, int P, i
                                          double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
                                          const float *particles, const int *ancestors, const int *last_slot, float *paths,
                                          int *lineage, void *stream) {
-    VSDE_RP_KIND_CHECKS;
-    PfParams p = {};
-    RpParams r = {};
-    int rc = rp_fill_guided(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
-                            positive_mask_host, particles, ancestors, last_slot, paths, lineage);
-    if (rc) return rc;
-    if (kind == 1) return rp_launch_guided<1, 1, EmDims<1>::P, false>(p, r, stream);
-    if (kind == 2) return rp_launch_guided<2, 2, EmDims<2>::P, false>(p, r, stream);
-    switch (S) {
-        case 1: return rp_launch_guided<3, 1, EmDims<3>::P, false>(p, r, stream);
-        case 2: return rp_launch_guided<3, 2, EmDims<3>::P, false>(p, r, stream);
-        case 3: return rp_launch_guided<3, 3, EmDims<3>::P, false>(p, r, stream);
-        default: return rp_launch_guided<3, 4, EmDims<3>::P, false>(p, r, stream);
-    }
+    return filter_replay(SdeRoute{kind}, true, M, N, S, P, K, O, D, T, x0, theta, obs_rows, obs_values, obs_matrix, variance, key,
+                         time_step, positive_mask_host, particles, ancestors, last_slot, paths, lineage, stream);
 }
-#undef VSDE_RP_KIND_CHECKS
 
 extern "C" int vsde_crn_guided_filter_replay(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, int D, int T,
                                              const float *x0, const float *theta, const int *obs_rows, const float *obs_values,
                                              const float *obs_matrix, double variance, const uint32_t *key, double time_step,
                                              const uint8_t *positive_mask_host, const float *particles, const int *ancestors,
                                              const int *last_slot, float *paths, int *lineage, void *stream) {
-    PfParams p = {};
-    RpParams r = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n);
-    if (rc) return rc;
-    rc = rp_fill_guided(p, r, M, N, S, P, K, O, D, T, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
-                        positive_mask_host, particles, ancestors, last_slot, paths, lineage);
-    if (rc) return rc;
-    p.net = n;
-    return pf_crn_dispatch_guided(S, P, [&](auto ns, auto nr) {
-        return rp_launch_guided<4, decltype(ns)::value, decltype(nr)::value, false>(p, r, stream);
-    });
+    return filter_replay(crn_route(net), true, M, N, S, P, K, O, D, T, x0, theta, obs_rows, obs_values, obs_matrix, variance, key,
+                         time_step, positive_mask_host, particles, ancestors, last_slot, paths, lineage, stream);
 }
 
 extern "C" int vsde_crn_kinetic_guided_filter_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S,
@@ -994,17 +824,6 @@ extern "C" int vsde_crn_kinetic_guided_filter_replay(const vsde_crn_network *net
                                                      double variance, const uint32_t *key, double time_step,
                                                      const uint8_t *positive_mask_host, const float *particles, const int *ancestors,
                                                      const int *last_slot, float *paths, int *lineage, void *stream) {
-    PfParams p = {};
-    RpParams r = {};
-    CrnNet n;
-    int rc = crn_net(net, S, P, n, true);
-    if (!rc) rc = crn_kinetics(kin, S, n);
-    if (rc) return rc;
-    rc = rp_fill_guided(p, r, M, N, S, P, K, O, D, T, x0, rates, obs_rows, obs_values, obs_matrix, variance, key, time_step,
-                        positive_mask_host, particles, ancestors, last_slot, paths, lineage);
-    if (rc) return rc;
-    p.net = n;
-    return pf_crn_dispatch_guided(S, n.R, [&](auto ns, auto nr) {
-        return rp_launch_guided<4, decltype(ns)::value, decltype(nr)::value, true>(p, r, stream);
-    });
+    return filter_replay(crn_route(net, kin), true, M, N, S, P, K, O, D, T, x0, rates, obs_rows, obs_values, obs_matrix, variance,
+                         key, time_step, positive_mask_host, particles, ancestors, last_slot, paths, lineage, stream);
 }

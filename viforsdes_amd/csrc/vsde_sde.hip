@@ -449,300 +449,214 @@ __global__ void __launch_bounds__(256) coef_diag_bwd_kernel(CoefParams p) {
     }
 }
 
-static int em_check(int kind, int B, int T, int S, int P) {
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad Euler-Maruyama dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);
-    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
-    VSDE_CHECK_ARG(kind != 3 || (S >= 1 && S <= 32 && P == 2 * S), VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim <= 64");
+// ---------------------------------------------------------------------------------------------------------------------
+// Host: one body per operation, taking the model route (vsde_sde_coef.h: SdeRoute); the exported functions below build the route
+// and forward.  Every check, the descriptor's included, comes before the first HIP call.
+
+// the checks the five operations share (what: the operation, for the message) and the dims of its parameter block
+template <class Params> static int sde_begin(Params &p, const SdeRoute &rt, const char *what, int B, int T, int S, int P) {
+    const int rc = route_check(rt, S, P, p.net);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(rt.kind != 3 || (S >= 1 && S <= 32), VSDE_E_BADARG, "linear-diagonal SDE needs state_dim 1..32 (got %d)", S);
+    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad %s dims B=%d T=%d", what, B, T);
+    p.B = B; p.T = T; p.S = S; p.P = P;
     return 0;
+}
+
+template <class Params> static void sde_time(Params &p, double time_step, const uint8_t *positive_mask_host) {
+    p.pos_mask = em_mask(positive_mask_host, p.S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
+}
+
+template <class Kern, class Params> static int sde_launch(Kern kern, dim3 grid, dim3 block, const Params &p, void *stream) {
+    hipLaunchKernelGGL(kern, grid, block, 0, (hipStream_t)stream, p);
+    VSDE_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// the simulators' geometry: a 64-thread workgroup of paths, or (kind 3) a thread per (path, dim)
+template <int KIND> static dim3 em_grid(int B, int S) {
+    return KIND == 3 ? dim3((unsigned)(((int64_t)B * S + 255) / 256)) : dim3((B + kEmPaths - 1) / kEmPaths);
+}
+template <int KIND> static dim3 em_block() { return KIND == 3 ? dim3(256) : dim3(kEmPaths); }
+
+static int em_fwd(const SdeRoute &rt, int B, int T, int S, int P, const float *x0, const float *theta, const float *noise,
+                  double time_step, const uint8_t *positive_mask_host, float *traj, void *stream) {
+    EmParams p = {};
+    const int rc = sde_begin(p, rt, "Euler-Maruyama", B, T, S, P);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(x0 && theta && noise && traj && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
+    p.x0 = x0; p.theta = theta; p.noise = noise; p.traj = traj;
+    sde_time(p, time_step, positive_mask_host);
+    return route_dispatch<0>(rt, S, p.net.R, [&](auto kind, auto ns, auto nr, auto kin) {
+        constexpr int KIND = decltype(kind)::value;
+        if constexpr (KIND == 3) return sde_launch(em_diag_fwd_kernel, em_grid<3>(B, S), em_block<3>(), p, stream);
+        else return sde_launch(em_fwd_kernel<KIND, decltype(ns)::value, decltype(nr)::value, decltype(kin)::value>, em_grid<KIND>(B, S),
+                               em_block<KIND>(), p, stream);
+    });
+}
+
+static int em_bwd(const SdeRoute &rt, int B, int T, int S, int P, const float *theta, const float *noise, const float *traj,
+                  const float *g_traj, double time_step, const uint8_t *positive_mask_host, float *g_x0, float *g_theta,
+                  void *stream) {
+    EmParams p = {};
+    const int rc = sde_begin(p, rt, "Euler-Maruyama", B, T, S, P);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(theta && noise && traj && g_traj && g_x0 && g_theta && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
+    p.theta = theta; p.noise = noise; p.traj_in = traj; p.g_traj = g_traj; p.g_x0 = g_x0; p.g_theta = g_theta;
+    sde_time(p, time_step, positive_mask_host);
+    return route_dispatch<0>(rt, S, p.net.R, [&](auto kind, auto ns, auto nr, auto kin) {
+        constexpr int KIND = decltype(kind)::value;
+        if constexpr (KIND == 3) return sde_launch(em_diag_bwd_kernel, em_grid<3>(B, S), em_block<3>(), p, stream);
+        else return sde_launch(em_bwd_kernel<KIND, decltype(ns)::value, decltype(nr)::value, decltype(kin)::value>, em_grid<KIND>(B, S),
+                               em_block<KIND>(), p, stream);
+    });
+}
+
+static int forecast(const SdeRoute &rt, int B, int T, int S, int P, int K, const float *x_start, const float *theta,
+                    const int *out_steps, const uint32_t *key, double time_step, const uint8_t *positive_mask_host, float *out,
+                    void *stream) {
+    FcParams p = {};
+    const int rc = sde_begin(p, rt, "forecast", B, T, S, P);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(K > 0, VSDE_E_BADARG, "bad forecast output count K=%d", K);
+    VSDE_CHECK_ARG(x_start && theta && out_steps && key && out && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
+    p.K = K; p.x0 = x_start; p.theta = theta; p.steps = out_steps; p.key = key; p.out = out;
+    sde_time(p, time_step, positive_mask_host);
+    return route_dispatch<0>(rt, S, p.net.R, [&](auto kind, auto ns, auto nr, auto kin) {
+        constexpr int KIND = decltype(kind)::value;
+        return sde_launch(forecast_kernel<KIND, decltype(ns)::value, decltype(nr)::value, decltype(kin)::value>, em_grid<KIND>(B, S),
+                          em_block<KIND>(), p, stream);
+    });
+}
+
+static int coefficients_fwd(const SdeRoute &rt, int B, int T, int S, int P, const float *x, const float *theta, float *drift,
+                            float *diffusion, void *stream) {
+    CoefParams p = {};
+    const int rc = sde_begin(p, rt, "coefficient", B, T, S, P);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(x && theta && drift && diffusion, VSDE_E_BADARG, "NULL argument");
+    p.x = x; p.theta = theta; p.drift = drift; p.diff = diffusion;
+    // a thread per (path, step), or (kind 3) per (path, step, dim)
+    return route_dispatch<0>(rt, S, p.net.R, [&](auto kind, auto ns, auto nr, auto kin) {
+        constexpr int KIND = decltype(kind)::value;
+        const dim3 grid((unsigned)(((int64_t)B * T * (KIND == 3 ? S : 1) + 255) / 256));
+        if constexpr (KIND == 3) return sde_launch(coef_diag_fwd_kernel, grid, dim3(256), p, stream);
+        else return sde_launch(coef_fwd_kernel<KIND, decltype(ns)::value, decltype(nr)::value, decltype(kin)::value>, grid, dim3(256), p,
+                               stream);
+    });
+}
+
+static int coefficients_bwd(const SdeRoute &rt, int B, int T, int S, int P, const float *x, const float *theta, const float *g_drift,
+                            const float *g_diffusion, float *g_x, float *g_theta, void *stream) {
+    CoefParams p = {};
+    const int rc = sde_begin(p, rt, "coefficient", B, T, S, P);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(x && theta && g_drift && g_diffusion && g_x && g_theta, VSDE_E_BADARG, "NULL argument");
+    p.x = x; p.theta = theta; p.g_drift = g_drift; p.g_diff = g_diffusion; p.g_x = g_x; p.g_theta = g_theta;
+    return route_dispatch<0>(rt, S, p.net.R, [&](auto kind, auto ns, auto nr, auto kin) {
+        constexpr int KIND = decltype(kind)::value;
+        if constexpr (KIND == 3) return sde_launch(coef_diag_bwd_kernel, dim3(B), dim3(256), p, stream);
+        else return sde_launch(coef_bwd_kernel<KIND, decltype(ns)::value, decltype(nr)::value, decltype(kin)::value>, dim3(B), dim3(256), p,
+                               stream);
+    });
 }
 
 }  // namespace vsde
 
 using namespace vsde;
 
+// Built-in kinds 1..3
 extern "C" int vsde_euler_maruyama_fwd(int kind, int B, int T, int S, int P, const float *x0, const float *theta,
                                        const float *noise, double time_step, const uint8_t *positive_mask_host, float *traj,
                                        void *stream) {
-    int rc = em_check(kind, B, T, S, P);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(x0 && theta && noise && traj && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
-    EmParams p = {};
-    p.B = B; p.T = T; p.S = S; p.P = P; p.x0 = x0; p.theta = theta; p.noise = noise; p.traj = traj;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = (B + kEmPaths - 1) / kEmPaths;
-    if (kind == 1) hipLaunchKernelGGL(em_fwd_kernel<1>, dim3(grid), dim3(kEmPaths), 0, s, p);
-    else if (kind == 2) hipLaunchKernelGGL(em_fwd_kernel<2>, dim3(grid), dim3(kEmPaths), 0, s, p);
-    else hipLaunchKernelGGL(em_diag_fwd_kernel, dim3((unsigned)(((int64_t)B * S + 255) / 256)), dim3(256), 0, s, p);
-    VSDE_CHECK_HIP(hipGetLastError());
-    return 0;
+    return em_fwd(SdeRoute{kind}, B, T, S, P, x0, theta, noise, time_step, positive_mask_host, traj, stream);
 }
 
 extern "C" int vsde_euler_maruyama_bwd(int kind, int B, int T, int S, int P, const float *theta, const float *noise,
                                        const float *traj, const float *g_traj, double time_step,
                                        const uint8_t *positive_mask_host, float *g_x0, float *g_theta, void *stream) {
-    int rc = em_check(kind, B, T, S, P);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(theta && noise && traj && g_traj && g_x0 && g_theta && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
-    EmParams p = {};
-    p.B = B; p.T = T; p.S = S; p.P = P; p.theta = theta; p.noise = noise; p.traj_in = traj; p.g_traj = g_traj;
-    p.g_x0 = g_x0; p.g_theta = g_theta;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = (B + kEmPaths - 1) / kEmPaths;
-    if (kind == 1) hipLaunchKernelGGL(em_bwd_kernel<1>, dim3(grid), dim3(kEmPaths), 0, s, p);
-    else if (kind == 2) hipLaunchKernelGGL(em_bwd_kernel<2>, dim3(grid), dim3(kEmPaths), 0, s, p);
-    else hipLaunchKernelGGL(em_diag_bwd_kernel, dim3((unsigned)(((int64_t)B * S + 255) / 256)), dim3(256), 0, s, p);
-    VSDE_CHECK_HIP(hipGetLastError());
-    return 0;
+    return em_bwd(SdeRoute{kind}, B, T, S, P, theta, noise, traj, g_traj, time_step, positive_mask_host, g_x0, g_theta, stream);
 }
 
 extern "C" int vsde_forecast(int kind, int B, int T, int S, int P, int K, const float *x_start, const float *theta,
                              const int *out_steps, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
                              float *out, void *stream) {
-    int rc = em_check(kind, B, T, S, P);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(K > 0, VSDE_E_BADARG, "bad forecast output count K=%d", K);
-    VSDE_CHECK_ARG(S <= 32, VSDE_E_BADARG, "forecast state_dim %d above 32", S);
-    VSDE_CHECK_ARG(x_start && theta && out_steps && key && out && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
-    FcParams p = {};
-    p.B = B; p.T = T; p.S = S; p.P = P; p.K = K; p.x0 = x_start; p.theta = theta; p.steps = out_steps; p.key = key; p.out = out;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    hipStream_t s = (hipStream_t)stream;
-    if (kind == 1) hipLaunchKernelGGL(forecast_kernel<1>, dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0, s, p);
-    else if (kind == 2) hipLaunchKernelGGL(forecast_kernel<2>, dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0, s, p);
-    else hipLaunchKernelGGL(forecast_kernel<3>, dim3((unsigned)(((int64_t)B * S + 255) / 256)), dim3(256), 0, s, p);
-    VSDE_CHECK_HIP(hipGetLastError());
-    return 0;
+    return forecast(SdeRoute{kind}, B, T, S, P, K, x_start, theta, out_steps, key, time_step, positive_mask_host, out, stream);
 }
 
 extern "C" int vsde_sde_coefficients_fwd(int kind, int B, int T, int S, int P, const float *x, const float *theta, float *drift,
                                          float *diffusion, void *stream) {
-    int rc = em_check(kind, B, T, S, P);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(x && theta && drift && diffusion, VSDE_E_BADARG, "NULL argument");
-    CoefParams p = {};
-    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = theta; p.drift = drift; p.diff = diffusion;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned grid = (unsigned)(((int64_t)B * T + 255) / 256);
-    if (kind == 1) hipLaunchKernelGGL(coef_fwd_kernel<1>, dim3(grid), dim3(256), 0, s, p);
-    else if (kind == 2) hipLaunchKernelGGL(coef_fwd_kernel<2>, dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(coef_diag_fwd_kernel, dim3((unsigned)(((int64_t)B * T * S + 255) / 256)), dim3(256), 0, s, p);
-    VSDE_CHECK_HIP(hipGetLastError());
-    return 0;
+    return coefficients_fwd(SdeRoute{kind}, B, T, S, P, x, theta, drift, diffusion, stream);
 }
 
 extern "C" int vsde_sde_coefficients_bwd(int kind, int B, int T, int S, int P, const float *x, const float *theta,
                                          const float *g_drift, const float *g_diffusion, float *g_x, float *g_theta, void *stream) {
-    int rc = em_check(kind, B, T, S, P);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(x && theta && g_drift && g_diffusion && g_x && g_theta, VSDE_E_BADARG, "NULL argument");
-    CoefParams p = {};
-    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = theta; p.g_drift = g_drift; p.g_diff = g_diffusion;
-    p.g_x = g_x; p.g_theta = g_theta;
-    hipStream_t s = (hipStream_t)stream;
-    if (kind == 1) hipLaunchKernelGGL(coef_bwd_kernel<1>, dim3(B), dim3(256), 0, s, p);
-    else if (kind == 2) hipLaunchKernelGGL(coef_bwd_kernel<2>, dim3(B), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(coef_diag_bwd_kernel, dim3(B), dim3(256), 0, s, p);
-    VSDE_CHECK_HIP(hipGetLastError());
-    return 0;
+    return coefficients_bwd(SdeRoute{kind}, B, T, S, P, x, theta, g_drift, g_diffusion, g_x, g_theta, stream);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Kind 4: reaction networks (include/vsde_hip.h: vsde_crn_network).  The descriptor is checked and copied into the kernel
-// arguments here, before any HIP call.
-
+// Kind 4: reaction networks (include/vsde_hip.h: vsde_crn_network), theta [B][R]
 extern "C" int vsde_crn_euler_maruyama_fwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *x0,
                                            const float *theta, const float *noise, double time_step,
                                            const uint8_t *positive_mask_host, float *traj, void *stream) {
-    EmParams p = {};
-    int rc = crn_net(net, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad Euler-Maruyama dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(x0 && theta && noise && traj && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.x0 = x0; p.theta = theta; p.noise = noise; p.traj = traj;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    return crn_dispatch(S, P, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((em_fwd_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0,
-                           (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return em_fwd(crn_route(net), B, T, S, P, x0, theta, noise, time_step, positive_mask_host, traj, stream);
 }
 
 extern "C" int vsde_crn_euler_maruyama_bwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *theta,
                                            const float *noise, const float *traj, const float *g_traj, double time_step,
                                            const uint8_t *positive_mask_host, float *g_x0, float *g_theta, void *stream) {
-    EmParams p = {};
-    int rc = crn_net(net, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad Euler-Maruyama dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(theta && noise && traj && g_traj && g_x0 && g_theta && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.theta = theta; p.noise = noise; p.traj_in = traj; p.g_traj = g_traj;
-    p.g_x0 = g_x0; p.g_theta = g_theta;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    return crn_dispatch(S, P, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((em_bwd_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0,
-                           (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return em_bwd(crn_route(net), B, T, S, P, theta, noise, traj, g_traj, time_step, positive_mask_host, g_x0, g_theta, stream);
 }
 
 extern "C" int vsde_crn_forecast(const vsde_crn_network *net, int B, int T, int S, int P, int K, const float *x_start,
                                  const float *theta, const int *out_steps, const uint32_t *key, double time_step,
                                  const uint8_t *positive_mask_host, float *out, void *stream) {
-    FcParams p = {};
-    int rc = crn_net(net, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad forecast dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(K > 0, VSDE_E_BADARG, "bad forecast output count K=%d", K);
-    VSDE_CHECK_ARG(x_start && theta && out_steps && key && out && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.K = K; p.x0 = x_start; p.theta = theta; p.steps = out_steps; p.key = key; p.out = out;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    return crn_dispatch(S, P, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((forecast_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3((B + kEmPaths - 1) / kEmPaths), dim3(kEmPaths), 0,
-                           (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return forecast(crn_route(net), B, T, S, P, K, x_start, theta, out_steps, key, time_step, positive_mask_host, out, stream);
 }
 
 extern "C" int vsde_crn_sde_coefficients_fwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *x,
                                              const float *theta, float *drift, float *diffusion, void *stream) {
-    CoefParams p = {};
-    int rc = crn_net(net, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad coefficient dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(x && theta && drift && diffusion, VSDE_E_BADARG, "NULL argument");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = theta; p.drift = drift; p.diff = diffusion;
-    return crn_dispatch(S, P, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((coef_fwd_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3((unsigned)(((int64_t)B * T + 255) / 256)), dim3(256), 0,
-                           (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return coefficients_fwd(crn_route(net), B, T, S, P, x, theta, drift, diffusion, stream);
 }
 
 extern "C" int vsde_crn_sde_coefficients_bwd(const vsde_crn_network *net, int B, int T, int S, int P, const float *x,
                                              const float *theta, const float *g_drift, const float *g_diffusion, float *g_x,
                                              float *g_theta, void *stream) {
-    CoefParams p = {};
-    int rc = crn_net(net, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad coefficient dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(x && theta && g_drift && g_diffusion && g_x && g_theta, VSDE_E_BADARG, "NULL argument");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = theta; p.g_drift = g_drift; p.g_diff = g_diffusion;
-    p.g_x = g_x; p.g_theta = g_theta;
-    return crn_dispatch(S, P, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((coef_bwd_kernel<4, decltype(ns)::value, decltype(nr)::value>), dim3(B), dim3(256), 0, (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return coefficients_bwd(crn_route(net), B, T, S, P, x, theta, g_drift, g_diffusion, g_x, g_theta, stream);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
 // Kind 4 with rate laws (include/vsde_hip.h: vsde_crn_kinetics): the KIN instantiations, theta = the effective constants
-// rates [B][2R].  Both descriptors are checked and copied into the kernel arguments here, before any HIP call.
-
-static int crn_kinetic_net(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int S, int P, CrnNet &n) {
-    const int rc = crn_net(net, S, P, n, true);
-    return rc ? rc : crn_kinetics(kin, S, n);
-}
-
+// rates [B][2R]
 extern "C" int vsde_crn_kinetic_euler_maruyama_fwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S,
                                                    int P, const float *x0, const float *rates, const float *noise,
                                                    double time_step, const uint8_t *positive_mask_host, float *traj,
                                                    void *stream) {
-    EmParams p = {};
-    int rc = crn_kinetic_net(net, kin, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad Euler-Maruyama dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(x0 && rates && noise && traj && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.x0 = x0; p.theta = rates; p.noise = noise; p.traj = traj;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((em_fwd_kernel<4, decltype(ns)::value, decltype(nr)::value, true>), dim3((B + kEmPaths - 1) / kEmPaths),
-                           dim3(kEmPaths), 0, (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return em_fwd(crn_route(net, kin), B, T, S, P, x0, rates, noise, time_step, positive_mask_host, traj, stream);
 }
 
 extern "C" int vsde_crn_kinetic_euler_maruyama_bwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S,
                                                    int P, const float *rates, const float *noise, const float *traj,
                                                    const float *g_traj, double time_step, const uint8_t *positive_mask_host,
                                                    float *g_x0, float *g_rates, void *stream) {
-    EmParams p = {};
-    int rc = crn_kinetic_net(net, kin, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad Euler-Maruyama dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(rates && noise && traj && g_traj && g_x0 && g_rates && time_step > 0, VSDE_E_BADARG,
-                   "NULL argument / bad time_step");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.theta = rates; p.noise = noise; p.traj_in = traj; p.g_traj = g_traj;
-    p.g_x0 = g_x0; p.g_theta = g_rates;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((em_bwd_kernel<4, decltype(ns)::value, decltype(nr)::value, true>), dim3((B + kEmPaths - 1) / kEmPaths),
-                           dim3(kEmPaths), 0, (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return em_bwd(crn_route(net, kin), B, T, S, P, rates, noise, traj, g_traj, time_step, positive_mask_host, g_x0, g_rates,
+                  stream);
 }
 
 extern "C" int vsde_crn_kinetic_forecast(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T, int S, int P,
                                          int K, const float *x_start, const float *rates, const int *out_steps,
                                          const uint32_t *key, double time_step, const uint8_t *positive_mask_host, float *out,
                                          void *stream) {
-    FcParams p = {};
-    int rc = crn_kinetic_net(net, kin, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad forecast dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(K > 0, VSDE_E_BADARG, "bad forecast output count K=%d", K);
-    VSDE_CHECK_ARG(x_start && rates && out_steps && key && out && time_step > 0, VSDE_E_BADARG, "NULL argument / bad time_step");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.K = K; p.x0 = x_start; p.theta = rates; p.steps = out_steps; p.key = key; p.out = out;
-    p.pos_mask = em_mask(positive_mask_host, S); p.dt = (float)time_step; p.sqdt = (float)sqrt(time_step);
-    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((forecast_kernel<4, decltype(ns)::value, decltype(nr)::value, true>), dim3((B + kEmPaths - 1) / kEmPaths),
-                           dim3(kEmPaths), 0, (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return forecast(crn_route(net, kin), B, T, S, P, K, x_start, rates, out_steps, key, time_step, positive_mask_host, out,
+                    stream);
 }
 
 extern "C" int vsde_crn_kinetic_sde_coefficients_fwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T,
                                                      int S, int P, const float *x, const float *rates, float *drift,
                                                      float *diffusion, void *stream) {
-    CoefParams p = {};
-    int rc = crn_kinetic_net(net, kin, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad coefficient dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(x && rates && drift && diffusion, VSDE_E_BADARG, "NULL argument");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = rates; p.drift = drift; p.diff = diffusion;
-    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((coef_fwd_kernel<4, decltype(ns)::value, decltype(nr)::value, true>),
-                           dim3((unsigned)(((int64_t)B * T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return coefficients_fwd(crn_route(net, kin), B, T, S, P, x, rates, drift, diffusion, stream);
 }
 
 extern "C" int vsde_crn_kinetic_sde_coefficients_bwd(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int T,
                                                      int S, int P, const float *x, const float *rates, const float *g_drift,
                                                      const float *g_diffusion, float *g_x, float *g_rates, void *stream) {
-    CoefParams p = {};
-    int rc = crn_kinetic_net(net, kin, S, P, p.net);
-    if (rc) return rc;
-    VSDE_CHECK_ARG(B > 0 && T > 0, VSDE_E_BADARG, "bad coefficient dims B=%d T=%d", B, T);
-    VSDE_CHECK_ARG(x && rates && g_drift && g_diffusion && g_x && g_rates, VSDE_E_BADARG, "NULL argument");
-    p.B = B; p.T = T; p.S = S; p.P = P; p.x = x; p.theta = rates; p.g_drift = g_drift; p.g_diff = g_diffusion;
-    p.g_x = g_x; p.g_theta = g_rates;
-    return crn_dispatch(S, p.net.R, [&](auto ns, auto nr) {
-        hipLaunchKernelGGL((coef_bwd_kernel<4, decltype(ns)::value, decltype(nr)::value, true>), dim3(B), dim3(256), 0,
-                           (hipStream_t)stream, p);
-        VSDE_CHECK_HIP(hipGetLastError());
-        return 0;
-    });
+    return coefficients_bwd(crn_route(net, kin), B, T, S, P, x, rates, g_drift, g_diffusion, g_x, g_rates, stream);
 }

@@ -47,6 +47,12 @@ static inline int count_lik(CountLik &c, int lik_kind, double scale, double disp
     return 0;
 }
 
+// the count arguments of a vsde_*count_* entry point (NULL: the Gaussian form); checked after the shared checks
+struct CountArgs { int lik_kind; double scale, dispersion; const float *row_const; };
+static inline int count_fill(CountLik &c, const CountArgs *ca, int K) {
+    return ca ? count_lik(c, ca->lik_kind, ca->scale, ca->dispersion, ca->row_const, K) : 0;
+}
+
 __device__ __forceinline__ float log_ratio(float a, float b) {
     const float d = a - b;
     return fabsf(d) < 0.5f * b ? log1pf(d / b) : logf(a / b);
@@ -397,24 +403,76 @@ template <int NR> __device__ __forceinline__ void crn_store_rates(float *g, cons
         if (j < R) { o[j] = gth[j]; o[R + j] = gth[NR + j]; }
 }
 
-// host: f(std::integral_constant<int, S>, std::integral_constant<int, NR>) for the run-time S in 1..kCrnMaxS and the reaction
-// bound NR of R
-template <int S, class F> static int crn_dispatch_r(int R, F &&f) {
-    if (R <= 4) return f(std::integral_constant<int, S>{}, std::integral_constant<int, 4>{});
-    if (R <= 8) return f(std::integral_constant<int, S>{}, std::integral_constant<int, 8>{});
-    return f(std::integral_constant<int, S>{}, std::integral_constant<int, kCrnMaxR>{});
+// ---------------------------------------------------------------------------------------------------------------------
+// Host: the model route of an entry point and its compile-time dispatch, shared by the simulator (vsde_sde.hip), the log-weight
+// (vsde_elbo.hip) and the particle-filter (vsde_filter.hip) entry points.  A route is a built-in kind 1..3 the caller names, or
+// kind 4: a reaction network (vsde_crn_*), with rate laws for the vsde_crn_kinetic_* entry points (theta is then the effective
+// constants [2R]).  `descriptors` counts what the entry point takes, so a NULL pointer is an error and not another route.
+struct SdeRoute {
+    int kind;
+    int descriptors = 0;   // 0: built-in kind; 1: network; 2: network and rate laws
+    const vsde_crn_network *net = nullptr;
+    const vsde_crn_kinetics *kin = nullptr;
+};
+static inline SdeRoute crn_route(const vsde_crn_network *net) { return {4, 1, net, nullptr}; }
+static inline SdeRoute crn_route(const vsde_crn_network *net, const vsde_crn_kinetics *kin) { return {4, 2, net, kin}; }
+
+// the built-in kinds' relations between S and P
+static inline int kind_check(int kind, int S, int P) {
+    VSDE_CHECK_ARG(kind >= 1 && kind <= 3, VSDE_E_BADARG, "unknown built-in SDE kind %d", kind);
+    VSDE_CHECK_ARG(kind != 1 || (S == 1 && P == 3), VSDE_E_BADARG, "Ornstein-Uhlenbeck needs state_dim 1, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 2 || (S == 2 && P == 3), VSDE_E_BADARG, "Lotka-Volterra needs state_dim 2, sde_param_dim 3");
+    VSDE_CHECK_ARG(kind != 3 || P == 2 * S, VSDE_E_BADARG, "linear-diagonal SDE needs sde_param_dim = 2 state_dim");
+    return 0;
 }
-template <class F> static int crn_dispatch(int S, int R, F &&f) {
-    switch (S) {
-        case 1: return crn_dispatch_r<1>(R, f);
-        case 2: return crn_dispatch_r<2>(R, f);
-        case 3: return crn_dispatch_r<3>(R, f);
-        case 4: return crn_dispatch_r<4>(R, f);
-        case 5: return crn_dispatch_r<5>(R, f);
-        case 6: return crn_dispatch_r<6>(R, f);
-        case 7: return crn_dispatch_r<7>(R, f);
-        case 8: return crn_dispatch_r<8>(R, f);
-        default: set_error("reaction network: %d species (1..%d supported)", S, kCrnMaxS); return VSDE_E_BADARG;
+
+// the descriptors of a kind-4 route against the call's S / P, converted into n
+static inline int crn_route_net(const SdeRoute &rt, int S, int P, CrnNet &n) {
+    const int rc = crn_net(rt.net, S, P, n, rt.descriptors == 2);
+    return rc || rt.descriptors < 2 ? rc : crn_kinetics(rt.kin, S, n);
+}
+
+// the route's own argument checks
+static inline int route_check(const SdeRoute &rt, int S, int P, CrnNet &n) {
+    return rt.descriptors ? crn_route_net(rt, S, P, n) : kind_check(rt.kind, S, P);
+}
+
+template <int V> using IntC = std::integral_constant<int, V>;
+
+// f(IntC<n>) for the run-time n in 1..MAX (the callers' argument checks keep n in range)
+template <int MAX, int N = 1, class F> static int dispatch_dim(int n, F &&f) {
+    if (n == N) return f(IntC<N>{});
+    if constexpr (N < MAX) {
+        return dispatch_dim<MAX, N + 1>(n, f);
+    } else {
+        set_error("state_dim %d not supported (1..%d)", n, MAX);
+        return VSDE_E_STATE;
+    }
+}
+
+// f(IntC<S>, IntC<NR>) for the run-time S in 1..MAX_S and the reaction bound NR of R
+template <int MAX_S = kCrnMaxS, class F> static int crn_dispatch(int S, int R, F &&f) {
+    return dispatch_dim<MAX_S>(S, [&](auto ns) {
+        if (R <= 4) return f(ns, IntC<4>{});
+        if (R <= 8) return f(ns, IntC<8>{});
+        return f(ns, IntC<kCrnMaxR>{});
+    });
+}
+
+// f(IntC<KIND>, IntC<NS>, IntC<NR>, std::bool_constant<KIN>): the template arguments of the route's kernels (R: the network's
+// reaction count).  Kind 3 is dispatched on S in 1..DIAG_MAX_S, or, with DIAG_MAX_S = 0 (kernels that read S at run time), called
+// once with EmDims<3>; kind 4 on S in 1..CRN_MAX_S.
+template <int DIAG_MAX_S, int CRN_MAX_S = kCrnMaxS, class F> static int route_dispatch(const SdeRoute &rt, int S, int R, F &&f) {
+    constexpr std::false_type no{};
+    switch (rt.kind) {
+        case 1: return f(IntC<1>{}, IntC<EmDims<1>::S>{}, IntC<EmDims<1>::P>{}, no);
+        case 2: return f(IntC<2>{}, IntC<EmDims<2>::S>{}, IntC<EmDims<2>::P>{}, no);
+        case 3:
+            if constexpr (DIAG_MAX_S == 0) return f(IntC<3>{}, IntC<EmDims<3>::S>{}, IntC<EmDims<3>::P>{}, no);
+            else return dispatch_dim<DIAG_MAX_S>(S, [&](auto ns) { return f(IntC<3>{}, ns, IntC<EmDims<3>::P>{}, no); });
+        default:
+            if (rt.descriptors == 2) return crn_dispatch<CRN_MAX_S>(S, R, [&](auto ns, auto nr) { return f(IntC<4>{}, ns, nr, std::true_type{}); });
+            return crn_dispatch<CRN_MAX_S>(S, R, [&](auto ns, auto nr) { return f(IntC<4>{}, ns, nr, no); });
     }
 }
 
