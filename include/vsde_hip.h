@@ -736,6 +736,31 @@ int vsde_crn_kinetic_guided_filter_replay(const vsde_crn_network *net, const vsd
                                           double time_step, const uint8_t *positive_mask_host, const float *particles,
                                           const int *ancestors, const int *last_slot, float *paths, int *lineage, void *stream);
 
+/* Metropolis step of particle marginal Metropolis-Hastings (viforsdes_amd/inference/particle_mcmc.py is the specification): C
+ * independent chains over u [P] (theta with a log taken on the positive dims), a thread per chain, R filter estimates per chain.
+ * One launch CLOSES iteration `iteration - 1` and OPENS iteration `iteration`; the caller runs the particle filter on
+ * theta_prop[C*R][P] with filter_key between two launches and hands its log_likelihood [C][R] to the next one as loglik_prop.
+ *   Close (skipped when loglik_prop is NULL), it = iteration - 1: ll' = log mean_r exp(loglik_prop[c][r]) (NaN if any is NaN, -inf
+ * if all are -inf); target' = prop_log_prior[c] + ll'; log_u = log(((w0 >> 8) + 0.5) 2^-24) with w0 the first word of
+ * philox4x32_10({it, 0, c, 4}, key); accepted iff target' is not NaN and (it == 0 or (target' != -inf and log_u < target' -
+ * cur_log_target[c])).  On acceptance cur_u[c] = prop_u[c], cur_log_target[c] = target', cur_loglik[c] = ll', n_accept[c] += 1.
+ * Then, where not NULL, sample_row[c][P] = theta of cur_u[c] (exp on the positive dims), loglik_row[c], target_row[c] = the
+ * carried values.
+ *   Open: for iteration > 0, u'_i = cur_u[c][i] + step_size sum_{j <= i} scale_tril[i][j] z_j with z_j the Box-Muller normal j & 3
+ * of philox4x32_10({iteration, j >> 2, c, 3}, key) (the rule of vsde_forecast: word pairs (w0, w1), (w2, w3)), written to
+ * prop_u[c]; iteration 0 proposes prop_u[c] as the caller gave it.  theta' = u' with exp on the positive dims, R copies of it to
+ * theta_prop[c R + r]; prop_log_prior[c] = the prior's log density of theta' (prior_type 0: Normal, 1: LogNormal, iid over P, as
+ * vsde_elbo_tail_fwd) + sum over the positive dims of u'_i; filter_key = the first two words of philox4x32_10({iteration, 0, 0,
+ * 5}, key).  Counter words 3, 4, 5 in the fourth slot: 0, 1, 2 are the path normals, the resampling uniforms and the smoother.
+ *   scale_tril [P][P] is read on the HOST (it travels in the kernel's argument block) and so is theta_positive_mask_host; every
+ * other pointer is device memory.  VSDE_E_BADARG before any HIP call: C, R < 1, iteration < 0, P outside 1..16, C R P >= 2^31, a
+ * NULL pointer other than loglik_prop / sample_row / loglik_row / target_row, loglik_prop given at iteration 0, step_size or
+ * prior_std not positive, prior_type not 0 / 1, scale_tril not finite, not lower triangular or with a diagonal entry <= 0. */
+int vsde_pmmh_step(int C, int P, int R, int iteration, const float *scale_tril, double step_size, int prior_type, double prior_mean,
+                   double prior_std, const uint8_t *theta_positive_mask_host, const uint32_t *key, const float *loglik_prop,
+                   float *cur_u, float *cur_log_target, float *cur_loglik, float *prop_u, float *prop_log_prior, float *theta_prop,
+                   uint32_t *filter_key, float *sample_row, float *loglik_row, float *target_row, int *n_accept, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

@@ -18,6 +18,7 @@ from .core.reaction_network import Hill, MichaelisMenten, ReactionNetworkSDE
 from .core.sde import SDE, FunctionalSDE, make_sde
 from .infer import InferenceConfig, infer
 from .inference.particle_filter import ParticleFilterResult, particle_filter
+from .inference.particle_mcmc import ParticleMCMCResult, particle_mcmc
 from .inference.particle_smoother import SmoothedPaths, particle_smoother
 from .posterior.variational_posterior import (EvidenceEstimate, ParameterReweighting, PathReweighting, PosteriorPredictive,
                                               VariationalPosterior)
@@ -27,5 +28,5 @@ __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "Trainin
            "ObservationLikelihood", "Observations", "Prior", "PriorType", "SDE",
            "FunctionalSDE", "Hill", "MichaelisMenten", "ReactionNetworkSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior",
            "EvidenceEstimate", "PosteriorPredictive", "ParameterReweighting", "ParticleFilterResult", "particle_filter",
-           "PathReweighting", "SmoothedPaths", "particle_smoother"]
+           "PathReweighting", "SmoothedPaths", "particle_smoother", "ParticleMCMCResult", "particle_mcmc"]
 __version__ = "0.1.0"

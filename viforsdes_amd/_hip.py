@@ -71,7 +71,7 @@ EXPORTS = (
     "vsde_crn_kinetic_log_weights", "vsde_particle_filter", "vsde_crn_particle_filter", "vsde_crn_kinetic_particle_filter",
     "vsde_guided_particle_filter", "vsde_crn_guided_particle_filter", "vsde_crn_kinetic_guided_particle_filter",
     "vsde_filter_replay", "vsde_crn_filter_replay", "vsde_crn_kinetic_filter_replay",
-    "vsde_guided_filter_replay", "vsde_crn_guided_filter_replay", "vsde_crn_kinetic_guided_filter_replay",
+    "vsde_guided_filter_replay", "vsde_crn_guided_filter_replay", "vsde_crn_kinetic_guided_filter_replay", "vsde_pmmh_step",
     "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
@@ -580,6 +580,44 @@ def guided_filter_replay(kind: str, x0, theta, obs_rows, obs_values, obs_matrix,
     bridge steps need the observations, obs_matrix and variance of that call as well."""
     return _filter_replay("guided_filter_replay", kind, x0, theta, obs_rows, (obs_values, obs_matrix, variance), key, time_step,
                           particles, ancestors, last_slot, n_steps, positive_dims, network)
+
+
+PMMH_MAX_PARAMS = 16
+
+
+def pmmh_step(iteration: int, scale_tril, step_size: float, prior_type: int, prior_mean: float, prior_std: float,
+              theta_positive_dims, key, loglik_prop, cur_u, cur_log_target, cur_loglik, prop_u, prop_log_prior, theta_prop,
+              filter_key, n_accept, sample_row=None, loglik_row=None, target_row=None) -> None:
+    """One Metropolis step of particle MCMC, in place (include/vsde_hip.h: vsde_pmmh_step): closes iteration ``iteration - 1`` with
+    the filter estimates ``loglik_prop [C, R]`` (None: nothing to close) and opens iteration ``iteration``.  ``scale_tril``: a
+    contiguous fp32 CPU tensor [P, P]; ``key`` / ``filter_key``: 2 int32 words on the device; chain state ``cur_u [C, P]``,
+    ``cur_log_target [C]``, ``cur_loglik [C]``, the pending proposal ``prop_u [C, P]``, ``prop_log_prior [C]``, the filter's input
+    ``theta_prop [C R, P]`` and ``n_accept [C]`` (int32) are contiguous device tensors written in place; ``sample_row [C, P]``,
+    ``loglik_row [C]``, ``target_row [C]``: where the closed state is kept, or None.  C, P are prop_u's shape, R = rows of
+    theta_prop / C."""
+    lib = load()
+    dev = _require_hip(key, prop_u, theta_prop)
+    if not (isinstance(scale_tril, torch.Tensor) and scale_tril.device.type == "cpu" and scale_tril.dtype == torch.float32
+            and scale_tril.is_contiguous() and prop_u.ndim == 2 and tuple(scale_tril.shape) == (prop_u.shape[1],) * 2):
+        raise ValueError("pmmh_step: prop_u [C, P] and scale_tril, a contiguous fp32 CPU tensor [P, P], expected")
+    for t, dt in ((key, None), (filter_key, None), (n_accept, torch.int32), (loglik_prop, torch.float32), (cur_u, torch.float32),
+                  (cur_log_target, torch.float32), (cur_loglik, torch.float32), (prop_u, torch.float32),
+                  (prop_log_prior, torch.float32), (theta_prop, torch.float32), (sample_row, torch.float32),
+                  (loglik_row, torch.float32), (target_row, torch.float32)):
+        if t is not None and (t.device != dev or not t.is_contiguous() or (t.dtype != dt if dt else t.dtype not in (torch.int32, torch.uint32))):
+            raise ValueError("pmmh_step: contiguous fp32 tensors (int32: key, filter_key, n_accept) on one device expected")
+    C, P = prop_u.shape
+    R = theta_prop.shape[0] // C if C else 1
+    sizes = ((key, 2), (filter_key, 2), (n_accept, C), (loglik_prop, C * R), (cur_u, C * P), (cur_log_target, C), (cur_loglik, C),
+             (prop_log_prior, C), (theta_prop, C * R * P), (sample_row, C * P), (loglik_row, C), (target_row, C))
+    if any(t is not None and t.numel() != n for t, n in sizes):
+        raise ValueError(f"pmmh_step: a tensor does not have the size that C = {C}, P = {P}, R = {R} give it")
+    with torch.cuda.device(dev):
+        _call(lib.vsde_pmmh_step, ctypes.c_int(C), ctypes.c_int(P), ctypes.c_int(R), ctypes.c_int(int(iteration)),
+              ctypes.c_void_p(scale_tril.data_ptr()), ctypes.c_double(step_size), ctypes.c_int(int(prior_type)),
+              ctypes.c_double(prior_mean), ctypes.c_double(prior_std), _mask_bytes(theta_positive_dims, P), _ptr(key),
+              _ptr(loglik_prop), _ptr(cur_u), _ptr(cur_log_target), _ptr(cur_loglik), _ptr(prop_u), _ptr(prop_log_prior),
+              _ptr(theta_prop), _ptr(filter_key), _ptr(sample_row), _ptr(loglik_row), _ptr(target_row), _ptr(n_accept), _stream(dev))
 
 
 def _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean, post_log_std, theta_positive_dims):

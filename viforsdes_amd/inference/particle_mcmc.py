@@ -1,0 +1,475 @@
+"""Particle MCMC: particle marginal Metropolis-Hastings (PMMH; Andrieu, Doucet and Holenstein 2010) for the exact posterior of the
+SDE parameters ``p(theta | y)`` of the Euler-Maruyama-discretised model, whatever its shape.  ``particle_filter`` of this package
+returns an unbiased estimate ``p^(y | theta)`` for a batch of theta in one launch; a Metropolis-Hastings chain that uses the
+estimate in place of the likelihood, and CARRIES the estimate of its current point instead of refreshing it, still has the exact
+posterior as its invariant distribution (the pseudo-marginal argument).  Many independent chains run in lock-step, so one filter
+launch per iteration serves all of them, and because the chains are independent the Monte-Carlo error of a posterior mean is simply
+the spread of the chain means (``ParticleMCMCResult.mean_standard_error``).  Started from draws of a variational q(theta)
+(``VariationalPosterior.refine_parameters``) the chains repair what a mean-field q cannot represent.
+
+The rule.  ``u`` is theta with a log taken on ``theta_positive_dims``; the random walk is symmetric in ``u``.  The log-target of a
+chain is ``log p(theta) + sum_{positive dims} u_i + ll`` with ``ll = log mean_r exp(log p^_r)`` over the ``R = filters_per_chain``
+independent filters of the same theta (a mean of unbiased estimates is unbiased: the way past the kernel's 1024 particles per
+filter).  Iteration ``i = 0, 1, ...`` of chain ``c`` (``C`` chains, ``P`` parameters, ``key``: the call's two words):
+
+1. adaptation (warm-up only, below), then the proposal ``u' = u + step_size L z``: ``L = proposal_scale_tril`` (lower triangular
+   ``[P, P]``, shared by the chains), ``z_j`` the Box-Muller normal ``j & 3`` of ``philox4x32_10({i, j >> 2, c, 3}, key)`` by the rule
+   of ``particle_filter.stream_normals`` (word pairs (w0, w1), (w2, w3), fp32 uniforms ``((w >> 8) + 0.5) 2^-24``).  Iteration 0
+   proposes ``initial_theta`` itself;
+2. ``theta'`` from ``u'``, and ONE ``particle_filter`` call on the ``[C R, P]`` rows (filter ``m = c R + r`` has ``theta'_c``; every
+   other argument is the caller's) with the key of iteration i: the first two words of ``philox4x32_10({i, 0, 0, 5}, key)``.  The
+   current point's estimate is never refreshed: that is what keeps the chain exact;
+3. acceptance: ``log alpha = target' - target``; ``log_u = log(((w0 >> 8) + 0.5) 2^-24)`` with ``w0`` the first word of
+   ``philox4x32_10({i, 0, c, 4}, key)``.  A proposal whose target is NaN or -inf is rejected; otherwise it is accepted iff
+   ``log_u < log alpha`` (a current target of -inf gives ``log alpha = +inf``).  Iteration 0 is accepted unless its target is NaN
+   (a chain whose start is refused has target -inf and takes the first proposal with a finite one).  On acceptance ``u``,
+   ``target`` and ``ll`` become the proposal's.
+
+Counter words 3, 4 and 5 in the fourth slot: 0, 1 and 2 are the path normals, the resampling uniforms and the smoother's final
+draw.  The step uses the call's key, the filters the per-iteration keys; the same key gives the same chains.
+
+Warm-up is the first ``warmup`` iterations, is never returned, and is the only time anything adapts, so the kept chain is a plain
+Metropolis-Hastings chain.  Before the proposal of iteration i:
+
+* if ``0 < i <= warmup`` and ``i % adapt_interval == 0``: ``a`` = the pooled acceptance rate of iterations ``[i - adapt_interval,
+  i)`` (the only host read in the loop) and ``step_size *= exp(a - target_accept)``;
+* once, at ``i = warmup // 2``, with ``adapt=True``, ``C > P`` and ``warmup // 4 < warmup // 2``: ``L`` becomes the lower Cholesky
+  factor of the sample covariance of all chains' ``u`` over iterations ``[warmup // 4, warmup // 2)`` plus ``1e-8 I`` (kept as it
+  was if that matrix is not positive definite) and ``step_size`` is reset to ``2.38 / sqrt(P)``.
+
+Defaults: ``L = diag(std over chains of the initial u)`` floored at 1e-3 (the identity for C = 1), ``step_size = 2.38 / sqrt(P)``,
+and ``target_accept = 0.15`` rather than the 0.234 of a random walk with an exact likelihood: the noise of ``log p^`` makes every
+chain reject more at any step size and moves the optimum down (Sherlock, Thiery, Roberts and Rosenthal 2015: about 7 % at the
+optimal noise level in high dimension, 15..25 % in the few dimensions of this package's models).  After warm-up every ``thin``-th
+state is kept and nothing is read back from the device.
+
+The torch code below is the specification; it takes any SDE, any likelihood and any prior object with ``log_prob``, runs on CPU or
+GPU and follows the dtype of ``initial_theta``.  Where ``particle_filter`` takes its kernel route, ``initial_theta`` is CUDA fp32,
+``P <= 16`` and ``prior`` is the package's ``Prior``, everything but the filter runs as ONE kernel per iteration
+(csrc/vsde_mcmc.hip, a thread per chain: it closes iteration i - 1 and opens iteration i), and an iteration is that launch, the
+rate-law map of a kinetic network, and the filter launch with the device key the step kernel wrote.  ``HIP_MCMC = False`` forces the
+torch step (around whatever route the filter takes) for A/B."""
+from __future__ import annotations
+
+import math
+from collections.abc import Sequence
+from dataclasses import dataclass
+from typing import Any, Optional
+
+import torch
+from torch import Tensor
+
+from ..core.observations import COUNT_LIKELIHOODS, GaussianObservationLikelihood, ObservationLikelihood, Observations
+from ..core.priors import Prior, PriorType
+from ..core.sde import SDE, kernel_theta
+from . import particle_filter as _pf
+
+HIP_MCMC = True   # set False to force the torch step (A/B tests); the filter keeps its own switch
+DEFAULT_TARGET_ACCEPT = 0.15
+COVARIANCE_JITTER = 1e-8
+DEFAULT_SCALE_FLOOR = 1e-3
+_ITERATION_HOOK = None   # measurement aid (tools/particle_mcmc_bench.py): called with i at the top of every iteration of either loop
+
+
+@dataclass(frozen=True)
+class ParticleMCMCResult:
+    """Draws of the exact parameter posterior of the discretised model by particle MCMC (``particle_mcmc``,
+    ``VariationalPosterior.refine_parameters``): ``C`` independent chains, ``n_keep`` kept states each.
+
+    * ``samples [n_keep, C, P]``: theta (constrained); ``log_likelihood [n_keep, C]``: the filter estimate ``ll`` each state
+      carried (NOT a fresh estimate); ``log_target [n_keep, C]``: log prior + log Jacobian + ``ll``;
+    * ``acceptance_rate [C]``: accepted share of the iterations after warm-up;
+    * ``mean``, ``std`` ``[P]`` and ``quantiles`` of theta over all kept draws of all chains;
+    * ``mean_standard_error [P]``: the std over chains of the per-chain means divided by sqrt(C) -- the chains are independent, so
+      this is the Monte-Carlo error of ``mean`` with no autocorrelation estimate in it (NaN for C = 1);
+    * ``r_hat [P]``, ``effective_sample_size [P]``: split-R^ and the multi-chain ESS with Geyer's initial-positive-sequence
+      truncation (Gelman et al., BDA3, sections 11.4-11.5), computed in float64 on ``u`` (theta with a log on the positive dims);
+      NaN when fewer than 4 states were kept;
+    * ``step_size``, ``proposal_scale_tril [P, P]``: the final values (what the kept chain ran with);
+    * ``n_filters_dead``: proposals (over the whole run, warm-up included) whose every filter returned -inf -- many of them
+      means the filter, not the chain, is the problem: more particles, or ``proposal="bridge"``;
+    * ``variational_mean`` / ``variational_std [P]``: plain moments of the q draws the chains started from
+      (``refine_parameters`` only, else None)."""
+    samples: Tensor
+    log_likelihood: Tensor
+    log_target: Tensor
+    acceptance_rate: Tensor
+    mean: Tensor
+    std: Tensor
+    quantiles: Any
+    mean_standard_error: Tensor
+    r_hat: Tensor
+    effective_sample_size: Tensor
+    step_size: float
+    proposal_scale_tril: Tensor
+    n_filters_dead: int
+    variational_mean: Optional[Tensor] = None
+    variational_std: Optional[Tensor] = None
+
+
+def _words(key: Tensor, c0, c1, c2, c3) -> list[Tensor]:
+    k0, k1 = _pf._key_words(key)
+    as_t = lambda v: v if isinstance(v, Tensor) else torch.full((1,), int(v), device=key.device, dtype=torch.int64)
+    return _pf.philox4x32_10(as_t(c0), as_t(c1), as_t(c2), as_t(c3), k0, k1)
+
+
+def proposal_normals(n_chains: int, n_params: int, iteration: int, key: Tensor) -> Tensor:
+    """The normals ``z [C, P]`` (float64) of iteration ``iteration``: u in fp32, log / sqrt / cos / sin in float64."""
+    dev = key.device
+    c = torch.arange(n_chains, device=dev, dtype=torch.int64)[:, None]
+    blk = torch.arange((n_params + 3) // 4, device=dev, dtype=torch.int64)[None, :]
+    w = _words(key, iteration, blk, c, 3)
+    out = []
+    for wa, wb in ((w[0], w[1]), (w[2], w[3])):
+        r = torch.sqrt(-2.0 * torch.log(_pf._uniform(wa).double()))
+        ang = 2.0 * math.pi * _pf._uniform(wb).double()
+        out += [r * torch.cos(ang), r * torch.sin(ang)]
+    return torch.stack(out, dim=-1).reshape(n_chains, -1)[:, :n_params]
+
+
+def acceptance_log_uniforms(n_chains: int, iteration: int, key: Tensor) -> Tensor:
+    """``log_u [C]`` (float64) of iteration ``iteration``."""
+    c = torch.arange(n_chains, device=key.device, dtype=torch.int64)
+    return torch.log(_pf._uniform(_words(key, iteration, 0, c, 4)[0]).double())
+
+
+def filter_key(iteration: int, key: Tensor) -> Tensor:
+    """The filter key of iteration ``iteration``: two int32 words."""
+    w = _words(key, iteration, 0, 0, 5)
+    k = torch.cat([w[0].reshape(1), w[1].reshape(1)])
+    return torch.where(k >= 2 ** 31, k - 2 ** 32, k).to(torch.int32)
+
+
+def log_mean_exp(loglik: Tensor) -> Tensor:
+    """``log mean_r exp(loglik[c, r])``: NaN if a row holds a NaN, -inf if all of it is -inf."""
+    mx = loglik.max(dim=1, keepdim=True).values          # NaN if any entry is
+    safe = torch.where(torch.isneginf(mx), torch.zeros_like(mx), mx)
+    return (safe + torch.log(torch.exp(loglik - safe).sum(dim=1, keepdim=True)) - math.log(loglik.shape[1]))[:, 0]
+
+
+def constrain(u: Tensor, positive_mask: Tensor) -> Tensor:
+    return torch.where(positive_mask, u.exp(), u)
+
+
+def unconstrain(theta: Tensor, positive_mask: Tensor) -> Tensor:
+    return torch.where(positive_mask, torch.where(positive_mask, theta, torch.ones_like(theta)).log(), theta)
+
+
+def _log_prior_jacobian(prior, theta: Tensor, u: Tensor, positive_mask: Tensor) -> Tensor:
+    lp = prior.log_prob(theta)
+    if lp.ndim > 1:
+        lp = lp.sum(dim=-1)
+    return lp + torch.where(positive_mask, u, torch.zeros_like(u)).sum(dim=-1)
+
+
+def _accept(iteration: int, log_u: Tensor, prop_target: Tensor, cur_target: Tensor) -> Tensor:
+    ok = ~torch.isnan(prop_target)
+    if iteration == 0:
+        return ok
+    return ok & ~torch.isneginf(prop_target) & (log_u.to(prop_target.dtype) < prop_target - cur_target)
+
+
+def _close(iteration: int, key: Tensor, loglik: Tensor, prop_u: Tensor, prop_log_prior: Tensor, cur_u: Tensor, cur_target: Tensor,
+           cur_loglik: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The end of iteration ``iteration`` on the torch route: (cur_u, cur_target, cur_loglik, accepted) from the filter estimates
+    ``loglik [C, R]`` of the pending proposal."""
+    ll = log_mean_exp(loglik)
+    target = prop_log_prior + ll
+    acc = _accept(iteration, acceptance_log_uniforms(cur_u.shape[0], iteration, key), target, cur_target)
+    return (torch.where(acc[:, None], prop_u, cur_u), torch.where(acc, target, cur_target), torch.where(acc, ll, cur_loglik), acc)
+
+
+def adapted_scale_tril(u_history: Tensor, current: Tensor) -> Tensor:
+    """Lower Cholesky factor of the sample covariance of ``u_history [n, P]`` plus ``1e-8 I`` (float64 arithmetic), or ``current``
+    when that matrix is not finite and positive definite."""
+    P = u_history.shape[1]
+    x = u_history.double().cpu()                                         # a [P, P] factorisation, once per run: on the host
+    cov = torch.cov(x.T).reshape(P, P) + COVARIANCE_JITTER * torch.eye(P, dtype=torch.float64)
+    if not bool(torch.isfinite(cov).all()):
+        return current
+    factor, info = torch.linalg.cholesky_ex(cov)
+    if int(info) != 0 or not bool(torch.isfinite(factor).all()):
+        return current
+    return torch.tril(factor).to(device=current.device, dtype=current.dtype)
+
+
+def _validate(sde, observations, observation_likelihood, initial_theta, time_step, n_iterations, warmup, n_particles,
+              filters_per_chain, thin, theta_positive_dims, initial_state, proposal, proposal_scale_tril, step_size, target_accept,
+              adapt_interval):
+    if proposal not in _pf.PROPOSALS:
+        raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
+    if proposal == "bridge" and not isinstance(observation_likelihood, GaussianObservationLikelihood):
+        raise ValueError("proposal='bridge' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
+                         f"variance (got {type(observation_likelihood).__name__})")
+    if thin < 1 or adapt_interval < 1 or filters_per_chain < 1:
+        raise ValueError(f"thin, adapt_interval and filters_per_chain must be >= 1 (got {thin}, {adapt_interval}, {filters_per_chain})")
+    if warmup < 0 or n_iterations <= warmup:
+        raise ValueError(f"0 <= warmup < n_iterations expected, got warmup {warmup}, n_iterations {n_iterations}")
+    if not 0.0 < target_accept < 1.0:
+        raise ValueError(f"target_accept must lie in (0, 1), got {target_accept}")
+    if step_size is not None and not (step_size > 0 and math.isfinite(step_size)):
+        raise ValueError(f"step_size must be positive and finite, got {step_size}")
+    if not isinstance(initial_theta, Tensor) or not initial_theta.is_floating_point():
+        raise ValueError("initial_theta must be a floating-point tensor [C, P]")
+    if initial_theta.ndim == 1:
+        initial_theta = initial_theta.unsqueeze(0)
+    R = int(filters_per_chain)
+    rows = initial_theta.repeat_interleave(R, dim=0) if initial_theta.ndim == 2 else initial_theta
+    x0 = initial_state
+    if x0 is not None and x0.ndim == 2 and initial_theta.ndim == 2 and x0.shape[0] == initial_theta.shape[0]:
+        x0 = x0.repeat_interleave(R, dim=0)
+    rows, x0 = _pf._validate(sde, observations, rows, time_step, n_particles, x0)
+    C, P = initial_theta.shape
+    pos = sorted({int(d) for d in theta_positive_dims})
+    if any(d < 0 or d >= P for d in pos):
+        raise ValueError(f"theta_positive_dims must be in [0, {P}), got {tuple(theta_positive_dims)}")
+    mask = torch.zeros(P, dtype=torch.bool)
+    mask[pos] = True
+    mask = mask.to(initial_theta.device)
+    if pos and bool((initial_theta[:, pos] <= 0).any()):
+        raise ValueError("initial_theta must be positive on theta_positive_dims")
+    if proposal_scale_tril is not None:
+        L = torch.as_tensor(proposal_scale_tril)
+        if tuple(L.shape) != (P, P):
+            raise ValueError(f"proposal_scale_tril [{P}, {P}] expected, got {tuple(L.shape)}")
+        Lc = L.detach().double().cpu()
+        if not bool(torch.isfinite(Lc).all()) or bool((torch.triu(Lc, 1) != 0).any()) or bool((torch.diagonal(Lc) <= 0).any()):
+            raise ValueError("proposal_scale_tril must be finite and lower triangular with a positive diagonal")
+    return initial_theta, x0, mask, tuple(pos)
+
+
+def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: ObservationLikelihood, prior, time_step: float,
+                  initial_theta: Tensor, n_iterations: int, warmup: int = 0, n_particles: int = 512, filters_per_chain: int = 1,
+                  thin: int = 1, theta_positive_dims: Sequence[int] = (), positive_dims: Sequence[int] = (),
+                  initial_state: Optional[Tensor] = None, proposal: str = "bootstrap", proposal_scale_tril: Optional[Tensor] = None,
+                  step_size: Optional[float] = None, adapt: bool = True, target_accept: float = DEFAULT_TARGET_ACCEPT,
+                  adapt_interval: int = 25, key: Optional[Tensor] = None, _estimator=None, _trace: Optional[list] = None
+                  ) -> ParticleMCMCResult:
+    """``C`` independent PMMH chains, one per row of ``initial_theta [C, P]``, run in lock-step for ``n_iterations`` iterations of
+    which the first ``warmup`` adapt and are dropped; every ``thin``-th state after them is kept (the module docstring has the
+    rule).  ``prior``: the package's ``Prior`` or any object with ``log_prob(theta [C, P])``; ``theta_positive_dims``: the dims of
+    theta that walk in log space (``initial_theta`` must be positive there); ``n_particles``, ``initial_state`` (``[S]`` or
+    ``[C, S]``; default: the first observation), ``positive_dims`` (of the state) and ``proposal`` go to ``particle_filter``;
+    ``filters_per_chain``: independent filters averaged per proposal; ``proposal_scale_tril``, ``step_size``: the random walk
+    ``u' = u + step_size L z`` (defaults in the module docstring); ``adapt``: whether L is re-estimated once in warm-up (the step size
+    adapts in warm-up either way); ``key``: two int32 words (default: drawn from torch's generator on theta's device).  The same key
+    gives the same chains.  No gradients."""
+    theta0, x0, mask, pos_theta = _validate(sde, observations, observation_likelihood, initial_theta, time_step, n_iterations, warmup,
+                                            n_particles, filters_per_chain, thin, theta_positive_dims, initial_state, proposal,
+                                            proposal_scale_tril, step_size, target_accept, adapt_interval)
+    dev, dtype = theta0.device, theta0.dtype
+    C, P = theta0.shape
+    R = int(filters_per_chain)
+    obs = observations if observations.values.device == dev else observations.to(dev)
+    if key is None:
+        key = torch.randint(-2 ** 31, 2 ** 31, (2,), device=dev, dtype=torch.int32)
+    else:
+        key = torch.as_tensor(key).to(dev)
+        if key.numel() != 2 or key.is_floating_point():
+            raise ValueError("key must hold two 32-bit integer words")
+        key = key.reshape(2)
+    with torch.no_grad():
+        u0 = unconstrain(theta0, mask)
+        if proposal_scale_tril is not None:
+            L = torch.tril(torch.as_tensor(proposal_scale_tril).detach().to(device=dev, dtype=dtype))
+        elif C > 1:
+            L = torch.diag(u0.std(dim=0).clamp(min=DEFAULT_SCALE_FLOOR))
+        else:
+            L = torch.eye(P, device=dev, dtype=dtype)
+        run = dict(sde=sde, obs=obs, like=observation_likelihood, prior=prior, dt=float(time_step), u0=u0, x0=x0, mask=mask,
+                   pos_theta=pos_theta, pos_state=tuple(positive_dims), n_iterations=int(n_iterations), warmup=int(warmup),
+                   N=int(n_particles), R=R, thin=int(thin), proposal=proposal, L=L,
+                   step=float(step_size) if step_size is not None else 2.38 / math.sqrt(P), adapt=bool(adapt) and C > P,
+                   target_accept=float(target_accept), interval=int(adapt_interval), key=key, estimator=_estimator, trace=_trace)
+        route = None
+        if HIP_MCMC and _estimator is None and theta0.is_cuda and dtype == torch.float32 and type(prior) is Prior and prior.dim == P:
+            from .. import _hip
+            if P <= _hip.PMMH_MAX_PARAMS:
+                route = _pf._kernel_route(sde, obs, observation_likelihood, theta0.repeat_interleave(R, dim=0), int(n_particles), proposal)
+        out = _torch_loop(**run) if route is None else _kernel_loop(route, **run)
+        return _result(*out, mask)
+
+
+def _adaptation(i, warmup, interval, adapt):
+    """(whether the step size adapts, whether L is re-estimated) before the proposal of iteration i."""
+    return 0 < i <= warmup and i % interval == 0, adapt and i == warmup // 2 and warmup // 4 < warmup // 2
+
+
+def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n_iterations, warmup, N, R, thin, proposal, L, step,
+                adapt, target_accept, interval, key, estimator, trace):
+    dev, dtype = u0.device, u0.dtype
+    C, P = u0.shape
+    cur_u = u0.clone()
+    cur_t = torch.full((C,), float("-inf"), device=dev, dtype=dtype)
+    cur_ll = cur_t.clone()
+    n_keep = (n_iterations - warmup + thin - 1) // thin
+    samples = torch.empty(n_keep, C, P, device=dev, dtype=dtype)
+    lls, tgts = torch.empty(n_keep, C, device=dev, dtype=dtype), torch.empty(n_keep, C, device=dev, dtype=dtype)
+    window = torch.zeros((), device=dev, dtype=torch.int64)
+    kept_acc = torch.zeros(C, device=dev, dtype=torch.int64)
+    n_dead = torch.zeros((), device=dev, dtype=torch.int64)
+    w4, w2 = warmup // 4, warmup // 2
+    history = torch.empty(max(w2 - w4, 0), C, P, device=dev, dtype=dtype) if adapt else None
+    for i in range(n_iterations):
+        if _ITERATION_HOOK is not None:
+            _ITERATION_HOOK(i)
+        adapt_step, adapt_L = _adaptation(i, warmup, interval, adapt)
+        if adapt_step:
+            step *= math.exp(float(window) / (C * interval) - target_accept)
+            window.zero_()
+        if adapt_L:
+            L = adapted_scale_tril(history.reshape(-1, P), L)
+            step = 2.38 / math.sqrt(P)
+        prop_u = cur_u + step * (proposal_normals(C, P, i, key).to(dtype) @ L.T) if i > 0 else u0.clone()
+        theta = constrain(prop_u, mask)
+        prop_lp = _log_prior_jacobian(prior, theta, prop_u, mask)
+        rows = theta.repeat_interleave(R, dim=0)
+        fkey = filter_key(i, key)
+        if estimator is not None:
+            loglik = estimator(rows, i, fkey)
+        else:
+            loglik = _pf.particle_filter(sde, obs, like, rows, dt, n_particles=N, initial_state=x0, positive_dims=pos_state, key=fkey,
+                                         proposal=proposal).log_likelihood
+        loglik = loglik.to(dtype).reshape(C, R)
+        n_dead += torch.isneginf(loglik).all(dim=1).sum()
+        cur_u, cur_t, cur_ll, acc = _close(i, key, loglik, prop_u, prop_lp, cur_u, cur_t, cur_ll)
+        window += acc.sum()
+        if i >= warmup:
+            kept_acc += acc
+            if (i - warmup) % thin == 0:
+                k = (i - warmup) // thin
+                samples[k], lls[k], tgts[k] = constrain(cur_u, mask), cur_ll, cur_t
+        elif history is not None and w4 <= i < w2:
+            history[i - w4] = cur_u
+        if trace is not None:
+            trace.append(dict(prop_u=prop_u, theta_prop=rows, prop_log_prior=prop_lp, loglik=loglik, accept=acc, cur_u=cur_u,
+                              cur_log_target=cur_t, cur_loglik=cur_ll, step_size=step, scale_tril=L, filter_key=fkey))
+    rate = kept_acc.to(dtype) / (n_iterations - warmup)
+    return samples, lls, tgts, rate, step, L, n_dead
+
+
+def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n_iterations, warmup, N, R, thin, proposal, L,
+                 step, adapt, target_accept, interval, key, estimator, trace):
+    """The loop with the step kernel: launch i closes iteration i - 1 and opens iteration i, the filter launch follows.  When the
+    step size or L changes before iteration i (warm-up only) the proposal is opened again with the new values: the open half is a
+    pure function of (state, i, key, step size, L)."""
+    from .. import _hip
+    kind, network = route
+    dev = u0.device
+    C, P = u0.shape
+    f32 = dict(device=dev, dtype=torch.float32)
+    cur_u, prop_u = u0.clone().contiguous(), u0.clone().contiguous()
+    cur_t, cur_ll = torch.full((C,), float("-inf"), **f32), torch.full((C,), float("-inf"), **f32)
+    prop_lp, theta_prop = torch.empty(C, **f32), torch.empty(C * R, P, **f32)
+    fkey, n_acc = torch.empty(2, device=dev, dtype=torch.int32), torch.zeros(C, device=dev, dtype=torch.int32)
+    key = key.to(torch.int32).contiguous()
+    n_keep = (n_iterations - warmup + thin - 1) // thin
+    samples, lls, tgts = torch.empty(n_keep, C, P, **f32), torch.empty(n_keep, C, **f32), torch.empty(n_keep, C, **f32)
+    w4, w2 = warmup // 4, warmup // 2
+    history = torch.empty(max(w2 - w4, 0), C, P, **f32) if adapt else None
+    L_host = L.detach().float().cpu().contiguous()
+    prior_args = (1 if prior.type == PriorType.LOG_NORMAL else 0, float(prior.mean), float(prior.std), pos_theta)
+    # the filter launch's fixed arguments, formed once (particle_filter.particle_filter forms them per call)
+    H = like.obs_matrix
+    rows = torch.round(obs.times / dt).to(torch.int32)
+    term = like.kernel_terms(obs.values) if type(like) in COUNT_LIKELIHOODS else float(like.variance)
+    H = None if H is None else H.to(u0)
+    filt = _hip.guided_particle_filter if proposal == "bridge" else _hip.particle_filter
+    x0 = x0.contiguous()
+    logliks, loglik, window_base, pending = [], None, 0, None
+
+    def step_launch(i, closing, keep=None):
+        rows_out = (None, None, None) if keep is None else (samples[keep], lls[keep], tgts[keep])
+        _hip.pmmh_step(i, L_host, step, *prior_args, key, closing, cur_u, cur_t, cur_ll, prop_u, prop_lp, theta_prop, fkey, n_acc,
+                       *rows_out)
+
+    for i in range(n_iterations + 1):
+        if _ITERATION_HOOK is not None and i < n_iterations:
+            _ITERATION_HOOK(i)
+        closed = i - 1
+        keep = (closed - warmup) // thin if closed >= warmup and (closed - warmup) % thin == 0 else None
+        before = n_acc.clone() if trace is not None else None
+        step_launch(i, loglik, keep)
+        if trace is not None and pending is not None:
+            pending.update(accept=(n_acc - before) > 0, cur_u=cur_u.clone(), cur_log_target=cur_t.clone(), cur_loglik=cur_ll.clone())
+            trace.append(pending)
+        if i == n_iterations:
+            break
+        if history is not None and w4 <= closed < w2:
+            history[closed - w4].copy_(cur_u)
+        adapt_step, adapt_L = _adaptation(i, warmup, interval, adapt)
+        if adapt_step:
+            total = int(n_acc.sum())                       # the only host read of the loop, in warm-up only
+            step *= math.exp((total - window_base) / (C * interval) - target_accept)
+            window_base = total
+        if adapt_L:
+            L = adapted_scale_tril(history.reshape(-1, P), L)
+            L_host = L.detach().float().cpu().contiguous()
+            step = 2.38 / math.sqrt(P)
+        if adapt_step or adapt_L:
+            step_launch(i, None)                           # open iteration i again with the new step size / L
+        if i == warmup:
+            n_acc.zero_()
+        out = filt(kind, x0, kernel_theta(network, theta_prop), rows, obs.values, H, term, fkey, dt, N, pos_state, network=network)
+        loglik = out[0].view(C, R)
+        logliks.append(loglik)
+        if trace is not None:
+            pending = dict(prop_u=prop_u.clone(), theta_prop=theta_prop.clone(), prop_log_prior=prop_lp.clone(), loglik=loglik,
+                           step_size=step, scale_tril=L, filter_key=fkey.clone())
+    n_dead = torch.isneginf(torch.stack(logliks)).all(dim=2).sum()
+    rate = n_acc.to(torch.float32) / (n_iterations - warmup)
+    return samples, lls, tgts, rate, step, L, n_dead
+
+
+def split_r_hat_and_ess(draws: Tensor) -> tuple[Tensor, Tensor]:
+    """Split-R^ and the multi-chain effective sample size of ``draws [n, C, P]`` (n states of C chains), per coordinate, float64
+    (Gelman et al., BDA3 sections 11.4-11.5): every chain is split into halves (m = 2 C sequences of length h = n // 2, a middle
+    state of an odd n dropped), ``W`` the mean within-sequence variance, ``B / h`` the variance of the sequence means,
+    ``var+ = (h - 1) / h W + B / h``, ``R^ = sqrt(var+ / W)``; with the variogram ``V_t`` (mean squared difference at lag t over all
+    sequences), ``rho_t = 1 - V_t / (2 var+)`` and ``T`` the first odd lag at which ``rho_{T+1} + rho_{T+2} < 0``,
+    ``ESS = m h / (1 + 2 sum_{t=1..T} rho_t)``.  NaN for n < 4 or a coordinate that does not move."""
+    n, C, P = draws.shape
+    nan = torch.full((P,), float("nan"), dtype=torch.float64, device=draws.device)
+    if n < 4:
+        return nan, nan.clone()
+    h = n // 2
+    x = torch.cat([draws[:h], draws[n - h:]], dim=1).double()           # [h, m, P]
+    m = x.shape[1]
+    means = x.mean(dim=0)                                                # [m, P]
+    W = x.var(dim=0, unbiased=True).mean(dim=0)                          # [P]
+    B_over_h = means.var(dim=0, unbiased=True) if m > 1 else torch.zeros_like(W)
+    var_plus = (h - 1) / h * W + B_over_h
+    r_hat = torch.sqrt(var_plus / W)
+    xc = x - means[None]
+    sq = (xc * xc).cumsum(dim=0)                                         # [h, m, P]
+    total = sq[-1]
+    f = torch.fft.rfft(xc, n=2 * h, dim=0)
+    acov = torch.fft.irfft(f * f.conj(), n=2 * h, dim=0)[:h]            # sum_i xc_i xc_{i-t}
+    rho = torch.ones(h, P, dtype=torch.float64, device=draws.device)
+    for t in range(1, h):
+        # sum_i (x_i - x_{i-t})^2 = sum_{i >= t} x_i^2 + sum_{i < h - t} x_i^2 - 2 sum_i x_i x_{i-t}
+        s = (total - sq[t - 1]) + sq[h - t - 1] - 2.0 * acov[t]
+        rho[t] = 1.0 - (s.sum(dim=0) / (m * (h - t))) / (2.0 * var_plus)
+    n_pairs = (h - 2) // 2                                               # pairs (rho_{2k}, rho_{2k+1}), k = 1 .. n_pairs
+    tau = 1.0 + 2.0 * rho[1] if h > 1 else torch.ones_like(W)
+    if n_pairs > 0:
+        pairs = rho[2:2 + 2 * n_pairs].reshape(n_pairs, 2, P).sum(dim=1)
+        alive = torch.cumprod((pairs >= 0).to(torch.float64), dim=0)
+        tau = tau + 2.0 * (pairs * alive).sum(dim=0)
+    ess = m * h / tau
+    return r_hat, torch.where(torch.isfinite(r_hat), ess, nan)
+
+
+def _result(samples, lls, tgts, rate, step, L, n_dead, mask) -> ParticleMCMCResult:
+    from ..posterior.variational_posterior import QUANTILE_LEVELS, Quantiles
+    n_keep, C, P = samples.shape
+    flat = samples.reshape(n_keep * C, P)
+    levels = torch.tensor(QUANTILE_LEVELS, device=samples.device, dtype=samples.dtype)
+    nan = torch.full((P,), float("nan"), device=samples.device, dtype=samples.dtype)
+    chain_means = samples.mean(dim=0)
+    r_hat, ess = (t.to(samples.device) for t in split_r_hat_and_ess(unconstrain(samples, mask).double().cpu()))
+    return ParticleMCMCResult(
+        samples=samples, log_likelihood=lls, log_target=tgts, acceptance_rate=rate, mean=flat.mean(dim=0),
+        std=flat.std(dim=0) if flat.shape[0] > 1 else torch.zeros_like(nan), quantiles=Quantiles(*torch.quantile(flat, levels, dim=0).unbind(0)),
+        mean_standard_error=chain_means.std(dim=0) / math.sqrt(C) if C > 1 else nan, r_hat=r_hat, effective_sample_size=ess,
+        step_size=float(step), proposal_scale_tril=L, n_filters_dead=int(n_dead))

@@ -551,6 +551,38 @@ class VariationalPosterior:
             m + math.log(s1) - math.log(n_samples), math.sqrt(max(1.0 / ess - 1.0 / n_samples, 0.0)), ess, n_samples, 0, min_ess,
             times, shape(mean), shape(std), Quantiles(*(shape(v) for v in quant.unbind(0))), *draws)
 
+    @torch.no_grad()
+    def refine_parameters(self, sde: SDE, observation_likelihood: ObservationLikelihood, n_chains: int = 256,
+                          n_iterations: int = 600, warmup: int = 300, n_particles: int = 512, filters_per_chain: int = 1,
+                          thin: int = 1, proposal: str = "bootstrap"):
+        """When ``reweight_parameters`` says q(theta) is poor (a small ``effective_sample_size``: a mean-field q cannot follow a
+        correlated posterior), this gives something better: ``n_chains`` independent particle-MCMC chains (``particle_mcmc``) started
+        at draws of q under the EMA weights, as ``reweight_parameters`` draws them, which sample the exact theta posterior of the
+        Euler-Maruyama-discretised model on this posterior's grid (prior, first observation as start state and
+        ``state_space.positive_dims`` as everywhere here; q's positive mask says which dims walk in log space; the initial proposal
+        scale is q's own ``exp(log_std)``).  Returns the ``ParticleMCMCResult`` with ``variational_mean`` / ``variational_std``, the
+        plain moments of the starting draws, next to the chains' ``mean`` / ``std``; check ``r_hat`` and ``mean_standard_error``
+        before trusting them.  It runs on a CPU posterior too (the torch route) and touches none of ``sample()``'s caches or
+        graphs."""
+        import dataclasses
+        from ..inference import particle_mcmc as _mc
+        if n_chains < 1:
+            raise ValueError(f"n_chains must be >= 1, got {n_chains}")
+        q = self.model.sde_parameter_posterior
+        S, P = self.state_space.dim, q.sde_param_dim
+        if sde.state_dim != S or sde.sde_param_dim != P:
+            raise ValueError(f"sde has state_dim {sde.state_dim}, sde_param_dim {sde.sde_param_dim}; the posterior has {S}, {P}")
+        self.model.eval()
+        with self.exponential_moving_average.apply():
+            theta = q.rsample(n_chains)
+            scale = torch.diag(q.log_std.detach().exp())
+        res = _mc.particle_mcmc(sde, self.observations, observation_likelihood, self.prior, self.time_step, theta, n_iterations,
+                                warmup=warmup, n_particles=n_particles, filters_per_chain=filters_per_chain, thin=thin,
+                                theta_positive_dims=q._positive_dims, positive_dims=self.state_space.positive_dims,
+                                initial_state=self.observations.values[0], proposal=proposal, proposal_scale_tril=scale)
+        v_std = theta.std(dim=0) if n_chains > 1 else torch.zeros_like(theta[0])
+        return dataclasses.replace(res, variational_mean=theta.mean(dim=0), variational_std=v_std)
+
     def summary(self, n_samples: int = 1000, mixed_precision: bool = False) -> VariationalPosteriorSummary:
         s = self.sample(n_samples, mixed_precision)
         levels = torch.tensor(QUANTILE_LEVELS, device=self.device, dtype=s.sde_parameters.dtype)
