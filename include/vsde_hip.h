@@ -761,6 +761,64 @@ int vsde_pmmh_step(int C, int P, int R, int iteration, const float *scale_tril, 
                    float *cur_u, float *cur_log_target, float *cur_loglik, float *prop_u, float *prop_log_prior, float *theta_prop,
                    uint32_t *filter_key, float *sample_row, float *loglik_row, float *target_row, int *n_accept, void *stream);
 
+/* vsde_pmmh_step for chains that carry a latent path with their state (PMMH as a sampler of p(theta, x_{0:T} | y)): the same launch,
+ * every output of vsde_pmmh_step bit for bit, and for a chain ACCEPTED in the close half the record of the proposal's path, drawn
+ * from what the filter launch of iteration it = iteration - 1 stored: particles[C R][K][N][S] (states before resampling) and
+ * ancestors[C R][K][N] (filter m = c R + r, N particles, K observations).
+ *   Filter: w_r = exp(loglik_prop[c][r] - max_r), C_r its inclusive sums in r order, v0 and v1 the uniforms ((w >> 8) + 0.5) 2^-24
+ * of the first and second word of philox4x32_10({it, 0, c, 6}, key), r* = min(#{r : C_r <= v0 C_{R-1}}, R - 1), m* = c R + r*.
+ * Slot: J = min(floor(v1 N), N - 1) (the fp32 product), lineage[K-1] = ancestors[m*][K-1][J] (a uniformly chosen offspring slot of
+ * the filter's own last resampling has an ancestor drawn from the final weights), lineage[k-1] = ancestors[m*][k-1][lineage[k]],
+ * every entry clamped into [0, N - 1].  Record: cur_anchor[c][k][S] = particles[m*][k][lineage[k]], cur_noise_path[c][k] = m* N +
+ * lineage[k], cur_path_iteration[c] = it.  Where every estimate is -inf (iteration 0 accepts such a proposal) the record is dead:
+ * noise paths 0xFFFFFFFF, anchors NaN.  A rejected chain keeps its record.  Then, where not NULL, anchor_row[C][K][S],
+ * noise_row[C][K] and iteration_row[C] receive the carried record of every chain.  Counter word 6 in the fourth slot is new.
+ *   VSDE_E_BADARG before any HIP call: those of vsde_pmmh_step; N, K or S < 1, C R N >= 2^32, a NULL pointer among particles,
+ * ancestors, cur_anchor, cur_noise_path, cur_path_iteration. */
+int vsde_pmmh_step_paths(int C, int P, int R, int iteration, const float *scale_tril, double step_size, int prior_type,
+                         double prior_mean, double prior_std, const uint8_t *theta_positive_mask_host, const uint32_t *key,
+                         const float *loglik_prop, float *cur_u, float *cur_log_target, float *cur_loglik, float *prop_u,
+                         float *prop_log_prior, float *theta_prop, uint32_t *filter_key, float *sample_row, float *loglik_row,
+                         float *target_row, int *n_accept, int N, int K, int S, const float *particles, const int *ancestors,
+                         float *cur_anchor, uint32_t *cur_noise_path, int *cur_path_iteration, float *anchor_row, uint32_t *noise_row,
+                         int *iteration_row, void *stream);
+
+/* Replay of B path records of vsde_pmmh_step_paths: paths[B][T+1][S] on the grid, T = obs_rows[K-1].  Record b brings x0[b][S],
+ * theta[b][P] (rates), anchors[b][K][S], noise_path[b][K] and its own filter key keys[b][2]; kind / descriptors, S, P, K, O,
+ * obs_rows, time_step and positive_mask_host are those of the filter launches the records were drawn from.  One launch, a thread
+ * per (k, b): segment k, the grid steps obs_rows[k-1] .. obs_rows[k] - 1 (from 0 for k = 0), starts at anchors[b][k-1] (x0[b] for
+ * k = 0) and takes the normals of path noise_path[b][k] under keys[b], with the step and 1e-6 clamp of vsde_particle_filter: the
+ * state after step t goes to paths[b][t+1], paths[b][0] = x0[b].  A record with noise_path[b][K-1] = 0xFFFFFFFF is dead: paths NaN.
+ * A segment whose rows decrease or pass T is not written.
+ *   VSDE_E_BADARG before any HIP call: B, K < 1, S or O outside 1..16, T < 0, B K >= 2^31, time_step <= 0, a NULL argument. */
+int vsde_anchored_replay(int kind, int B, int S, int P, int K, int O, int T, const float *x0, const float *theta, const int *obs_rows,
+                         const float *anchors, const uint32_t *noise_path, const uint32_t *keys, double time_step,
+                         const uint8_t *positive_mask_host, float *paths, void *stream);
+int vsde_crn_anchored_replay(const vsde_crn_network *net, int B, int S, int P, int K, int O, int T, const float *x0, const float *theta,
+                             const int *obs_rows, const float *anchors, const uint32_t *noise_path, const uint32_t *keys,
+                             double time_step, const uint8_t *positive_mask_host, float *paths, void *stream);
+int vsde_crn_kinetic_anchored_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int S, int P, int K, int O, int T,
+                                     const float *x0, const float *rates, const int *obs_rows, const float *anchors,
+                                     const uint32_t *noise_path, const uint32_t *keys, double time_step,
+                                     const uint8_t *positive_mask_host, float *paths, void *stream);
+
+/* vsde_anchored_replay for records drawn from vsde_guided_particle_filter launches: segment k repeats the bridge steps towards
+ * obs_values[k], so obs_values[K][O], obs_matrix[O][S] or NULL and variance must be those launches' as well.  S <= 4 and O <= 4
+ * (VSDE_E_BADARG otherwise, before any HIP call). */
+int vsde_guided_anchored_replay(int kind, int B, int S, int P, int K, int O, int T, const float *x0, const float *theta,
+                                const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                                const float *anchors, const uint32_t *noise_path, const uint32_t *keys, double time_step,
+                                const uint8_t *positive_mask_host, float *paths, void *stream);
+int vsde_crn_guided_anchored_replay(const vsde_crn_network *net, int B, int S, int P, int K, int O, int T, const float *x0,
+                                    const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                    double variance, const float *anchors, const uint32_t *noise_path, const uint32_t *keys,
+                                    double time_step, const uint8_t *positive_mask_host, float *paths, void *stream);
+int vsde_crn_kinetic_guided_anchored_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int S, int P, int K, int O,
+                                            int T, const float *x0, const float *rates, const int *obs_rows, const float *obs_values,
+                                            const float *obs_matrix, double variance, const float *anchors,
+                                            const uint32_t *noise_path, const uint32_t *keys, double time_step,
+                                            const uint8_t *positive_mask_host, float *paths, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

@@ -5,7 +5,9 @@ Three figures, in ms per iteration, in the same process:
 
 (a) the filter launch alone on the same [C, P] batch (``_hip.particle_filter``): what an iteration cannot go below;
 (b) the kernel route: the step kernel (csrc/vsde_mcmc.hip) and the filter launch;
-(c) ``particle_mcmc.HIP_MCMC = False``: the torch step around the same kernel filter, on the same device.
+(c) ``particle_mcmc.HIP_MCMC = False``: the torch step around the same kernel filter, on the same device;
+(d) the kernel route with ``return_paths=True`` (the filter stores particles and ancestors, the step kernel draws the records of
+    the chains it accepts), and the one replay launch after the loop over its ``(reps + 1) C`` records, by events of its own.
 
 Time: device events around ``--reps`` iterations after ``--warmup`` warm-up iterations of the same call (the events are recorded
 from ``particle_mcmc._ITERATION_HOOK``), twice (the pair shows the spread).  Prints one JSON line.
@@ -61,7 +63,21 @@ def main():
     run_filter = lambda: _hip.particle_filter("lotka_volterra", x0, theta, rows, obs.values, None, like.variance, key, dt, N, pos)
     f1, f2 = timed(run_filter, 3, a.reps), timed(run_filter, 0, a.reps)
 
-    def chain_ms(hip):
+    replay_ms = []
+    real_replay = _hip.anchored_replay
+
+    def timed_replay(*args, **kw):
+        r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        r0.record()
+        out = real_replay(*args, **kw)
+        r1.record()
+        torch.cuda.synchronize()
+        replay_ms.append(r0.elapsed_time(r1))
+        return out
+
+    _hip.anchored_replay = timed_replay
+
+    def chain_ms(hip, paths=False):
         mc.HIP_MCMC = hip
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
@@ -74,7 +90,7 @@ def main():
         mc._ITERATION_HOOK = hook
         try:
             res = particle_mcmc(sde, obs, like, prior, dt, theta, a.warmup + a.reps + 1, warmup=a.warmup, n_particles=N,
-                                theta_positive_dims=(0, 1, 2), positive_dims=pos, key=key)
+                                theta_positive_dims=(0, 1, 2), positive_dims=pos, key=key, return_paths=paths)
         finally:
             mc._ITERATION_HOOK, mc.HIP_MCMC = None, True
         torch.cuda.synchronize()
@@ -84,11 +100,17 @@ def main():
     k2, _ = chain_ms(True)
     t1, res_t = chain_ms(False)
     t2, _ = chain_ms(False)
-    fa, kb, tc = min(f1, f2), min(k1, k2), min(t1, t2)
+    p1, res_p = chain_ms(True, paths=True)
+    p2, _ = chain_ms(True, paths=True)
+    k3, _ = chain_ms(True)                                # once more without paths, after them: drift of the box shows here
+    fa, kb, tc, pd = min(f1, f2), min(k1, k2, k3), min(t1, t2), min(p1, p2)
     rec = {"tool": "particle_mcmc_bench", "device": torch.cuda.get_device_name(DEV), "C": C, "N": N, "R": 1, "steps": int(rows[-1]),
            "observations": int(rows.shape[0]), "reps": a.reps, "warmup": a.warmup,
            "filter_alone_ms": round(fa, 4), "filter_alone_ms_runs": [round(f1, 4), round(f2, 4)],
-           "kernel_route_ms_per_iteration": round(kb, 4), "kernel_route_ms_runs": [round(k1, 4), round(k2, 4)],
+           "kernel_route_ms_per_iteration": round(kb, 4), "kernel_route_ms_runs": [round(k1, 4), round(k2, 4), round(k3, 4)],
+           "paths_ms_per_iteration": round(pd, 4), "paths_ms_runs": [round(p1, 4), round(p2, 4)], "paths_over_kernel_route": round(pd / kb, 3),
+           "replay_ms": round(min(replay_ms), 4), "replay_ms_runs": [round(v, 4) for v in replay_ms], "replay_records": (a.reps + 1) * C,
+           "paths_equal_theta_chain": bool(torch.equal(res.samples, res_p.samples)),
            "torch_step_ms_per_iteration": round(tc, 4), "torch_step_ms_runs": [round(t1, 4), round(t2, 4)],
            "step_overhead_over_filter": round((kb - fa) / fa, 3), "torch_over_kernel_route": round(tc / kb, 2),
            "acceptance_rate": round(float(res.acceptance_rate.mean()), 3), "acceptance_rate_torch_step": round(float(res_t.acceptance_rate.mean()), 3),

@@ -72,6 +72,8 @@ EXPORTS = (
     "vsde_guided_particle_filter", "vsde_crn_guided_particle_filter", "vsde_crn_kinetic_guided_particle_filter",
     "vsde_filter_replay", "vsde_crn_filter_replay", "vsde_crn_kinetic_filter_replay",
     "vsde_guided_filter_replay", "vsde_crn_guided_filter_replay", "vsde_crn_kinetic_guided_filter_replay", "vsde_pmmh_step",
+    "vsde_pmmh_step_paths", "vsde_anchored_replay", "vsde_crn_anchored_replay", "vsde_crn_kinetic_anchored_replay",
+    "vsde_guided_anchored_replay", "vsde_crn_guided_anchored_replay", "vsde_crn_kinetic_guided_anchored_replay",
     "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
@@ -466,7 +468,7 @@ def particle_filter_max_particles(kind: str, state_dim: int, proposal: str = "bo
 
 
 def _particle_filter(entry: str, want_lw: bool, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
-                     n_particles, positive_dims, network, return_particles):
+                     n_particles, positive_dims, network, return_particles, store=None):
     lib = load()
     dev = _require_hip(x0, theta, obs_rows, obs_values, obs_matrix, key)
     x0, theta, obs_values = _f32c(x0), _f32c(theta), _f32c(obs_values)
@@ -493,6 +495,14 @@ def _particle_filter(entry: str, want_lw: bool, kind, x0, theta, obs_rows, obs_v
         extra = ()
         if want_lw:
             extra = (torch.empty(M, K, N, **f32) if keep else None,)
+        if store is not None:
+            particles, ancestors = store
+            if not (particles.is_contiguous() and ancestors.is_contiguous() and particles.dtype == torch.float32
+                    and ancestors.dtype == torch.int32 and particles.device == ancestors.device == dev
+                    and tuple(particles.shape) == (M, K, N, S) and tuple(ancestors.shape) == (M, K, N)):
+                raise ValueError(f"particle_filter: store = (particles fp32 [{M}, {K}, {N}, {S}], ancestors int32 [{M}, {K}, {N}]), "
+                                 "contiguous on the call's device, expected")
+            extra = (None,) if want_lw else ()
         prefix, term = _observation_term(variance, K, dev)
         if prefix and want_lw:
             raise ValueError("the guided particle filter needs a Gaussian observation term")
@@ -505,24 +515,25 @@ def _particle_filter(entry: str, want_lw: bool, kind, x0, theta, obs_rows, obs_v
 
 
 def particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, key, time_step: float,
-                    n_particles: int, positive_dims=(), network=None, return_particles: bool = False):
+                    n_particles: int, positive_dims=(), network=None, return_particles: bool = False, store=None):
     """Bootstrap particle filters of a built-in model SDE (``kind`` in SDE_KINDS), one per row of theta [M, P] (the effective
     constants [M, 2R] for a CrnKineticRoute) from the start states x0 [M, S], against obs_values [K, O] at the grid rows obs_rows
     (int32 device tensor [K]) with a Gaussian observation term (obs_matrix [O, S] or None; ``variance``: a number) or a count term
     (``variance``: the likelihood's ``CountKernelTerms``: vsde_count_particle_filter); noise and resampling uniforms come from
     the Philox stream of ``key`` (2 int32 words on the device).  See include/vsde_hip.h: vsde_particle_filter.  Returns
     (log_likelihood [M], increments [M, K], effective_sample_size [M, K], filtered_mean [M, K, S], filtered_std [M, K, S],
-    particles [M, K, N, S] or None, ancestors [M, K, N] int32 or None)."""
+    particles [M, K, N, S] or None, ancestors [M, K, N] int32 or None).  ``store``: (particles, ancestors) buffers of those shapes
+    to write into instead of ``return_particles`` (a caller that runs the filter in a loop allocates them once)."""
     return _particle_filter("particle_filter", False, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step,
-                            n_particles, positive_dims, network, return_particles)
+                            n_particles, positive_dims, network, return_particles, store)
 
 
 def guided_particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, key, time_step: float,
-                           n_particles: int, positive_dims=(), network=None, return_particles: bool = False):
+                           n_particles: int, positive_dims=(), network=None, return_particles: bool = False, store=None):
     """``particle_filter`` with the bridge proposal (include/vsde_hip.h: vsde_guided_particle_filter; S <= 4, O <= 4): the same
-    arguments, and the same 7 outputs followed by log_weights [M, K, N] or None."""
+    arguments, and the same 7 outputs followed by log_weights [M, K, N] or None (None with ``store``)."""
     return _particle_filter("guided_particle_filter", True, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key,
-                            time_step, n_particles, positive_dims, network, return_particles)
+                            time_step, n_particles, positive_dims, network, return_particles, store)
 
 
 def _filter_replay(entry: str, kind, x0, theta, obs_rows, model, key, time_step, particles, ancestors, last_slot, n_steps,
@@ -587,7 +598,7 @@ PMMH_MAX_PARAMS = 16
 
 def pmmh_step(iteration: int, scale_tril, step_size: float, prior_type: int, prior_mean: float, prior_std: float,
               theta_positive_dims, key, loglik_prop, cur_u, cur_log_target, cur_loglik, prop_u, prop_log_prior, theta_prop,
-              filter_key, n_accept, sample_row=None, loglik_row=None, target_row=None) -> None:
+              filter_key, n_accept, sample_row=None, loglik_row=None, target_row=None, _paths=None) -> None:
     """One Metropolis step of particle MCMC, in place (include/vsde_hip.h: vsde_pmmh_step): closes iteration ``iteration - 1`` with
     the filter estimates ``loglik_prop [C, R]`` (None: nothing to close) and opens iteration ``iteration``.  ``scale_tril``: a
     contiguous fp32 CPU tensor [P, P]; ``key`` / ``filter_key``: 2 int32 words on the device; chain state ``cur_u [C, P]``,
@@ -612,12 +623,99 @@ def pmmh_step(iteration: int, scale_tril, step_size: float, prior_type: int, pri
              (prop_log_prior, C), (theta_prop, C * R * P), (sample_row, C * P), (loglik_row, C), (target_row, C))
     if any(t is not None and t.numel() != n for t, n in sizes):
         raise ValueError(f"pmmh_step: a tensor does not have the size that C = {C}, P = {P}, R = {R} give it")
+    entry, tail = lib.vsde_pmmh_step, ()
+    if _paths is not None:
+        particles, ancestors, cur_anchor, cur_noise_path, cur_path_iteration, anchor_row, noise_row, iteration_row = _paths
+        bad = "pmmh_step_paths: particles fp32 [C R, K, N, S], ancestors int32 [C R, K, N], cur_anchor fp32 [C, K, S], cur_noise_path " \
+              "int32 [C, K], cur_path_iteration int32 [C] and rows of the records' shapes or None, contiguous on one device, expected"
+        if not (isinstance(particles, torch.Tensor) and particles.ndim == 4 and particles.shape[0] == C * R):
+            raise ValueError(bad)
+        _, K, N, S = particles.shape
+        for t, dt, shape in ((particles, torch.float32, (C * R, K, N, S)), (ancestors, torch.int32, (C * R, K, N)),
+                             (cur_anchor, torch.float32, (C, K, S)), (cur_noise_path, None, (C, K)),
+                             (cur_path_iteration, torch.int32, (C,)), (anchor_row, torch.float32, (C, K, S)), (noise_row, None, (C, K)),
+                             (iteration_row, torch.int32, (C,))):
+            required = t is particles or t is ancestors or t is cur_anchor or t is cur_noise_path or t is cur_path_iteration
+            if t is None and not required:
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape \
+                    or (t.dtype != dt if dt else t.dtype not in (torch.int32, torch.uint32)):
+                raise ValueError(bad)
+        entry = lib.vsde_pmmh_step_paths
+        tail = (ctypes.c_int(N), ctypes.c_int(K), ctypes.c_int(S), _ptr(particles), _ptr(ancestors), _ptr(cur_anchor),
+                _ptr(cur_noise_path), _ptr(cur_path_iteration), _ptr(anchor_row), _ptr(noise_row), _ptr(iteration_row))
     with torch.cuda.device(dev):
-        _call(lib.vsde_pmmh_step, ctypes.c_int(C), ctypes.c_int(P), ctypes.c_int(R), ctypes.c_int(int(iteration)),
+        _call(entry, ctypes.c_int(C), ctypes.c_int(P), ctypes.c_int(R), ctypes.c_int(int(iteration)),
               ctypes.c_void_p(scale_tril.data_ptr()), ctypes.c_double(step_size), ctypes.c_int(int(prior_type)),
               ctypes.c_double(prior_mean), ctypes.c_double(prior_std), _mask_bytes(theta_positive_dims, P), _ptr(key),
               _ptr(loglik_prop), _ptr(cur_u), _ptr(cur_log_target), _ptr(cur_loglik), _ptr(prop_u), _ptr(prop_log_prior),
-              _ptr(theta_prop), _ptr(filter_key), _ptr(sample_row), _ptr(loglik_row), _ptr(target_row), _ptr(n_accept), _stream(dev))
+              _ptr(theta_prop), _ptr(filter_key), _ptr(sample_row), _ptr(loglik_row), _ptr(target_row), _ptr(n_accept), *tail,
+              _stream(dev))
+
+
+def pmmh_step_paths(iteration: int, scale_tril, step_size: float, prior_type: int, prior_mean: float, prior_std: float,
+                    theta_positive_dims, key, loglik_prop, cur_u, cur_log_target, cur_loglik, prop_u, prop_log_prior, theta_prop,
+                    filter_key, n_accept, particles, ancestors, cur_anchor, cur_noise_path, cur_path_iteration, sample_row=None,
+                    loglik_row=None, target_row=None, anchor_row=None, noise_row=None, iteration_row=None) -> None:
+    """``pmmh_step`` for chains that carry a latent path (include/vsde_hip.h: vsde_pmmh_step_paths): the same step, and for every
+    chain it accepts the record of the proposal's path drawn from ``particles [C R, K, N, S]`` and ``ancestors [C R, K, N]`` (int32),
+    what the filter launch of the closed iteration stored.  The records ``cur_anchor [C, K, S]``, ``cur_noise_path [C, K]`` (int32
+    holding the uint32 path indices; all ones: dead) and ``cur_path_iteration [C]`` (int32) are written in place; ``anchor_row``,
+    ``noise_row``, ``iteration_row``: where the carried records are kept, or None."""
+    pmmh_step(iteration, scale_tril, step_size, prior_type, prior_mean, prior_std, theta_positive_dims, key, loglik_prop, cur_u,
+              cur_log_target, cur_loglik, prop_u, prop_log_prior, theta_prop, filter_key, n_accept, sample_row, loglik_row, target_row,
+              _paths=(particles, ancestors, cur_anchor, cur_noise_path, cur_path_iteration, anchor_row, noise_row, iteration_row))
+
+
+def _anchored_replay(entry: str, kind, x0, theta, obs_rows, model, anchors, noise_path, keys, time_step, n_steps, positive_dims,
+                     network):
+    lib = load()
+    dev = _require_hip(x0, theta, obs_rows, anchors, noise_path, keys, *model[:2])
+    x0, theta, anchors = _f32c(x0), _f32c(theta), _f32c(anchors)
+    ints = (torch.int32, torch.uint32)
+    if obs_rows.dtype != torch.int32 or obs_rows.ndim != 1 or noise_path.dtype not in ints or keys.dtype not in ints:
+        raise ValueError("anchored_replay: obs_rows must be an int32 [K] tensor, noise_path [B, K] and keys [B, 2] int32 tensors")
+    obs_rows, noise_path, keys = obs_rows.contiguous(), noise_path.contiguous(), keys.contiguous()
+    K = obs_rows.shape[0]
+    if x0.ndim != 2 or theta.ndim != 2 or theta.shape[0] != x0.shape[0] or tuple(anchors.shape) != (x0.shape[0], K, x0.shape[1]) \
+            or tuple(noise_path.shape) != (x0.shape[0], K) or tuple(keys.shape) != (x0.shape[0], 2):
+        raise ValueError(f"anchored_replay: x0 [B, S], theta [B, P], obs_rows [K], anchors [B, K, S], noise_path [B, K], keys [B, 2] "
+                         f"expected, got {tuple(x0.shape)}, {tuple(theta.shape)}, {tuple(obs_rows.shape)}, {tuple(anchors.shape)}, "
+                         f"{tuple(noise_path.shape)}, {tuple(keys.shape)}")
+    B, S = x0.shape
+    T = int(obs_rows[-1]) if n_steps is None and K else int(n_steps or 0)
+    obs_values, obs_matrix, variance = model
+    O, extra = S, ()
+    if entry.startswith("guided"):
+        obs_values = _f32c(obs_values)
+        obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
+        if obs_values.ndim != 2 or obs_values.shape[0] != K or (obs_matrix is not None and tuple(obs_matrix.shape) != (obs_values.shape[1], S)):
+            raise ValueError(f"anchored_replay: obs_values [{K}, O] and obs_matrix [O, {S}] expected")
+        O, extra = obs_values.shape[1], (_ptr(obs_values), _ptr(obs_matrix), ctypes.c_double(variance))
+    with torch.cuda.device(dev):
+        paths = torch.empty(B, T + 1, S, device=dev, dtype=torch.float32) if T >= 0 else None   # a bad T is the entry point's to refuse
+        _call(*_sde_entry(lib, entry, kind, network), ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(theta.shape[1]), ctypes.c_int(K),
+              ctypes.c_int(O), ctypes.c_int(T), _ptr(x0), _ptr(theta), _ptr(obs_rows), *extra, _ptr(anchors), _ptr(noise_path),
+              _ptr(keys), ctypes.c_double(time_step), _mask_bytes(positive_dims, S), _ptr(paths), _stream(dev))
+    return paths
+
+
+def anchored_replay(kind: str, x0, theta, obs_rows, anchors, noise_path, keys, time_step: float, positive_dims=(), network=None,
+                    n_steps: Optional[int] = None):
+    """Paths [B, T+1, S] of B path records of ``pmmh_step_paths`` (include/vsde_hip.h: vsde_anchored_replay): per record its start
+    state x0 [B, S], theta [B, P] (the effective constants for a CrnKineticRoute), anchors [B, K, S], noise_path [B, K] and filter
+    key keys [B, 2] (int32); ``kind``, obs_rows, time_step, positive_dims and network as given to the filter launches the records
+    were drawn from.  ``n_steps``: obs_rows[K-1] when the caller knows it (saves reading it back from the device)."""
+    return _anchored_replay("anchored_replay", kind, x0, theta, obs_rows, (None, None, None), anchors, noise_path, keys, time_step,
+                            n_steps, positive_dims, network)
+
+
+def guided_anchored_replay(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, anchors, noise_path, keys,
+                           time_step: float, positive_dims=(), network=None, n_steps: Optional[int] = None):
+    """``anchored_replay`` for records drawn from ``guided_particle_filter`` launches (vsde_guided_anchored_replay; S <= 4, O <= 4):
+    the bridge steps need the observations, obs_matrix and variance of those launches as well."""
+    return _anchored_replay("guided_anchored_replay", kind, x0, theta, obs_rows, (obs_values, obs_matrix, variance), anchors,
+                            noise_path, keys, time_step, n_steps, positive_dims, network)
 
 
 def _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean, post_log_std, theta_positive_dims):

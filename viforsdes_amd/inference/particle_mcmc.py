@@ -43,12 +43,40 @@ chain reject more at any step size and moves the optimum down (Sherlock, Thiery,
 optimal noise level in high dimension, 15..25 % in the few dimensions of this package's models).  After warm-up every ``thin``-th
 state is kept and nothing is read back from the device.
 
+Paths (``return_paths=True``).  PMMH as published (section 2.4.2 of the paper) samples the JOINT posterior ``p(theta, x_{0:T} | y)``:
+every proposal also draws one trajectory from its filter's genealogy, accepted or rejected together with theta.  The chain carries
+the trajectory as a record of a few numbers per observation (the noise is counter-based, so the states between observations are
+recomputed at the end).  With ``N`` particles, ``K`` observations at the grid rows ``rows``, ``fkey_i`` the filter key of iteration i:
+
+4. the filter of step 2 runs with ``return_particles=True``: particles ``X[m, k, j]`` (before resampling at k), ancestors ``a[m, k, j]``;
+5. the filter: ``w_r = exp(loglik[c, r] - max_r)``, ``C_r`` its inclusive cumulative sums made non-decreasing by a running maximum,
+   ``v0`` and ``v1`` the uniforms ``((w >> 8) + 0.5) 2^-24`` of the first and second word of ``philox4x32_10({i, 0, c, 6}, key)``,
+   ``r* = min(#{r : C_r <= v0 C_{R-1}}, R - 1)``, ``m* = c R + r*``: a filter chosen in proportion to its estimate is what keeps the
+   average of R estimators exact for the path as well;
+6. the final slot: ``J = min(floor(v1 N), N - 1)`` (the product in fp32) and ``lineage[K-1] = a[m*, K-1, J]``: the filter's own
+   systematic resampling at the last observation gave offspring slot J the threshold ``(J + u) / N``, uniform on (0, 1] for a
+   uniform J, so its ancestor is a draw from the final weights, whatever the weights are made of (no weights, no scan, the same
+   for Gaussian, count and bridge weights).  Trace: ``lineage[k-1] = a[m*, k-1, lineage[k]]``, every entry clamped into [0, N - 1];
+7. the proposal's record: ``anchors[k] = X[m*, k, lineage[k]]`` (``[K, S]``), ``noise_path[k] = m* N + lineage[k]`` (uint32 ``[K]``),
+   ``path_iteration = i``.  A proposal whose ``ll`` is -inf or NaN has a dead record: noise paths 0xFFFFFFFF, anchors NaN;
+8. on acceptance the record becomes the chain's with ``u``, ``target`` and ``ll`` (the decision of step 3 is untouched; counter word
+   6 in the fourth slot is new); at a kept state whose index is a multiple of ``path_thin`` the record is kept with it;
+9. after the loop every kept record is replayed as in ``particle_smoother``: segment k, the grid steps ``rows[k-1] .. rows[k] - 1``
+   (segment 0 from step 0 and ``x0[c]``), starts at ``anchors[k-1]``, takes the normals of path ``noise_path[k]`` under the key
+   ``fkey_{path_iteration}`` and the theta of the kept state, and runs the filter's step (Euler-Maruyama, or the bridge step towards
+   ``y_k`` for ``proposal="bridge"``, then the 1e-6 clamp).  The state after step t goes to ``paths[.., t + 1]``, ``paths[.., 0] =
+   x0[c]``; a dead record (a chain that never reached a finite target) gives NaN paths and ``path_iteration`` -1.
+
+With ``return_paths=False`` nothing of this happens: no store, no launch, no random number.
+
 The torch code below is the specification; it takes any SDE, any likelihood and any prior object with ``log_prob``, runs on CPU or
 GPU and follows the dtype of ``initial_theta``.  Where ``particle_filter`` takes its kernel route, ``initial_theta`` is CUDA fp32,
 ``P <= 16`` and ``prior`` is the package's ``Prior``, everything but the filter runs as ONE kernel per iteration
 (csrc/vsde_mcmc.hip, a thread per chain: it closes iteration i - 1 and opens iteration i), and an iteration is that launch, the
-rate-law map of a kinetic network, and the filter launch with the device key the step kernel wrote.  ``HIP_MCMC = False`` forces the
-torch step (around whatever route the filter takes) for A/B."""
+rate-law map of a kinetic network, and the filter launch with the device key the step kernel wrote.  With paths the same kernel
+draws the record of every chain it accepts from the particles and ancestors the filter launch stored (buffers allocated once), and
+ONE replay launch after the loop (csrc/vsde_anchored.hip: ar_kernel, a thread per (observation, record)) turns the kept records
+into paths.  ``HIP_MCMC = False`` forces the torch step (around whatever route the filter takes) for A/B."""
 from __future__ import annotations
 
 import math
@@ -68,6 +96,7 @@ HIP_MCMC = True   # set False to force the torch step (A/B tests); the filter ke
 DEFAULT_TARGET_ACCEPT = 0.15
 COVARIANCE_JITTER = 1e-8
 DEFAULT_SCALE_FLOOR = 1e-3
+DEAD_PATH = 0xFFFFFFFF   # noise_path of a record without a path
 _ITERATION_HOOK = None   # measurement aid (tools/particle_mcmc_bench.py): called with i at the top of every iteration of either loop
 
 
@@ -89,7 +118,12 @@ class ParticleMCMCResult:
     * ``n_filters_dead``: proposals (over the whole run, warm-up included) whose every filter returned -inf -- many of them
       means the filter, not the chain, is the problem: more particles, or ``proposal="bridge"``;
     * ``variational_mean`` / ``variational_std [P]``: plain moments of the q draws the chains started from
-      (``refine_parameters`` only, else None)."""
+      (``refine_parameters`` only, else None);
+    * with ``return_paths=True`` (else None): ``paths [n_path, C, T+1, S]``: the latent path of every ``path_thin``-th kept state
+      on the grid, a draw of ``x_{0:T} | y`` JOINTLY with that state's theta; ``path_iteration [n_path, C]`` (int32): the iteration
+      whose filter the path came from, -1 for a dead record (its path is NaN); ``path_mean``, ``path_std [T+1, S]`` and
+      ``path_quantiles`` over all live draws of all chains; ``path_mean_standard_error [T+1, S]``: the std over chains of the
+      per-chain path means divided by sqrt(C) (NaN for C = 1)."""
     samples: Tensor
     log_likelihood: Tensor
     log_target: Tensor
@@ -105,6 +139,12 @@ class ParticleMCMCResult:
     n_filters_dead: int
     variational_mean: Optional[Tensor] = None
     variational_std: Optional[Tensor] = None
+    paths: Optional[Tensor] = None
+    path_iteration: Optional[Tensor] = None
+    path_mean: Optional[Tensor] = None
+    path_std: Optional[Tensor] = None
+    path_quantiles: Any = None
+    path_mean_standard_error: Optional[Tensor] = None
 
 
 def _words(key: Tensor, c0, c1, c2, c3) -> list[Tensor]:
@@ -138,6 +178,106 @@ def filter_key(iteration: int, key: Tensor) -> Tensor:
     w = _words(key, iteration, 0, 0, 5)
     k = torch.cat([w[0].reshape(1), w[1].reshape(1)])
     return torch.where(k >= 2 ** 31, k - 2 ** 32, k).to(torch.int32)
+
+
+def filter_keys(iterations: Tensor, key: Tensor) -> Tensor:
+    """``filter_key`` for a tensor of iterations ``[...]``: int32 ``[..., 2]`` (a negative iteration, a dead record's, counts as 0)."""
+    w = _words(key, iterations.to(device=key.device, dtype=torch.int64).clamp(min=0), 0, 0, 5)
+    k = torch.stack([w[0], w[1]], dim=-1)
+    return torch.where(k >= 2 ** 31, k - 2 ** 32, k).to(torch.int32)
+
+
+def path_uniforms(n_chains: int, iteration: int, key: Tensor) -> tuple[Tensor, Tensor]:
+    """``(v0, v1)``, fp32 ``[C]`` each: the uniforms of the filter choice and of the final slot of iteration ``iteration``."""
+    c = torch.arange(n_chains, device=key.device, dtype=torch.int64)
+    w = _words(key, iteration, 0, c, 6)
+    return _pf._uniform(w[0]), _pf._uniform(w[1])
+
+
+def draw_path_records(loglik: Tensor, particles: Tensor, ancestors: Tensor, iteration: int, key: Tensor) -> tuple[Tensor, Tensor]:
+    """The path records of the proposals of iteration ``iteration`` (steps 5-7 of the module docstring) from the estimates
+    ``loglik [C, R]`` and the store ``particles [C R, K, N, S]``, ``ancestors [C R, K, N]`` of their filters: ``(anchors [C, K, S],
+    noise_path [C, K])``, the latter int64 holding uint32 values.  A chain whose estimates are all -inf, or hold a NaN, gets a dead
+    record."""
+    C, R = loglik.shape
+    _, K, N, S = particles.shape
+    dev = loglik.device
+    v0, v1 = path_uniforms(C, iteration, key)
+    mx = loglik.max(dim=1, keepdim=True).values
+    dead = ~(mx > float("-inf"))                                         # -inf, or NaN
+    w = torch.exp(loglik - torch.where(dead, torch.zeros_like(mx), mx))
+    w = torch.where(dead | torch.isnan(w), torch.ones_like(w), w)
+    cum = torch.cummax(torch.cumsum(w, dim=1), dim=1).values
+    tau = v0.to(w.dtype)[:, None] * cum[:, -1:]
+    r = torch.searchsorted(cum.contiguous(), tau.contiguous(), right=True).clamp(max=R - 1)[:, 0]
+    m = torch.arange(C, device=dev, dtype=torch.int64) * R + r
+    slot = torch.floor(v1 * N).long().clamp(max=N - 1)                  # the product in fp32, as the kernel forms it
+    anc = ancestors[m].long().clamp(min=0, max=N - 1)                    # [C, K, N]
+    cols = [torch.gather(anc[:, K - 1], 1, slot[:, None])[:, 0]]
+    for k in range(K - 1, 0, -1):
+        cols.append(torch.gather(anc[:, k - 1], 1, cols[-1][:, None])[:, 0])
+    lineage = torch.stack(cols[::-1], dim=1)                             # [C, K]
+    anchors = torch.gather(particles[m], 2, lineage[:, :, None, None].expand(C, K, 1, S))[:, :, 0]
+    noise = m[:, None] * N + lineage
+    return (torch.where(dead[:, :, None], torch.full_like(anchors, float("nan")), anchors),
+            torch.where(dead, torch.full_like(noise, DEAD_PATH), noise))
+
+
+def _record_normals(paths: Tensor, block: int, state_dim: int, keys: Tensor) -> Tensor:
+    """``particle_filter.stream_normals`` for the path indices ``paths [B]`` (int64), record b under its own key ``keys[b]``:
+    float64 ``[B, S, 4]``."""
+    dev = paths.device
+    k = keys.to(torch.int64) & 0xFFFFFFFF
+    i = torch.arange(state_dim, device=dev, dtype=torch.int64)[None, :]
+    blk = torch.full((1, 1), int(block), device=dev, dtype=torch.int64)
+    w = _pf.philox4x32_10(blk, i, paths[:, None], torch.zeros_like(blk), k[:, 0:1], k[:, 1:2])
+    out = []
+    for wa, wb in ((w[0], w[1]), (w[2], w[3])):
+        r = torch.sqrt(-2.0 * torch.log(_pf._uniform(wa).double()))
+        ang = 2.0 * math.pi * _pf._uniform(wb).double()
+        out += [r * torch.cos(ang), r * torch.sin(ang)]
+    return torch.stack(out, dim=-1)
+
+
+def replay_path_records(sde, obs, like, theta: Tensor, x0: Tensor, anchors: Tensor, noise_path: Tensor, keys: Tensor, dt: float,
+                        pos: Sequence[int], bridge: bool) -> Tensor:
+    """Step 9 of the module docstring in torch: ``paths [B, T+1, S]`` of the records ``(theta [B, P], x0 [B, S], anchors [B, K, S],
+    noise_path [B, K] int64, keys [B, 2])``, the steps of ``particle_smoother``'s torch replay."""
+    from ..core.euler_maruyama import _floor_vector
+    dev, dtype = theta.device, theta.dtype
+    B, K, S = anchors.shape
+    rows = torch.round(obs.times / dt).long().tolist()
+    T = rows[-1]
+    dead = noise_path[:, -1] == DEAD_PATH
+    noise = torch.where(dead[:, None], torch.zeros_like(noise_path), noise_path)
+    start = torch.where(dead[:, None, None], torch.zeros_like(anchors), anchors)
+    floor = _floor_vector(list(pos), S, dev, dtype) if pos else None
+    root_dt = dt ** 0.5
+    H = like.obs_matrix if bridge else None
+    H = None if H is None else H.to(device=dev, dtype=dtype)
+    paths = torch.empty(B, T + 1, S, device=dev, dtype=dtype)
+    paths[:, 0] = x0
+    row_prev = 0
+    for k in range(K):
+        if rows[k] == row_prev:
+            continue
+        x = x0 if k == 0 else start[:, k - 1]
+        z, z_block = None, -1
+        for t in range(row_prev, rows[k]):
+            if t // 4 != z_block:
+                z_block = t // 4
+                z = _record_normals(noise[:, k], z_block, S, keys).to(dtype)
+            if bridge:
+                x, _ = _pf._bridge_step(sde, x, theta, z[..., t % 4], obs.values[k].to(dtype), H, float(like.variance), rows[k] - t, dt,
+                                        root_dt)
+            else:
+                shock = torch.einsum("bij,bj->bi", sde.diffusion(x, theta), z[..., t % 4])
+                x = x + sde.drift(x, theta) * dt + shock * root_dt
+            if floor is not None:
+                x = torch.maximum(x, floor)
+            paths[:, t + 1] = x
+        row_prev = rows[k]
+    return torch.where(dead[:, None, None], torch.full_like(paths, float("nan")), paths)
 
 
 def log_mean_exp(loglik: Tensor) -> Tensor:
@@ -195,7 +335,11 @@ def adapted_scale_tril(u_history: Tensor, current: Tensor) -> Tensor:
 
 def _validate(sde, observations, observation_likelihood, initial_theta, time_step, n_iterations, warmup, n_particles,
               filters_per_chain, thin, theta_positive_dims, initial_state, proposal, proposal_scale_tril, step_size, target_accept,
-              adapt_interval):
+              adapt_interval, return_paths=False, path_thin=1, estimator=None):
+    if path_thin < 1:
+        raise ValueError(f"path_thin must be >= 1, got {path_thin}")
+    if return_paths and estimator is not None:
+        raise ValueError("return_paths=True needs the particle filter's store: it cannot be combined with _estimator")
     if proposal not in _pf.PROPOSALS:
         raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
     if proposal == "bridge" and not isinstance(observation_likelihood, GaussianObservationLikelihood):
@@ -243,8 +387,8 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
                   thin: int = 1, theta_positive_dims: Sequence[int] = (), positive_dims: Sequence[int] = (),
                   initial_state: Optional[Tensor] = None, proposal: str = "bootstrap", proposal_scale_tril: Optional[Tensor] = None,
                   step_size: Optional[float] = None, adapt: bool = True, target_accept: float = DEFAULT_TARGET_ACCEPT,
-                  adapt_interval: int = 25, key: Optional[Tensor] = None, _estimator=None, _trace: Optional[list] = None
-                  ) -> ParticleMCMCResult:
+                  adapt_interval: int = 25, key: Optional[Tensor] = None, return_paths: bool = False, path_thin: int = 1,
+                  _estimator=None, _trace: Optional[list] = None) -> ParticleMCMCResult:
     """``C`` independent PMMH chains, one per row of ``initial_theta [C, P]``, run in lock-step for ``n_iterations`` iterations of
     which the first ``warmup`` adapt and are dropped; every ``thin``-th state after them is kept (the module docstring has the
     rule).  ``prior``: the package's ``Prior`` or any object with ``log_prob(theta [C, P])``; ``theta_positive_dims``: the dims of
@@ -253,10 +397,12 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
     ``filters_per_chain``: independent filters averaged per proposal; ``proposal_scale_tril``, ``step_size``: the random walk
     ``u' = u + step_size L z`` (defaults in the module docstring); ``adapt``: whether L is re-estimated once in warm-up (the step size
     adapts in warm-up either way); ``key``: two int32 words (default: drawn from torch's generator on theta's device).  The same key
-    gives the same chains.  No gradients."""
+    gives the same chains.  ``return_paths``: every ``path_thin``-th kept state also gets the latent path accepted with it (the
+    ``paths`` fields of the result; ``path_thin >= 1``); the theta chain is the same with and without.  No gradients."""
     theta0, x0, mask, pos_theta = _validate(sde, observations, observation_likelihood, initial_theta, time_step, n_iterations, warmup,
                                             n_particles, filters_per_chain, thin, theta_positive_dims, initial_state, proposal,
-                                            proposal_scale_tril, step_size, target_accept, adapt_interval)
+                                            proposal_scale_tril, step_size, target_accept, adapt_interval, return_paths, path_thin,
+                                            _estimator)
     dev, dtype = theta0.device, theta0.dtype
     C, P = theta0.shape
     R = int(filters_per_chain)
@@ -280,14 +426,15 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
                    pos_theta=pos_theta, pos_state=tuple(positive_dims), n_iterations=int(n_iterations), warmup=int(warmup),
                    N=int(n_particles), R=R, thin=int(thin), proposal=proposal, L=L,
                    step=float(step_size) if step_size is not None else 2.38 / math.sqrt(P), adapt=bool(adapt) and C > P,
-                   target_accept=float(target_accept), interval=int(adapt_interval), key=key, estimator=_estimator, trace=_trace)
+                   target_accept=float(target_accept), interval=int(adapt_interval), key=key, estimator=_estimator, trace=_trace,
+                   path_thin=int(path_thin) if return_paths else 0)
         route = None
         if HIP_MCMC and _estimator is None and theta0.is_cuda and dtype == torch.float32 and type(prior) is Prior and prior.dim == P:
             from .. import _hip
             if P <= _hip.PMMH_MAX_PARAMS:
                 route = _pf._kernel_route(sde, obs, observation_likelihood, theta0.repeat_interleave(R, dim=0), int(n_particles), proposal)
         out = _torch_loop(**run) if route is None else _kernel_loop(route, **run)
-        return _result(*out, mask)
+        return _result(*out[:7], mask, *out[7:])
 
 
 def _adaptation(i, warmup, interval, adapt):
@@ -296,7 +443,7 @@ def _adaptation(i, warmup, interval, adapt):
 
 
 def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n_iterations, warmup, N, R, thin, proposal, L, step,
-                adapt, target_accept, interval, key, estimator, trace):
+                adapt, target_accept, interval, key, estimator, trace, path_thin=0):
     dev, dtype = u0.device, u0.dtype
     C, P = u0.shape
     cur_u = u0.clone()
@@ -310,6 +457,14 @@ def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n
     n_dead = torch.zeros((), device=dev, dtype=torch.int64)
     w4, w2 = warmup // 4, warmup // 2
     history = torch.empty(max(w2 - w4, 0), C, P, device=dev, dtype=dtype) if adapt else None
+    if path_thin:
+        K, S = obs.values.shape[0], x0.shape[1]
+        n_path = (n_keep + path_thin - 1) // path_thin
+        cur_anchor = torch.full((C, K, S), float("nan"), device=dev, dtype=dtype)
+        cur_noise = torch.full((C, K), DEAD_PATH, device=dev, dtype=torch.int64)
+        cur_iter = torch.full((C,), -1, device=dev, dtype=torch.int32)
+        anchor_rows, noise_rows = torch.empty(n_path, C, K, S, device=dev, dtype=dtype), torch.empty(n_path, C, K, device=dev, dtype=torch.int64)
+        iter_rows = torch.empty(n_path, C, device=dev, dtype=torch.int32)
     for i in range(n_iterations):
         if _ITERATION_HOOK is not None:
             _ITERATION_HOOK(i)
@@ -328,31 +483,49 @@ def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n
         if estimator is not None:
             loglik = estimator(rows, i, fkey)
         else:
-            loglik = _pf.particle_filter(sde, obs, like, rows, dt, n_particles=N, initial_state=x0, positive_dims=pos_state, key=fkey,
-                                         proposal=proposal).log_likelihood
+            filtered = _pf.particle_filter(sde, obs, like, rows, dt, n_particles=N, initial_state=x0, positive_dims=pos_state, key=fkey,
+                                           proposal=proposal, return_particles=bool(path_thin))
+            loglik = filtered.log_likelihood
         loglik = loglik.to(dtype).reshape(C, R)
         n_dead += torch.isneginf(loglik).all(dim=1).sum()
         cur_u, cur_t, cur_ll, acc = _close(i, key, loglik, prop_u, prop_lp, cur_u, cur_t, cur_ll)
+        if path_thin:
+            prop_anchor, prop_noise = draw_path_records(loglik, filtered.particles, filtered.ancestors, i, key)
+            cur_anchor = torch.where(acc[:, None, None], prop_anchor.to(dtype), cur_anchor)
+            cur_noise = torch.where(acc[:, None], prop_noise, cur_noise)
+            cur_iter = torch.where(acc, torch.full_like(cur_iter, i), cur_iter)
         window += acc.sum()
         if i >= warmup:
             kept_acc += acc
             if (i - warmup) % thin == 0:
                 k = (i - warmup) // thin
                 samples[k], lls[k], tgts[k] = constrain(cur_u, mask), cur_ll, cur_t
+                if path_thin and k % path_thin == 0:
+                    anchor_rows[k // path_thin], noise_rows[k // path_thin], iter_rows[k // path_thin] = cur_anchor, cur_noise, cur_iter
         elif history is not None and w4 <= i < w2:
             history[i - w4] = cur_u
         if trace is not None:
             trace.append(dict(prop_u=prop_u, theta_prop=rows, prop_log_prior=prop_lp, loglik=loglik, accept=acc, cur_u=cur_u,
                               cur_log_target=cur_t, cur_loglik=cur_ll, step_size=step, scale_tril=L, filter_key=fkey))
+            if path_thin:
+                trace[-1].update(cur_anchor=cur_anchor, cur_noise_path=cur_noise, cur_path_iteration=cur_iter)
     rate = kept_acc.to(dtype) / (n_iterations - warmup)
-    return samples, lls, tgts, rate, step, L, n_dead
+    out = samples, lls, tgts, rate, step, L, n_dead
+    if not path_thin:
+        return out
+    B = n_path * C
+    paths = replay_path_records(sde, obs, like, samples[::path_thin].reshape(B, P), x0[::R].repeat(n_path, 1), anchor_rows.reshape(B, K, S),
+                                noise_rows.reshape(B, K), filter_keys(iter_rows.reshape(B), key), dt, pos_state, proposal == "bridge")
+    return out + (paths.reshape(n_path, C, -1, S), torch.where(noise_rows[:, :, -1] == DEAD_PATH, torch.full_like(iter_rows, -1), iter_rows))
 
 
 def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n_iterations, warmup, N, R, thin, proposal, L,
-                 step, adapt, target_accept, interval, key, estimator, trace):
+                 step, adapt, target_accept, interval, key, estimator, trace, path_thin=0):
     """The loop with the step kernel: launch i closes iteration i - 1 and opens iteration i, the filter launch follows.  When the
     step size or L changes before iteration i (warm-up only) the proposal is opened again with the new values: the open half is a
-    pure function of (state, i, key, step size, L)."""
+    pure function of (state, i, key, step size, L).  With paths the filter stores particles and ancestors into two buffers
+    allocated here, launch i draws the records of the chains it accepts from them (the filter launch of iteration i overwrites
+    them only afterwards), and one replay launch after the loop turns the kept records into paths."""
     from .. import _hip
     kind, network = route
     dev = u0.device
@@ -377,9 +550,25 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
     filt = _hip.guided_particle_filter if proposal == "bridge" else _hip.particle_filter
     x0 = x0.contiguous()
     logliks, loglik, window_base, pending = [], None, 0, None
+    store = None
+    if path_thin:
+        K, S = obs.values.shape[0], x0.shape[1]
+        i32 = dict(device=dev, dtype=torch.int32)
+        n_path = (n_keep + path_thin - 1) // path_thin
+        n_steps = int(round(float(obs.times[-1]) / dt))                # read here: nothing is read back once the loop runs
+        store = (torch.empty(C * R, K, N, S, **f32), torch.empty(C * R, K, N, **i32))
+        cur_anchor, cur_noise = torch.full((C, K, S), float("nan"), **f32), torch.full((C, K), -1, **i32)   # all ones: dead
+        cur_iter = torch.full((C,), -1, **i32)
+        anchor_rows, noise_rows, iter_rows = torch.empty(n_path, C, K, S, **f32), torch.empty(n_path, C, K, **i32), torch.empty(n_path, C, **i32)
 
     def step_launch(i, closing, keep=None):
         rows_out = (None, None, None) if keep is None else (samples[keep], lls[keep], tgts[keep])
+        if path_thin:
+            n = keep // path_thin if keep is not None and keep % path_thin == 0 else None
+            record_rows = (None, None, None) if n is None else (anchor_rows[n], noise_rows[n], iter_rows[n])
+            _hip.pmmh_step_paths(i, L_host, step, *prior_args, key, closing, cur_u, cur_t, cur_ll, prop_u, prop_lp, theta_prop, fkey, n_acc,
+                                 *store, cur_anchor, cur_noise, cur_iter, *rows_out, *record_rows)
+            return
         _hip.pmmh_step(i, L_host, step, *prior_args, key, closing, cur_u, cur_t, cur_ll, prop_u, prop_lp, theta_prop, fkey, n_acc,
                        *rows_out)
 
@@ -392,6 +581,8 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
         step_launch(i, loglik, keep)
         if trace is not None and pending is not None:
             pending.update(accept=(n_acc - before) > 0, cur_u=cur_u.clone(), cur_log_target=cur_t.clone(), cur_loglik=cur_ll.clone())
+            if path_thin:
+                pending.update(cur_anchor=cur_anchor.clone(), cur_noise_path=cur_noise.long() & DEAD_PATH, cur_path_iteration=cur_iter.clone())
             trace.append(pending)
         if i == n_iterations:
             break
@@ -410,7 +601,8 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
             step_launch(i, None)                           # open iteration i again with the new step size / L
         if i == warmup:
             n_acc.zero_()
-        out = filt(kind, x0, kernel_theta(network, theta_prop), rows, obs.values, H, term, fkey, dt, N, pos_state, network=network)
+        out = filt(kind, x0, kernel_theta(network, theta_prop), rows, obs.values, H, term, fkey, dt, N, pos_state, network=network,
+                   store=store)
         loglik = out[0].view(C, R)
         logliks.append(loglik)
         if trace is not None:
@@ -418,7 +610,17 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
                            step_size=step, scale_tril=L, filter_key=fkey.clone())
     n_dead = torch.isneginf(torch.stack(logliks)).all(dim=2).sum()
     rate = n_acc.to(torch.float32) / (n_iterations - warmup)
-    return samples, lls, tgts, rate, step, L, n_dead
+    out = samples, lls, tgts, rate, step, L, n_dead
+    if not path_thin:
+        return out
+    B = n_path * C
+    record = (x0[::R].repeat(n_path, 1), kernel_theta(network, samples[::path_thin].reshape(B, P)), rows)
+    tail = (anchor_rows.view(B, K, S), noise_rows.view(B, K), filter_keys(iter_rows.view(B), key), dt, pos_state)
+    if proposal == "bridge":
+        paths = _hip.guided_anchored_replay(kind, *record, obs.values, H, float(like.variance), *tail, network=network, n_steps=n_steps)
+    else:
+        paths = _hip.anchored_replay(kind, *record, *tail, network=network, n_steps=n_steps)
+    return out + (paths.view(n_path, C, -1, S), torch.where(noise_rows[:, :, -1] == -1, torch.full_like(iter_rows, -1), iter_rows))
 
 
 def split_r_hat_and_ess(draws: Tensor) -> tuple[Tensor, Tensor]:
@@ -460,7 +662,30 @@ def split_r_hat_and_ess(draws: Tensor) -> tuple[Tensor, Tensor]:
     return r_hat, torch.where(torch.isfinite(r_hat), ess, nan)
 
 
-def _result(samples, lls, tgts, rate, step, L, n_dead, mask) -> ParticleMCMCResult:
+def _path_fields(paths: Tensor, path_iteration: Tensor) -> dict:
+    """The ``path_*`` fields of the result from ``paths [n_path, C, T+1, S]``: moments and quantiles over the live draws."""
+    from ..posterior.variational_posterior import _QUANTILE_MAX_ELEMENTS, QUANTILE_LEVELS, Quantiles
+    n_path, C, T1, S = paths.shape
+    live = path_iteration >= 0                                           # [n_path, C]
+    flat = paths.reshape(n_path * C, T1 * S)[live.reshape(-1)]
+    nan = torch.full((T1, S), float("nan"), device=paths.device, dtype=paths.dtype)
+    fields = dict(paths=paths, path_iteration=path_iteration, path_mean=nan, path_std=nan, path_mean_standard_error=nan,
+                  path_quantiles=Quantiles(*([nan] * len(QUANTILE_LEVELS))))
+    if flat.shape[0] == 0:
+        return fields
+    levels = torch.tensor(QUANTILE_LEVELS, device=paths.device, dtype=paths.dtype)
+    cols = max(1, _QUANTILE_MAX_ELEMENTS // flat.shape[0])
+    q = torch.cat([torch.quantile(flat[:, c:c + cols], levels, dim=0) for c in range(0, flat.shape[1], cols)], dim=1)
+    fields.update(path_mean=flat.mean(dim=0).reshape(T1, S), path_quantiles=Quantiles(*q.reshape(len(QUANTILE_LEVELS), T1, S).unbind(0)),
+                  path_std=flat.std(dim=0).reshape(T1, S) if flat.shape[0] > 1 else torch.zeros_like(nan))
+    if C > 1:
+        w = live[:, :, None, None].to(paths.dtype)
+        chain_means = torch.where(live[:, :, None, None], paths, torch.zeros_like(paths)).sum(dim=0) / w.sum(dim=0)   # NaN: no live draw
+        fields.update(path_mean_standard_error=chain_means.std(dim=0) / math.sqrt(C))
+    return fields
+
+
+def _result(samples, lls, tgts, rate, step, L, n_dead, mask, paths=None, path_iteration=None) -> ParticleMCMCResult:
     from ..posterior.variational_posterior import QUANTILE_LEVELS, Quantiles
     n_keep, C, P = samples.shape
     flat = samples.reshape(n_keep * C, P)
@@ -472,4 +697,5 @@ def _result(samples, lls, tgts, rate, step, L, n_dead, mask) -> ParticleMCMCResu
         samples=samples, log_likelihood=lls, log_target=tgts, acceptance_rate=rate, mean=flat.mean(dim=0),
         std=flat.std(dim=0) if flat.shape[0] > 1 else torch.zeros_like(nan), quantiles=Quantiles(*torch.quantile(flat, levels, dim=0).unbind(0)),
         mean_standard_error=chain_means.std(dim=0) / math.sqrt(C) if C > 1 else nan, r_hat=r_hat, effective_sample_size=ess,
-        step_size=float(step), proposal_scale_tril=L, n_filters_dead=int(n_dead))
+        step_size=float(step), proposal_scale_tril=L, n_filters_dead=int(n_dead),
+        **({} if paths is None else _path_fields(paths, path_iteration)))

@@ -554,7 +554,7 @@ class VariationalPosterior:
     @torch.no_grad()
     def refine_parameters(self, sde: SDE, observation_likelihood: ObservationLikelihood, n_chains: int = 256,
                           n_iterations: int = 600, warmup: int = 300, n_particles: int = 512, filters_per_chain: int = 1,
-                          thin: int = 1, proposal: str = "bootstrap"):
+                          thin: int = 1, proposal: str = "bootstrap", return_paths: bool = False, path_thin: int = 1):
         """When ``reweight_parameters`` says q(theta) is poor (a small ``effective_sample_size``: a mean-field q cannot follow a
         correlated posterior), this gives something better: ``n_chains`` independent particle-MCMC chains (``particle_mcmc``) started
         at draws of q under the EMA weights, as ``reweight_parameters`` draws them, which sample the exact theta posterior of the
@@ -562,7 +562,9 @@ class VariationalPosterior:
         ``state_space.positive_dims`` as everywhere here; q's positive mask says which dims walk in log space; the initial proposal
         scale is q's own ``exp(log_std)``).  Returns the ``ParticleMCMCResult`` with ``variational_mean`` / ``variational_std``, the
         plain moments of the starting draws, next to the chains' ``mean`` / ``std``; check ``r_hat`` and ``mean_standard_error``
-        before trusting them.  It runs on a CPU posterior too (the torch route) and touches none of ``sample()``'s caches or
+        before trusting them.  ``return_paths=True``: every ``path_thin``-th kept state also gets the latent path accepted with it
+        (``paths [n_path, C, T+1, S]`` and the ``path_*`` fields of the result): exact draws of the path to set beside
+        ``summary().diffusion_path_mean``, where ``smooth_paths`` is an importance sample around q.  It runs on a CPU posterior too (the torch route) and touches none of ``sample()``'s caches or
         graphs."""
         import dataclasses
         from ..inference import particle_mcmc as _mc
@@ -579,7 +581,8 @@ class VariationalPosterior:
         res = _mc.particle_mcmc(sde, self.observations, observation_likelihood, self.prior, self.time_step, theta, n_iterations,
                                 warmup=warmup, n_particles=n_particles, filters_per_chain=filters_per_chain, thin=thin,
                                 theta_positive_dims=q._positive_dims, positive_dims=self.state_space.positive_dims,
-                                initial_state=self.observations.values[0], proposal=proposal, proposal_scale_tril=scale)
+                                initial_state=self.observations.values[0], proposal=proposal, proposal_scale_tril=scale,
+                                return_paths=return_paths, path_thin=path_thin)
         v_std = theta.std(dim=0) if n_chains > 1 else torch.zeros_like(theta[0])
         return dataclasses.replace(res, variational_mean=theta.mean(dim=0), variational_std=v_std)
 
