@@ -839,6 +839,21 @@ int vsde_debug_head_mp(int mode);
 int vsde_head_mfma_range_exceeded(int clear);
 int vsde_profile_elapsed_ms(int which, float *ms);
 
+/* Test hooks: the non-recurrent GEMM stages of the head alone, on operands the caller supplies (no reference counterpart).  Both run
+ * the host code the product entry points run -- the weight packing and the same dispatch -- and nothing of the time loop; all
+ * argument checks come before the first HIP call.  `w` is the head's full weight set (the packing kernel reads every matrix).
+ *   context projection: G[B*T][3H] (fp32, contiguous) = ctx W_ih_l0[:, S:S+C]^T + b_ih_l0; workspace as for vsde_head_forward.
+ *   backward GEMMs: from the pre-activation gradients D4[B][T][L][4][H] (slots dr, du, dn, dc_n), the emission gradients
+ *   DO[B][T][S + S(S+1)/2], paths[B][T+1][S] and acts[B][T][L][5][H] it writes grads->context (context_dtype /
+ *   context_batch_stride as in vsde_head_backward) and the ten weight / bias gradients; grads->x0 and grads->theta are not touched.
+ *   Workspace as for vsde_head_backward. */
+int vsde_debug_head_context_projection(const vsde_head_dims *d, const vsde_context_view *ctx, const vsde_head_weights *w,
+                                       float *G, void *workspace, size_t workspace_bytes, void *stream);
+int vsde_debug_head_backward_gemms(const vsde_head_dims *d, const vsde_context_view *ctx, const float *theta,
+                                   const float *paths, const float *acts, const float *D4, const float *DO,
+                                   const vsde_head_weights *w, const vsde_head_grads *grads, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

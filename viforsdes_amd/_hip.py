@@ -57,6 +57,7 @@ EXPORTS = (
     "vsde_crn_kinetic_count_log_weights", "vsde_count_particle_filter", "vsde_crn_count_particle_filter",
     "vsde_crn_kinetic_count_particle_filter",
     "vsde_profile_enable", "vsde_profile_elapsed_ms", "vsde_debug_force_v1", "vsde_debug_head_mp", "vsde_head_mfma_range_exceeded",
+    "vsde_debug_head_context_projection", "vsde_debug_head_backward_gemms",
     "vsde_ln_modulate_fwd", "vsde_ln_modulate_bwd", "vsde_gated_residual_fwd", "vsde_gated_residual_bwd",
     "vsde_swiglu_fwd", "vsde_swiglu_bwd", "vsde_gate_merge_fwd", "vsde_gate_merge_bwd",
     "vsde_qk_norm_rope_fwd", "vsde_qk_norm_rope_bwd_partials", "vsde_qk_norm_rope_bwd",
@@ -227,12 +228,13 @@ def head_forward(x0, ctx, theta, eps, ws, time_step: float, save: bool, diag_min
 
 
 def head_backward(g_paths, g_means, g_chol, ctx, theta, eps, paths, chol_raw, acts, ws,
-                  time_step: float, diag_min: float = DIAG_MIN, context_grad_out=None):
+                  time_step: float, diag_min: float = DIAG_MIN, context_grad_out=None, workspace=None):
     """-> 13 fp32 gradients in launch_bwd order (reference kernels/backward.py:766-784).
 
     ``context_grad_out``: optional contiguous [B, T+1, C] (f32 or bf16) tensor; the context gradient is then written
     straight into its first T steps (in its dtype) and returned in place of the fp32 [B,T,C] tensor; its last step is
-    the caller's to zero."""
+    the caller's to zero.  ``workspace``: optional uint8 tensor of at least ``head_backward_workspace_bytes`` to run in (tests read the
+    sweep's pre-activation gradients back from it)."""
     lib = load()
     dev = _require_hip(g_paths, g_means, g_chol, ctx, theta, eps, paths, chol_raw, acts, *ws)
     g_paths = _f32c(g_paths); g_means = _f32c(g_means); g_chol = _f32c(g_chol)
@@ -259,7 +261,9 @@ def head_backward(g_paths, g_means, g_chol, ctx, theta, eps, paths, chol_raw, ac
         nbytes = lib.vsde_head_backward_workspace_bytes(ctypes.byref(d))
         if nbytes == 0:
             _raise(-1)
-        wsbuf = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        wsbuf = torch.empty(nbytes, device=dev, dtype=torch.uint8) if workspace is None else workspace
+        if wsbuf.dtype != torch.uint8 or wsbuf.numel() < nbytes or not wsbuf.is_contiguous() or wsbuf.device != dev:
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {nbytes} bytes on the same device")
         rc = lib.vsde_head_backward(
             ctypes.byref(d), _ptr(g_paths), _ptr(g_means), _ptr(g_chol), ctypes.byref(cview), _ptr(theta),
             _ptr(eps), _ptr(paths), _ptr(chol_raw), _ptr(acts), ctypes.byref(wstruct),
@@ -915,6 +919,87 @@ def debug_head_mp(mode: int) -> None:
     """Forward time-stepping kernel for hidden_dim 64 / L <= 2 / state_dim <= 2: 1 = the multi-path MFMA kernel whenever
     applicable, 0 = the four-waves-per-path kernel, -1 = default (VSDE_HEAD_MP, else by batch size)."""
     load().vsde_debug_head_mp(ctypes.c_int(mode))
+
+
+def head_backward_workspace_bytes(B: int, T: int, S: int, P: int, C: int, H: int, L: int) -> int:
+    """Size query of ``vsde_head_backward`` (host only, no GPU needed); 0 = dims the kernels refuse."""
+    return int(load().vsde_head_backward_workspace_bytes(ctypes.byref(_Dims(B, T, S, P, C, H, L))))
+
+
+def head_forward_workspace_bytes(B: int, T: int, S: int, P: int, C: int, H: int, L: int) -> int:
+    return int(load().vsde_head_forward_workspace_bytes(ctypes.byref(_Dims(B, T, S, P, C, H, L))))
+
+
+def debug_head_context_projection(ctx, ws, state_dim: int, param_dim: int):
+    """Test hook: G [B*T, 3H] = ctx W_ih_l0[:, S:S+C]^T + b_ih_l0 through the weight packing and the projection dispatch of
+    ``head_forward`` alone.  ``ctx`` [B, T, C] (f32 / bf16) is passed as the view it is (strides and alignment are what the dispatch
+    looks at); G is pre-filled with NaN."""
+    lib = load()
+    dev = _require_hip(ctx, *ws)
+    if ctx.dtype not in (torch.float32, torch.bfloat16) or ctx.stride(2) != 1:
+        raise ValueError("ctx must be an f32 / bf16 [B, T, C] view with a contiguous last dimension")
+    ctx, cview = context_view(ctx)
+    keep, wstruct = _weights_struct(ws)
+    B, T, C = ctx.shape
+    H = keep[1].shape[1]
+    L = 1 + (keep[4].shape[0] if keep[4].numel() > 0 else 0)
+    if tuple(keep[0].shape) != (3 * H, state_dim + C + param_dim):
+        raise ValueError(f"W_ih_l0 has shape {tuple(keep[0].shape)}, expected {(3 * H, state_dim + C + param_dim)}")
+    d = _Dims(B, T, state_dim, param_dim, C, H, L)
+    with torch.cuda.device(dev):
+        G = torch.full((B * T, 3 * H), float("nan"), device=dev, dtype=torch.float32)
+        nbytes = lib.vsde_head_forward_workspace_bytes(ctypes.byref(d))
+        if nbytes == 0:
+            _raise(-1)
+        wsbuf = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        rc = lib.vsde_debug_head_context_projection(ctypes.byref(d), ctypes.byref(cview), ctypes.byref(wstruct), _ptr(G),
+                                                    _ptr(wsbuf), ctypes.c_size_t(nbytes), _stream(dev))
+    if rc != 0:
+        _raise(rc)
+    return G
+
+
+def debug_head_backward_gemms(ctx, theta, paths, acts, D4, DO, ws, context_grad_out=None):
+    """Test hook: grad_context and the ten weight / bias gradients from GIVEN pre-activation gradients ``D4`` [B, T, L, 4, H] and
+    emission gradients ``DO`` [B, T, NO], through the weight packing, the grad_context dispatch and the grouped weight-gradient
+    launch of ``head_backward`` alone.  -> (context, W_ih_l0, W_hh_l0, b_ih_l0, b_hh_l0, W_ih_stack, W_hh_stack, b_ih_stack,
+    b_hh_stack, out_weight, out_bias), the ones allocated here pre-filled with NaN.  ``context_grad_out`` as in ``head_backward``."""
+    lib = load()
+    dev = _require_hip(ctx, theta, paths, acts, D4, DO, *ws)
+    if ctx.dtype not in (torch.float32, torch.bfloat16) or ctx.stride(2) != 1:
+        raise ValueError("ctx must be an f32 / bf16 [B, T, C] view with a contiguous last dimension")
+    ctx, cview = context_view(ctx)
+    keep, wstruct = _weights_struct(ws)
+    theta, paths, acts, D4, DO = (_f32c(t) for t in (theta, paths, acts, D4, DO))
+    B, T1, S = paths.shape
+    d = _dims(paths[:, 0], ctx, theta, keep)
+    T, C, P, H, L = d.T, d.C, d.P, d.H, d.L
+    NO = S + S * (S + 1) // 2
+    if T1 != T + 1 or tuple(acts.shape) != (B, T, L, 5, H) or tuple(D4.shape) != (B, T, L, 4, H) or tuple(DO.shape) != (B, T, NO):
+        raise ValueError("paths / acts / D4 / DO do not have the shapes [B, T+1, S] / [B, T, L, 5, H] / [B, T, L, 4, H] / [B, T, NO]")
+    with torch.cuda.device(dev):
+        mk = lambda *shape: torch.full(shape, float("nan"), device=dev, dtype=torch.float32)
+        g = [None, mk(B, T, C), None, mk(3 * H, S + C + P), mk(3 * H, H), mk(3 * H), mk(3 * H),
+             mk(L - 1, 3 * H, H), mk(L - 1, 3 * H, H), mk(L - 1, 3 * H), mk(L - 1, 3 * H), mk(NO, H), mk(NO)]
+        cdt, cbs = 0, 0
+        if context_grad_out is not None:
+            o = context_grad_out
+            if (not o.is_contiguous() or o.ndim != 3 or o.shape[0] != B or o.shape[1] < T or o.shape[2] != C
+                    or o.dtype not in (torch.float32, torch.bfloat16) or o.device != dev):
+                raise ValueError("context_grad_out must be a contiguous [B, >=T, C] f32/bf16 tensor on the same device")
+            g[1] = o
+            cdt, cbs = int(o.dtype == torch.bfloat16), o.shape[1] * C
+        gstruct = _Grads(*[_ptr(t) for t in g], cdt, cbs)
+        nbytes = lib.vsde_head_backward_workspace_bytes(ctypes.byref(d))
+        if nbytes == 0:
+            _raise(-1)
+        wsbuf = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        rc = lib.vsde_debug_head_backward_gemms(
+            ctypes.byref(d), ctypes.byref(cview), _ptr(theta), _ptr(paths), _ptr(acts), _ptr(D4), _ptr(DO), ctypes.byref(wstruct),
+            ctypes.byref(gstruct), _ptr(wsbuf), ctypes.c_size_t(nbytes), _stream(dev))
+    if rc != 0:
+        _raise(rc)
+    return tuple(t for t in g if t is not None)
 
 
 def head_mfma_range_exceeded(clear: bool = False) -> bool:

@@ -1608,6 +1608,30 @@ static RowView ctx_rowview(const vsde_context_view *c, int T, int C) {
     return v;
 }
 
+// Weight packing and the hoisted context projection G[B*T][3H] = ctx W_c^T + b_ih0: the head of vsde_head_forward, which
+// vsde_debug_head_context_projection runs alone (G then is the caller's buffer).  `pk` returns the packed images the time loop reads.
+static int context_projection(const vsde_head_dims *d, const vsde_context_view *ctx, const vsde_head_weights *w, const FwdLayout &lay,
+                              char *ws, float *G, int save, PackParams &pk, hipStream_t s) {
+    const int NO = d->S + d->S * (d->S + 1) / 2;
+    pk.S = d->S; pk.P = d->P; pk.C = d->C; pk.H = d->H; pk.L = d->L; pk.NO = NO;
+    pk.W_ih0 = w->W_ih_l0; pk.W_hh0 = w->W_hh_l0; pk.W_ih_st = w->W_ih_stack; pk.W_hh_st = w->W_hh_stack; pk.out_W = w->out_weight;
+    const bool wide = d->H > kHP || NO > kWave;
+    if (!wide) { pk.packF = (float4 *)(ws + lay.packF); pk.packO = (float4 *)(ws + lay.packO); }
+    pk.Wc = (float *)(ws + lay.Wc);
+    if (save) prof_mark(2, 0, s);
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(64), dim3(256), 0, s, pk);
+    VSDE_CHECK_HIP(hipGetLastError());
+
+    if (save) prof_mark(4, 0, s);
+    int rc = proj_fast_path() ? launch_proj_fwd_bf16(ctx_rowview(ctx, d->T, d->C), (int64_t)d->B * d->T, d->C, pk.Wc, d->C, 3 * d->H, w->b_ih_l0, G,
+                                                     3 * d->H, ws + lay.planes, proj_planes_bytes(3 * d->H, d->C), s) : 0;
+    if (rc < 0) return rc;
+    if (rc == 0) rc = launch_gemm_nt(ctx_rowview(ctx, d->T, d->C), d->B * d->T, d->C, pk.Wc, d->C, 3 * d->H, w->b_ih_l0, G, 3 * d->H, s);
+    else rc = 0;
+    if (save) prof_mark(4, 1, s);
+    return rc;
+}
+
 template <int L>
 static int launch_fwd_L(const FwdParams &p, bool save, int grid, int block, size_t lds, hipStream_t s) {
     if (save) {
@@ -1698,23 +1722,8 @@ extern "C" int vsde_head_forward(const vsde_head_dims *d, const float *x0, const
     const int NO = d->S + d->S * (d->S + 1) / 2;
 
     PackParams pk = {};
-    pk.S = d->S; pk.P = d->P; pk.C = d->C; pk.H = d->H; pk.L = d->L; pk.NO = NO;
-    pk.W_ih0 = w->W_ih_l0; pk.W_hh0 = w->W_hh_l0; pk.W_ih_st = w->W_ih_stack; pk.W_hh_st = w->W_hh_stack; pk.out_W = w->out_weight;
-    const bool wide = d->H > kHP || NO > kWave;
-    if (!wide) { pk.packF = (float4 *)(ws + lay.packF); pk.packO = (float4 *)(ws + lay.packO); }
-    pk.Wc = (float *)(ws + lay.Wc);
-    if (save) prof_mark(2, 0, s);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(64), dim3(256), 0, s, pk);
-    VSDE_CHECK_HIP(hipGetLastError());
-
     float *G = (float *)(ws + lay.G);
-    if (save) prof_mark(4, 0, s);
-    rc = proj_fast_path() ? launch_proj_fwd_bf16(ctx_rowview(ctx, d->T, d->C), (int64_t)d->B * d->T, d->C, pk.Wc, d->C, 3 * d->H, w->b_ih_l0, G,
-                                                 3 * d->H, ws + lay.planes, proj_planes_bytes(3 * d->H, d->C), s) : 0;
-    if (rc < 0) return rc;
-    if (rc == 0) rc = launch_gemm_nt(ctx_rowview(ctx, d->T, d->C), d->B * d->T, d->C, pk.Wc, d->C, 3 * d->H, w->b_ih_l0, G, 3 * d->H, s);
-    else rc = 0;
-    if (save) prof_mark(4, 1, s);
+    rc = context_projection(d, ctx, w, lay, ws, G, save, pk, s);
     if (rc) return rc;
 
     FwdParams p = {};
@@ -1877,6 +1886,58 @@ static BwdLayout bwd_layout(const vsde_head_dims *d) {
     o.total = off;
     return o;
 }
+
+static int check_context_grad(const vsde_head_dims *d, const vsde_head_grads *g) {
+    VSDE_CHECK_ARG(g->context_dtype == 0 || g->context_dtype == 1, VSDE_E_BADARG, "grads->context_dtype must be 0 (f32) or 1 (bf16)");
+    VSDE_CHECK_ARG(g->context_batch_stride == 0 || g->context_batch_stride >= (int64_t)d->T * d->C, VSDE_E_BADARG,
+                   "grads->context_batch_stride smaller than T*C");
+    return 0;
+}
+
+// The weight images of the backward: the sweep's packed matrices and WcT, the context block of W_ih_l0 that grad_context multiplies by
+static int pack_backward_weights(const vsde_head_dims *d, const vsde_head_weights *w, const BwdLayout &lay, char *ws, PackParams &pk,
+                                 hipStream_t s) {
+    const int NO = d->S + d->S * (d->S + 1) / 2;
+    pk.S = d->S; pk.P = d->P; pk.C = d->C; pk.H = d->H; pk.L = d->L; pk.NO = NO;
+    pk.W_ih0 = w->W_ih_l0; pk.W_hh0 = w->W_hh_l0; pk.W_ih_st = w->W_ih_stack; pk.W_hh_st = w->W_hh_stack; pk.out_W = w->out_weight;
+    if (!(d->H > kHP || NO > kWave)) pk.packB = (float4 *)(ws + lay.packB);
+    pk.WcT = (float *)(ws + lay.WcT);
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(64), dim3(256), 0, s, pk);
+    VSDE_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// The non-recurrent tail of vsde_head_backward: grad_context and the grouped weight / bias gradients from the pre-activation
+// gradients D4 [B][T][L][4][H] and the emission gradients DO [B][T][NO] (the sweep's, or the caller's in
+// vsde_debug_head_backward_gemms).  WcT is the context block of W_ih_l0 as pack_backward_weights left it.
+static int backward_gemms(const vsde_head_dims *d, const vsde_context_view *ctx, const float *theta, const float *paths,
+                          const float *acts, const float *D4, const float *DO, const float *WcT, const vsde_head_grads *g,
+                          const BwdLayout &lay, char *ws, hipStream_t s) {
+    const int M = d->B * d->T;
+    // grad_context[m][c] = sum_n d_pre0(m, n) W_ih_l0[n][S + c]   (backward.py:550-564)
+    RowView dv; dv.base = D4; dv.batch_stride = (int64_t)d->T * d->L * 4 * d->H; dv.row_stride = (int64_t)d->L * 4 * d->H;
+    dv.rows_per_batch = d->T; dv.shift = 0; dv.col_split = 3 * d->H; dv.col_skip = 0; dv.dtype = 0;
+    int rc = check_context_grad(d, g);
+    if (rc) return rc;
+    prof_mark(5, 0, s);
+    // the grouped weight-gradient reduction below runs after this GEMM on the same stream: its workspace doubles as plane scratch
+    rc = (proj_fast_path() && g->context_dtype == 1)
+             ? launch_proj_bwd_bf16(dv, M, 3 * d->H, WcT, 3 * d->H, d->C, g->context, d->C, g->context_batch_stride ? d->T : 0,
+                                    g->context_batch_stride, ws + lay.tn, lay.total - lay.tn, s) : 0;
+    if (rc < 0) return rc;
+    if (rc == 0) rc = launch_gemm_nt(dv, M, 3 * d->H, WcT, 3 * d->H, d->C, nullptr, g->context, d->C, s,
+                                     g->context_batch_stride ? d->T : 0, g->context_batch_stride, g->context_dtype);
+    else rc = 0;
+    prof_mark(5, 1, s);
+    if (rc) return rc;
+
+    TnProblem pr[kMaxTnProblems];
+    int n = build_tn(d, ctx, theta, paths, acts, D4, DO, g, pr);
+    prof_mark(6, 0, s);
+    rc = launch_tn_grouped(pr, n, M, ws + lay.tn, lay.total - lay.tn, s);
+    prof_mark(6, 1, s);
+    return rc;
+}
 }  // namespace vsde
 
 extern "C" size_t vsde_head_backward_workspace_bytes(const vsde_head_dims *d) {
@@ -1903,16 +1964,12 @@ extern "C" int vsde_head_backward(const vsde_head_dims *d, const float *g_paths,
     VSDE_CHECK_ARG(workspace_bytes >= lay.total, VSDE_E_WORKSPACE, "backward workspace too small: %zu < %zu", workspace_bytes, lay.total);
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    const int NO = d->S + d->S * (d->S + 1) / 2, M = d->B * d->T;
+    const int NO = d->S + d->S * (d->S + 1) / 2;
 
     PackParams pk = {};
-    pk.S = d->S; pk.P = d->P; pk.C = d->C; pk.H = d->H; pk.L = d->L; pk.NO = NO;
-    pk.W_ih0 = w->W_ih_l0; pk.W_hh0 = w->W_hh_l0; pk.W_ih_st = w->W_ih_stack; pk.W_hh_st = w->W_hh_stack; pk.out_W = w->out_weight;
-    if (!(d->H > kHP || NO > kWave)) pk.packB = (float4 *)(ws + lay.packB);
-    pk.WcT = (float *)(ws + lay.WcT);
     prof_mark(3, 0, s);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(64), dim3(256), 0, s, pk);
-    VSDE_CHECK_HIP(hipGetLastError());
+    rc = pack_backward_weights(d, w, lay, ws, pk, s);
+    if (rc) return rc;
 
     BwdParams p = {};
     p.B = d->B; p.T = d->T; p.S = d->S; p.P = d->P; p.C = d->C; p.H = d->H; p.NO = NO; p.ntril = NO - d->S;
@@ -2050,30 +2107,46 @@ extern "C" int vsde_head_backward(const vsde_head_dims *d, const float *g_paths,
     }
     }
     if (rc) return rc;
-
-    // grad_context[m][c] = sum_n d_pre0(m, n) W_ih_l0[n][S + c]   (backward.py:550-564)
-    RowView dv; dv.base = p.D4; dv.batch_stride = (int64_t)d->T * d->L * 4 * d->H; dv.row_stride = (int64_t)d->L * 4 * d->H;
-    dv.rows_per_batch = d->T; dv.shift = 0; dv.col_split = 3 * d->H; dv.col_skip = 0; dv.dtype = 0;
-    VSDE_CHECK_ARG(g->context_dtype == 0 || g->context_dtype == 1, VSDE_E_BADARG, "grads->context_dtype must be 0 (f32) or 1 (bf16)");
-    VSDE_CHECK_ARG(g->context_batch_stride == 0 || g->context_batch_stride >= (int64_t)d->T * d->C, VSDE_E_BADARG,
-                   "grads->context_batch_stride smaller than T*C");
-    prof_mark(5, 0, s);
-    // the grouped weight-gradient reduction below runs after this GEMM on the same stream: its workspace doubles as plane scratch
-    rc = (proj_fast_path() && g->context_dtype == 1)
-             ? launch_proj_bwd_bf16(dv, M, 3 * d->H, pk.WcT, 3 * d->H, d->C, g->context, d->C, g->context_batch_stride ? d->T : 0,
-                                    g->context_batch_stride, ws + lay.tn, lay.total - lay.tn, s) : 0;
-    if (rc < 0) return rc;
-    if (rc == 0) rc = launch_gemm_nt(dv, M, 3 * d->H, pk.WcT, 3 * d->H, d->C, nullptr, g->context, d->C, s,
-                                     g->context_batch_stride ? d->T : 0, g->context_batch_stride, g->context_dtype);
-    else rc = 0;
-    prof_mark(5, 1, s);
-    if (rc) return rc;
-
-    TnProblem pr[kMaxTnProblems];
-    int n = build_tn(d, ctx, theta, paths, acts, p.D4, p.DO, g, pr);
-    prof_mark(6, 0, s);
-    rc = launch_tn_grouped(pr, n, M, ws + lay.tn, lay.total - lay.tn, s);
-    prof_mark(6, 1, s);
+    rc = backward_gemms(d, ctx, theta, paths, acts, p.D4, p.DO, pk.WcT, g, lay, ws, s);
     prof_mark(3, 1, s);
     return rc;
+}
+
+// ---- test hooks: the non-recurrent GEMM stages alone, on the caller's operands (include/vsde_hip.h) ----------------------------
+extern "C" int vsde_debug_head_context_projection(const vsde_head_dims *d, const vsde_context_view *ctx, const vsde_head_weights *w,
+                                                  float *G, void *workspace, size_t workspace_bytes, void *stream) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(ctx && ctx->base && w && w->W_ih_l0 && w->W_hh_l0 && w->b_ih_l0 && w->out_weight && G && workspace, VSDE_E_BADARG,
+                   "NULL argument");
+    VSDE_CHECK_ARG(d->L == 1 || (w->W_ih_stack && w->W_hh_stack), VSDE_E_BADARG, "stacked layer weights are NULL");
+    VSDE_CHECK_ARG(ctx->dtype == VSDE_CTX_F32 || ctx->dtype == VSDE_CTX_BF16, VSDE_E_BADARG, "bad context dtype %d", ctx->dtype);
+    const FwdLayout lay = fwd_layout(d);
+    VSDE_CHECK_ARG(workspace_bytes >= lay.total, VSDE_E_WORKSPACE, "forward workspace too small: %zu < %zu", workspace_bytes, lay.total);
+    PackParams pk = {};
+    return context_projection(d, ctx, w, lay, (char *)workspace, G, 0, pk, (hipStream_t)stream);
+}
+
+extern "C" int vsde_debug_head_backward_gemms(const vsde_head_dims *d, const vsde_context_view *ctx, const float *theta,
+                                              const float *paths, const float *acts, const float *D4, const float *DO,
+                                              const vsde_head_weights *w, const vsde_head_grads *g, void *workspace,
+                                              size_t workspace_bytes, void *stream) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    VSDE_CHECK_ARG(ctx && ctx->base && paths && acts && D4 && DO && w && w->W_ih_l0 && w->W_hh_l0 && w->out_weight && g && workspace,
+                   VSDE_E_BADARG, "NULL argument");
+    VSDE_CHECK_ARG(ctx->dtype == VSDE_CTX_F32 || ctx->dtype == VSDE_CTX_BF16, VSDE_E_BADARG, "bad context dtype %d", ctx->dtype);
+    VSDE_CHECK_ARG(g->context && g->W_ih_l0 && g->W_hh_l0 && g->b_ih_l0 && g->b_hh_l0 && g->out_weight && g->out_bias,
+                   VSDE_E_BADARG, "NULL gradient output");
+    VSDE_CHECK_ARG(d->P == 0 || theta, VSDE_E_BADARG, "theta is NULL");
+    VSDE_CHECK_ARG(d->L == 1 || (w->W_ih_stack && w->W_hh_stack && g->W_ih_stack && g->W_hh_stack && g->b_ih_stack && g->b_hh_stack),
+                   VSDE_E_BADARG, "stacked layer tensors are NULL");
+    rc = check_context_grad(d, g);
+    if (rc) return rc;
+    const BwdLayout lay = bwd_layout(d);
+    VSDE_CHECK_ARG(workspace_bytes >= lay.total, VSDE_E_WORKSPACE, "backward workspace too small: %zu < %zu", workspace_bytes, lay.total);
+    PackParams pk = {};
+    rc = pack_backward_weights(d, w, lay, (char *)workspace, pk, (hipStream_t)stream);
+    if (rc) return rc;
+    return backward_gemms(d, ctx, theta, paths, acts, D4, DO, pk.WcT, g, lay, (char *)workspace, (hipStream_t)stream);
 }
