@@ -819,6 +819,60 @@ int vsde_crn_kinetic_guided_anchored_replay(const vsde_crn_network *net, const v
                                             const uint32_t *noise_path, const uint32_t *keys, double time_step,
                                             const uint8_t *positive_mask_host, float *paths, void *stream);
 
+/* Residual-bridge proposal (proposal = "residual_bridge": Whitaker, Golightly, Boys and Sherlock 2017;
+ * viforsdes_amd/inference/particle_filter.py is the specification): the nine guided entry points above with ONE quantity of the
+ * step replaced.  A particle carries a deterministic companion path eta: at the start of a segment (obs_rows[k-1], or 0, when
+ * there are steps towards observation k) eta = x, and a first pass runs the noise-free Euler scheme eta <- clamp(eta + time_step
+ * f(eta)) over the segment's obs_rows[k] - t0 steps; its end is eta_end.  In the step t -> t + 1 the residual of the guided step
+ * becomes y_k - H (eta_end + (x - eta) + n time_step (f(x) - f(eta))); A, psi, W, m, C, M, eps, x', the clamp and lr are those of
+ * vsde_guided_particle_filter with the same normals; then eta <- clamp(eta + time_step f(eta)).  Same arguments, same checks before
+ * any HIP call, same outputs and the same S <= 4, O <= 4; the particle limit is pf_max_n's residual rule (today the guided one:
+ * 512 at S = 4).  The replays restart every segment from its stored start state, so they form the same eta and repeat the filter's
+ * states bit for bit. */
+int vsde_residual_particle_filter(int kind, int M, int N, int S, int P, int K, int O, const float *x0, const float *theta,
+                                  const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                                  const uint32_t *key, double time_step, const uint8_t *positive_mask_host, float *log_likelihood,
+                                  float *increments, float *ess, float *filtered_mean, float *filtered_std, float *particles,
+                                  int *ancestors, float *log_weights, void *stream);
+int vsde_crn_residual_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const float *x0,
+                                      const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                      double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                      float *log_likelihood, float *increments, float *ess, float *filtered_mean, float *filtered_std,
+                                      float *particles, int *ancestors, float *log_weights, void *stream);
+int vsde_crn_kinetic_residual_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P,
+                                              int K, int O, const float *x0, const float *rates, const int *obs_rows,
+                                              const float *obs_values, const float *obs_matrix, double variance, const uint32_t *key,
+                                              double time_step, const uint8_t *positive_mask_host, float *log_likelihood,
+                                              float *increments, float *ess, float *filtered_mean, float *filtered_std,
+                                              float *particles, int *ancestors, float *log_weights, void *stream);
+int vsde_residual_filter_replay(int kind, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0, const float *theta,
+                                const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                                const uint32_t *key, double time_step, const uint8_t *positive_mask_host, const float *particles,
+                                const int *ancestors, const int *last_slot, float *paths, int *lineage, void *stream);
+int vsde_crn_residual_filter_replay(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, int D, int T, const float *x0,
+                                    const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                    double variance, const uint32_t *key, double time_step, const uint8_t *positive_mask_host,
+                                    const float *particles, const int *ancestors, const int *last_slot, float *paths, int *lineage,
+                                    void *stream);
+int vsde_crn_kinetic_residual_filter_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P, int K,
+                                            int O, int D, int T, const float *x0, const float *rates, const int *obs_rows,
+                                            const float *obs_values, const float *obs_matrix, double variance, const uint32_t *key,
+                                            double time_step, const uint8_t *positive_mask_host, const float *particles,
+                                            const int *ancestors, const int *last_slot, float *paths, int *lineage, void *stream);
+int vsde_residual_anchored_replay(int kind, int B, int S, int P, int K, int O, int T, const float *x0, const float *theta,
+                                  const int *obs_rows, const float *obs_values, const float *obs_matrix, double variance,
+                                  const float *anchors, const uint32_t *noise_path, const uint32_t *keys, double time_step,
+                                  const uint8_t *positive_mask_host, float *paths, void *stream);
+int vsde_crn_residual_anchored_replay(const vsde_crn_network *net, int B, int S, int P, int K, int O, int T, const float *x0,
+                                      const float *theta, const int *obs_rows, const float *obs_values, const float *obs_matrix,
+                                      double variance, const float *anchors, const uint32_t *noise_path, const uint32_t *keys,
+                                      double time_step, const uint8_t *positive_mask_host, float *paths, void *stream);
+int vsde_crn_kinetic_residual_anchored_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int S, int P, int K, int O,
+                                              int T, const float *x0, const float *rates, const int *obs_rows, const float *obs_values,
+                                              const float *obs_matrix, double variance, const float *anchors,
+                                              const uint32_t *noise_path, const uint32_t *keys, double time_step,
+                                              const uint8_t *positive_mask_host, float *paths, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

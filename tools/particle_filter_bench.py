@@ -12,13 +12,14 @@ There is no earlier version of the feature to compare with: the torch route on t
 ``--proposal bridge`` runs the guided filter instead; ``--proposal both`` adds, per case, what the proposal is for: ONE theta (the
 Lotka-Volterra example at the classical values 0.5, 0.0025, 0.3 with its own observation variance 1.0; the SIR case at 0.004, 0.15)
 repeated over ``--m`` filters with one key, so the spread of ``log p^`` over the filters is the estimator's own noise -- its
-standard deviation and the time per kernel launch, for both proposals, and the ratio of the times.
+standard deviation and the time per kernel launch, for both proposals, and the ratio of the times.  ``--proposal residual_bridge``
+runs the residual bridge; ``--proposal all`` is ``both`` with the residual bridge as the third proposal of the noise record.
 
 ``--likelihood poisson`` / ``negbin`` (dispersion ``--dispersion``, default 10) puts a count likelihood on both cases (the
 Lotka-Volterra observations rounded to integers) and runs the count instantiations of the kernel (vsde_count_particle_filter); the
 bridge proposal needs the Gaussian one.  ``--noise`` adds the one-theta record for the bootstrap proposal alone.
 
-    python tools/particle_filter_bench.py [--m 1024] [--n 1024] [--reps 200] [--torch-reps 2] [--proposal bootstrap|bridge|both]
+    python tools/particle_filter_bench.py [--m 1024] [--n 1024] [--reps 200] [--torch-reps 2] [--proposal bootstrap|bridge|residual_bridge|both|all]
                                           [--likelihood gaussian|poisson|negbin] [--dispersion 10] [--noise]"""
 import argparse
 import json
@@ -70,6 +71,8 @@ def noise(sde, obs, like, theta, dt, N, pos, a, proposals=("bootstrap", "bridge"
                          "median_min_particle_ess": round(float(res.effective_sample_size.min(dim=1).values.median()), 1)}
     if "bridge" in out and "bootstrap" in out:
         out["time_ratio_bridge_over_bootstrap"] = round(out["bridge"]["kernel_ms"] / out["bootstrap"]["kernel_ms"], 2)
+    if "residual_bridge" in out and "bootstrap" in out:
+        out["time_ratio_residual_bridge_over_bootstrap"] = round(out["residual_bridge"]["kernel_ms"] / out["bootstrap"]["kernel_ms"], 2)
     return out
 
 
@@ -110,7 +113,7 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--torch-reps", type=int, default=2)
-    ap.add_argument("--proposal", choices=["bootstrap", "bridge", "both"], default="bootstrap")
+    ap.add_argument("--proposal", choices=["bootstrap", "bridge", "residual_bridge", "both", "all"], default="bootstrap")
     ap.add_argument("--likelihood", choices=["gaussian", "poisson", "negbin"], default="gaussian")
     ap.add_argument("--dispersion", type=float, default=10.0)
     ap.add_argument("--noise", action="store_true", help="add the one-theta record for the bootstrap proposal alone")
@@ -133,9 +136,10 @@ def main():
                               else NegativeBinomialObservationLikelihood(dispersion=a.dispersion))
     rec = {"tool": "particle_filter_bench", "device": torch.cuda.get_device_name(DEV), "proposal": a.proposal,
            "likelihood": a.likelihood}
-    if a.proposal == "both":
-        rec["lv_noise"] = noise(lv, lv_obs, lv_like, torch.tensor([[0.5, 0.0025, 0.3]]), lv_dt, a.n, lv_pos, a)
-        rec["sir_noise"] = noise(sir, sir_obs, sir_like, torch.tensor([[0.004, 0.15]]), 0.1, a.n, [0, 1], a)
+    if a.proposal in ("both", "all"):
+        proposals = ("bootstrap", "bridge") + (("residual_bridge",) if a.proposal == "all" else ())
+        rec["lv_noise"] = noise(lv, lv_obs, lv_like, torch.tensor([[0.5, 0.0025, 0.3]]), lv_dt, a.n, lv_pos, a, proposals)
+        rec["sir_noise"] = noise(sir, sir_obs, sir_like, torch.tensor([[0.004, 0.15]]), 0.1, a.n, [0, 1], a, proposals)
     else:
         rec["lv"] = compare(lv, lv_obs, lv_like, lv_th, lv_dt, a.n, lv_pos, a)
         rec["sir"] = compare(sir, sir_obs, sir_like, sir_th, 0.1, a.n, [0, 1], a)

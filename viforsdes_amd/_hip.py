@@ -75,6 +75,9 @@ EXPORTS = (
     "vsde_guided_filter_replay", "vsde_crn_guided_filter_replay", "vsde_crn_kinetic_guided_filter_replay", "vsde_pmmh_step",
     "vsde_pmmh_step_paths", "vsde_anchored_replay", "vsde_crn_anchored_replay", "vsde_crn_kinetic_anchored_replay",
     "vsde_guided_anchored_replay", "vsde_crn_guided_anchored_replay", "vsde_crn_kinetic_guided_anchored_replay",
+    "vsde_residual_particle_filter", "vsde_crn_residual_particle_filter", "vsde_crn_kinetic_residual_particle_filter",
+    "vsde_residual_filter_replay", "vsde_crn_residual_filter_replay", "vsde_crn_kinetic_residual_filter_replay",
+    "vsde_residual_anchored_replay", "vsde_crn_residual_anchored_replay", "vsde_crn_kinetic_residual_anchored_replay",
     "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
@@ -457,16 +460,20 @@ def _observation_term(variance, n_rows: int, dev):
 
 PF_MAX_STATE, PF_MAX_OBS, PF_MAX_PARTICLES = 16, 16, 1024
 PF_GUIDED_MAX_STATE, PF_GUIDED_MAX_OBS = 4, 4
+PF_RESIDUAL_FULL_STATE = 3   # csrc/vsde_filter_step.h: kPfResidualFullS
 
 
 def particle_filter_max_particles(kind: str, state_dim: int, proposal: str = "bootstrap") -> int:
     """The largest ``n_particles`` (a multiple of 64) the filter kernel of a built-in SDE takes (csrc/vsde_filter.hip: pf_max_n):
     1024, and 512 for a reaction network of 5..8 species (its step needs more than the 128 registers of a 1024-thread workgroup).
     ``proposal="bridge"``: the guided step fits those registers up to state_dim 3; at state_dim 4 its instantiations are built
-    for 512 threads: 512."""
-    if proposal not in ("bootstrap", "bridge"):
-        raise ValueError(f"proposal must be 'bootstrap' or 'bridge', got {proposal!r}")
+    for 512 threads: 512.  ``proposal="residual_bridge"``: its own rule (pf_max_n's residual argument), which today gives the
+    bridge's limits: the companion path still fits the 128 registers up to state_dim 3."""
+    if proposal not in ("bootstrap", "bridge", "residual_bridge"):
+        raise ValueError(f"proposal must be 'bootstrap', 'bridge' or 'residual_bridge', got {proposal!r}")
     if proposal == "bridge" and state_dim > 3:
+        return PF_MAX_PARTICLES // 2
+    if proposal == "residual_bridge" and state_dim > PF_RESIDUAL_FULL_STATE:
         return PF_MAX_PARTICLES // 2
     return PF_MAX_PARTICLES // 2 if kind == "reaction_network" and state_dim > 4 else PF_MAX_PARTICLES
 
@@ -533,10 +540,12 @@ def particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, vari
 
 
 def guided_particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, key, time_step: float,
-                           n_particles: int, positive_dims=(), network=None, return_particles: bool = False, store=None):
+                           n_particles: int, positive_dims=(), network=None, return_particles: bool = False, store=None,
+                           residual: bool = False):
     """``particle_filter`` with the bridge proposal (include/vsde_hip.h: vsde_guided_particle_filter; S <= 4, O <= 4): the same
-    arguments, and the same 7 outputs followed by log_weights [M, K, N] or None (None with ``store``)."""
-    return _particle_filter("guided_particle_filter", True, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key,
+    arguments, and the same 7 outputs followed by log_weights [M, K, N] or None (None with ``store``).  ``residual``: the residual
+    bridge (vsde_residual_particle_filter)."""
+    return _particle_filter("residual_particle_filter" if residual else "guided_particle_filter", True, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key,
                             time_step, n_particles, positive_dims, network, return_particles, store)
 
 
@@ -562,7 +571,7 @@ def _filter_replay(entry: str, kind, x0, theta, obs_rows, model, key, time_step,
     T = int(obs_rows[-1]) if n_steps is None and K else int(n_steps or 0)
     obs_values, obs_matrix, variance = model
     O, extra = S, ()
-    if entry.startswith("guided"):
+    if entry.startswith(("guided", "residual")):
         obs_values = _f32c(obs_values)
         obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
         if obs_values.ndim != 2 or obs_values.shape[0] != K or (obs_matrix is not None and tuple(obs_matrix.shape) != (obs_values.shape[1], S)):
@@ -590,10 +599,11 @@ def filter_replay(kind: str, x0, theta, obs_rows, key, time_step: float, particl
 
 
 def guided_filter_replay(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, key, time_step: float, particles,
-                         ancestors, last_slot, positive_dims=(), network=None, n_steps: Optional[int] = None):
+                         ancestors, last_slot, positive_dims=(), network=None, n_steps: Optional[int] = None, residual: bool = False):
     """``filter_replay`` for the stored particles of ``guided_particle_filter`` (vsde_guided_filter_replay; S <= 4, O <= 4): the
-    bridge steps need the observations, obs_matrix and variance of that call as well."""
-    return _filter_replay("guided_filter_replay", kind, x0, theta, obs_rows, (obs_values, obs_matrix, variance), key, time_step,
+    bridge steps need the observations, obs_matrix and variance of that call as well, and its ``residual``
+    (vsde_residual_filter_replay)."""
+    return _filter_replay("residual_filter_replay" if residual else "guided_filter_replay", kind, x0, theta, obs_rows, (obs_values, obs_matrix, variance), key, time_step,
                           particles, ancestors, last_slot, n_steps, positive_dims, network)
 
 
@@ -690,7 +700,7 @@ def _anchored_replay(entry: str, kind, x0, theta, obs_rows, model, anchors, nois
     T = int(obs_rows[-1]) if n_steps is None and K else int(n_steps or 0)
     obs_values, obs_matrix, variance = model
     O, extra = S, ()
-    if entry.startswith("guided"):
+    if entry.startswith(("guided", "residual")):
         obs_values = _f32c(obs_values)
         obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
         if obs_values.ndim != 2 or obs_values.shape[0] != K or (obs_matrix is not None and tuple(obs_matrix.shape) != (obs_values.shape[1], S)):
@@ -715,10 +725,11 @@ def anchored_replay(kind: str, x0, theta, obs_rows, anchors, noise_path, keys, t
 
 
 def guided_anchored_replay(kind: str, x0, theta, obs_rows, obs_values, obs_matrix, variance: float, anchors, noise_path, keys,
-                           time_step: float, positive_dims=(), network=None, n_steps: Optional[int] = None):
+                           time_step: float, positive_dims=(), network=None, n_steps: Optional[int] = None, residual: bool = False):
     """``anchored_replay`` for records drawn from ``guided_particle_filter`` launches (vsde_guided_anchored_replay; S <= 4, O <= 4):
-    the bridge steps need the observations, obs_matrix and variance of those launches as well."""
-    return _anchored_replay("guided_anchored_replay", kind, x0, theta, obs_rows, (obs_values, obs_matrix, variance), anchors,
+    the bridge steps need the observations, obs_matrix and variance of those launches as well, and their ``residual``
+    (vsde_residual_anchored_replay)."""
+    return _anchored_replay("residual_anchored_replay" if residual else "guided_anchored_replay", kind, x0, theta, obs_rows, (obs_values, obs_matrix, variance), anchors,
                             noise_path, keys, time_step, n_steps, positive_dims, network)
 
 

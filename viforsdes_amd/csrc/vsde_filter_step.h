@@ -1,8 +1,8 @@
 // What the particle-filter translation units share (gfx950): the limits and the argument block of the filter kernels, the
 // propagation of one particle between two observations (pf_propagate: Euler-Maruyama; pf_propagate_guided: the modified-diffusion-
-// bridge step of the guided filter) with a store hook, and the host helpers that fill the argument block.  vsde_filter.hip (the
-// filter and the replay of its genealogy) and vsde_anchored.hip (the replay of carried path records) include it, so the three
-// kernels run one step code.
+// bridge step of the guided filter, and with RES its residual form) with a store hook, and the host helpers that fill the
+// argument block.  vsde_filter_kernels.h builds the three kernels on it (the filter, the replay of its genealogy, the replay of
+// carried path records), so they run one step code.
 #pragma once
 #include "vsde_sde_step.h"
 
@@ -10,14 +10,17 @@ namespace vsde {
 
 constexpr int kPfMaxN = 1024, kPfWaves = kPfMaxN / kWave, kPfMaxS = 16, kPfMaxO = 16;
 constexpr int kPfRed = kPfWaves * (kPfMaxS + 2);   // floats of the reduction stage
+constexpr int kPfResidualFullS = 3;   // the largest state dim whose residual-bridge instantiations fit a 1024-thread workgroup
 
 // Particles per filter an instantiation is built for.  A 1024-thread workgroup leaves 128 VGPRs per lane; the reaction-network step
 // at 5..8 species (its S x S covariance and Cholesky factor in registers) needs more, so those instantiations are built for 512
 // threads (256 VGPRs) and refuse a larger N rather than spill.
 // The guided step (A, psi, W, C and their factors next to f and G) fits the 128 VGPRs up to S = 3 (at most 122); at S = 4 it
 // would spill (12..68 bytes of scratch per lane), so the guided S = 4 instantiations are 512-thread ones too.
-constexpr int pf_max_n(int kind, int S, bool guided = false) {
-    return (kind == 4 && S > 4) || (guided && S > 3) ? kPfMaxN / 2 : kPfMaxN;
+// The residual variant of the guided step carries eta and eta_end, and f(eta) within a step (3 S floats), on top of that: up to
+// S = kPfResidualFullS it still fits (at most 127), so today its rule is the guided one; the argument keeps the two apart.
+constexpr int pf_max_n(int kind, int S, bool guided = false, bool residual = false) {
+    return (kind == 4 && S > 4) || (guided && S > 3) || (residual && S > kPfResidualFullS) ? kPfMaxN / 2 : kPfMaxN;
 }
 
 constexpr int kPfGuidedMaxS = 4, kPfGuidedMaxO = 4;
@@ -121,14 +124,41 @@ template <int N, bool FLOOR> __device__ __forceinline__ void pf_chol(float *a, f
     }
 }
 
+// the drift alone, f(x) [NS] (the residual bridge's deterministic path): the coefficient functions with the diffusion factor left to
+// the compiler to drop
+template <int KIND, int NS, int NR, bool KIN>
+__device__ __forceinline__ void pf_drift(const PfParams &p, const float *x, const float *th, float *f) {
+    if constexpr (KIND == 3) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) f[i] = -th[i] * x[i];
+    } else {
+        [[maybe_unused]] float G[NS * NS];
+        if constexpr (KIND == 4) crn_drift_cov<NS, NR, KIN>(p.net, x, th, f, G);
+        else coef_fwd<KIND>(x, th, f, G);
+    }
+}
+
+// eta <- clamp(eta + dt f): one noise-free Euler step with the state's own clamp
+template <int NS> __device__ __forceinline__ void pf_ode_step(const PfParams &p, float *eta, const float *f) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const float y = eta[i] + f[i] * p.dt;
+        eta[i] = ((p.pos_mask >> i) & 1u) ? floor_nan(y) : y;
+    }
+}
+
 // One guided Euler step (modified diffusion bridge) of a particle at x towards the observation yk that is nleft grid steps ahead:
 // A = sqrt(dt) H G, psi = nleft A A^T + var I = R R^T, W = R^-1 A, r = R^-1 (yk - H (x + nleft dt f)), m = W^T r, C = I - W^T W =
 // M M^T (floored pivots), eps = m + M z, x <- clamp(x + f dt + sqrt(dt) G eps), lr += -|eps|^2 / 2 + |z|^2 / 2 + sum log M_jj.
 // Rows o >= O of A, psi and the residual are exact zeros (psi_oo = var), so they add nothing.  th: kinds 1, 2, 4 as em_load_theta /
 // crn_load_rates leave it; kind 3: th[i] = a_i, th[NS + i] = softplus(b_i) + 1e-3
-template <int KIND, int NS, int NR, bool KIN, int NO>
+// RES (the residual bridge): the predicted endpoint x + nleft dt f is replaced by eta_end + (x - eta) + nleft dt (f - f(eta)) with
+// eta the noise-free Euler path from the segment's start state and eta_end its end at the observation's row; eta then takes its
+// own step with the f(eta) already formed.  Everything else is the same code.
+template <int KIND, int NS, int NR, bool KIN, int NO, bool RES = false>
 __device__ __forceinline__ void pf_bridge_step(const PfParams &p, float *x, const float *th, const float *z, const float *yk,
-                                               float nleft, float &lr) {
+                                               float nleft, float &lr, [[maybe_unused]] float *eta = nullptr,
+                                               [[maybe_unused]] const float *eta_end = nullptr) {
     float f[NS], G[NS * NS];
     if constexpr (KIND == 4) {
         crn_coef<NS, NR, KIN>(p.net, x, th, f, G);
@@ -143,6 +173,14 @@ __device__ __forceinline__ void pf_bridge_step(const PfParams &p, float *x, cons
         coef_fwd<KIND>(x, th, f, G);
     }
     const float ndt = nleft * p.dt;
+    [[maybe_unused]] float ahead[NS];   // RES: the predicted state at the observation's row
+    if constexpr (RES) {
+        float fe[NS];
+        pf_drift<KIND, NS, NR, KIN>(p, eta, th, fe);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) ahead[i] = eta_end[i] + (x[i] - eta[i]) + ndt * (f[i] - fe[i]);
+        pf_ode_step<NS>(p, eta, fe);
+    }
     float A[NO * NS], e[NO];
 #pragma unroll
     for (int o = 0; o < NO; ++o) {
@@ -155,7 +193,8 @@ __device__ __forceinline__ void pf_bridge_step(const PfParams &p, float *x, cons
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
                     const float h = p.obs_matrix[o * NS + k];
-                    pred += h * (x[k] + ndt * f[k]);
+                    if constexpr (RES) pred += h * ahead[k];
+                    else pred += h * (x[k] + ndt * f[k]);
 #pragma unroll
                     for (int i = 0; i <= k; ++i) A[o * NS + i] += h * G[k * NS + i];
                 }
@@ -163,7 +202,8 @@ __device__ __forceinline__ void pf_bridge_step(const PfParams &p, float *x, cons
 #pragma unroll
                 for (int i = 0; i < NS; ++i)
                     if (i <= o && o < NS) A[o * NS + i] = G[(o < NS ? o : 0) * NS + i];
-                pred = x[o < NS ? o : 0] + ndt * f[o < NS ? o : 0];
+                if constexpr (RES) pred = ahead[o < NS ? o : 0];
+                else pred = x[o < NS ? o : 0] + ndt * f[o < NS ? o : 0];
             }
 #pragma unroll
             for (int i = 0; i < NS; ++i) A[o * NS + i] *= p.sqdt;
@@ -230,10 +270,21 @@ __device__ __forceinline__ void pf_bridge_step(const PfParams &p, float *x, cons
     for (int i = 0; i < NS; ++i) x[i] = f[i];
 }
 
-// guided steps t0 .. t1 - 1 of one particle towards the observation yk at grid row t1
-template <int KIND, int NS, int NR, bool KIN, int NO, class ST = PfNoStore>
+// guided steps t0 .. t1 - 1 of one particle towards the observation yk at grid row t1.  RES: the segment opens with the noise-free
+// Euler pass from x over its t1 - t0 steps (drift only), whose end eta_end and running state eta stay in registers
+template <int KIND, int NS, int NR, bool KIN, int NO, bool RES = false, class ST = PfNoStore>
 __device__ __forceinline__ void pf_propagate_guided(const PfParams &p, float *x, const float *th, int t0, int t1, uint32_t b,
                                                     uint32_t k0, uint32_t k1, const float *yk, float &lr, ST st = ST()) {
+    [[maybe_unused]] float eta[NS], eta_end[NS];
+    if constexpr (RES) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) eta[i] = eta_end[i] = x[i];
+        for (int t = t0; t < t1; ++t) {
+            float fe[NS];
+            pf_drift<KIND, NS, NR, KIN>(p, eta_end, th, fe);
+            pf_ode_step<NS>(p, eta_end, fe);
+        }
+    }
     for (int blk = t0 >> 2; blk <= (t1 - 1) >> 2; ++blk) {
         float z[NS][4];
 #pragma unroll
@@ -245,7 +296,8 @@ __device__ __forceinline__ void pf_propagate_guided(const PfParams &p, float *x,
                 float zq[NS];
 #pragma unroll
                 for (int i = 0; i < NS; ++i) zq[i] = z[i][q];
-                pf_bridge_step<KIND, NS, NR, KIN, NO>(p, x, th, zq, yk, (float)(t1 - t), lr);
+                if constexpr (RES) pf_bridge_step<KIND, NS, NR, KIN, NO, true>(p, x, th, zq, yk, (float)(t1 - t), lr, eta, eta_end);
+                else pf_bridge_step<KIND, NS, NR, KIN, NO>(p, x, th, zq, yk, (float)(t1 - t), lr);
 #pragma unroll
                 for (int i = 0; i < NS; ++i) st(t, i, x[i]);
             }

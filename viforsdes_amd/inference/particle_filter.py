@@ -50,7 +50,25 @@ At observation k ``lw_j = lr_j + log p(y_k | x_j)`` (NaN counts as -inf) and eve
 ``lw``; ``lr`` is zero after every observation, so later observations on the same grid row get the plain Gaussian weight.  For n = 1
 the step ratio plus the observation term is ``log N(y; H (x + f D), D H L L^T H^T + v I)`` whatever z is (the fully adapted filter).
 The kernel takes the bridge for built-in SDEs with S <= 4 and O <= 4 (``_hip.particle_filter_max_particles(kind, S, proposal)``
-particles at most); everything else runs the torch route."""
+particles at most); everything else runs the torch route.
+
+``proposal="residual_bridge"`` (the residual bridge of Whitaker, Golightly, Boys and Sherlock 2017) is the bridge with ONE quantity
+replaced, for gaps over which the drift turns: the bridge's predicted state at the observation's row, ``x + n D f(x)``, extrapolates
+the drift at x linearly over all n steps that are left, which across an oscillation of a nonlinear model points nowhere near the
+path.  The residual bridge carries a deterministic companion path eta per particle and extrapolates only the difference from it:
+
+* at the start of every segment (row 0, and the row of observation k - 1 after resampling, when there are steps towards observation
+  k) ``eta <- x``, and a first pass runs the noise-free Euler scheme from x over the segment's ``n0 = rows[k] - t0`` steps,
+  ``eta <- clamp(eta + D f(eta, theta))`` with the state's own clamp; its result is ``eta_end``, nothing else of the pass is kept;
+* at every step of the segment, with ``f_eta = f(eta, theta)``:  ``e = y_k - H (eta_end + (x - eta) + n D (f(x) - f_eta))``;
+  A, psi, R, W, r, m, C, M, eps, x', the clamp and ``lr`` are the bridge's, with the same normals;
+* after the step ``eta <- clamp(eta + D f_eta)``.
+
+eta and eta_end are deterministic functions of the segment's start state and theta, and the proposal is still a Gaussian in noise
+space with the same M for the draw and its density, so the weights and the unbiasedness are the bridge's.  At the last step of a
+segment eta + D f_eta = eta_end, so the predicted state is ``x + D f(x)`` in exact arithmetic whenever eta's clamp does not bind on
+that step, and the fully adapted n = 1 identity above holds under that condition.  Same requirements, same kernel coverage and the
+same normals as the bridge."""
 from __future__ import annotations
 
 import math
@@ -66,7 +84,7 @@ from ..core.observations import COUNT_LIKELIHOODS, GaussianObservationLikelihood
 from ..core.sde import SDE, builtin_sde_route, kernel_theta
 
 HIP_FILTER = True   # set False to force the torch route (A/B tests)
-PROPOSALS = ("bootstrap", "bridge")
+PROPOSALS = ("bootstrap", "bridge", "residual_bridge")
 BRIDGE_PIVOT_FLOOR = 1e-6   # floor of the pivots of C = I - A^T psi^-1 A before their square root (csrc/vsde_filter.hip: kPfPivotFloor)
 
 _M0, _M1, _W0, _W1, _MASK = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xFFFFFFFF
@@ -188,13 +206,13 @@ def particle_filter(sde: SDE, observations: Observations, observation_likelihood
     started at ``initial_state`` (``[S]`` or ``[M, S]``; default: the first observation).  The observation at the start row counts
     like any other, so ``log_likelihood`` targets what ``VariationalPosterior.log_evidence`` conditions on.  ``key``: two int32
     words (a tensor); default: drawn from torch's generator on theta's device, so ``torch.manual_seed`` makes the call repeatable
-    and a call captured in a HIP graph draws a fresh key per replay.  ``proposal``: "bootstrap", or "bridge" for the guided filter
-    of the module docstring.  No gradients."""
+    and a call captured in a HIP graph draws a fresh key per replay.  ``proposal``: "bootstrap", or "bridge" / "residual_bridge" for
+    the guided filters of the module docstring.  No gradients."""
     if proposal not in PROPOSALS:
         raise ValueError(f"proposal must be one of {PROPOSALS}, got {proposal!r}")
-    bridge = proposal == "bridge"
+    bridge, residual = proposal != "bootstrap", proposal == "residual_bridge"
     if bridge and not isinstance(observation_likelihood, GaussianObservationLikelihood):
-        raise ValueError("proposal='bridge' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
+        raise ValueError(f"proposal='{proposal}' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
                          f"variance (got {type(observation_likelihood).__name__})")
     theta, x0 = _validate(sde, observations, theta, time_step, n_particles, initial_state)
     dev = theta.device
@@ -219,12 +237,13 @@ def particle_filter(sde: SDE, observations: Observations, observation_likelihood
             args = (kind, x0, kernel_theta(network, theta), rows, obs.values, None if H is None else H.to(theta), term, key.to(torch.int32) if key.dtype != torch.int32 else key,
                     float(time_step), n_particles, pos)
             if bridge:
-                return ParticleFilterResult(*_hip.guided_particle_filter(*args, network=network, return_particles=return_particles))
+                return ParticleFilterResult(*_hip.guided_particle_filter(*args, network=network, return_particles=return_particles,
+                                                                         residual=residual))
             out = _hip.particle_filter(*args, network=network, return_particles=return_particles)
             lw = _gaussian_log_weights(observation_likelihood, obs.values, out[5]) if return_particles else None
             return ParticleFilterResult(*out, lw)
         return _torch_filter(sde, obs, observation_likelihood, theta, float(time_step), n_particles, x0, pos, return_particles, key,
-                             bridge)
+                             bridge, residual)
 
 
 def _gaussian_log_weights(like, values, particles):
@@ -250,7 +269,7 @@ def _kernel_route(sde, obs, like, theta, n_particles, proposal="bootstrap"):
     S, O, H = int(sde.state_dim), obs.values.shape[1], like.obs_matrix
     if S > _hip.PF_MAX_STATE or O > _hip.PF_MAX_OBS or (H is None and O != S) or (H is not None and tuple(H.shape) != (O, S)):
         return None
-    if proposal == "bridge" and (S > _hip.PF_GUIDED_MAX_STATE or O > _hip.PF_GUIDED_MAX_OBS):
+    if proposal != "bootstrap" and (S > _hip.PF_GUIDED_MAX_STATE or O > _hip.PF_GUIDED_MAX_OBS):
         return None
     if n_particles % 64 != 0 or n_particles > _hip.particle_filter_max_particles(kind, S, proposal=proposal):
         return None
@@ -273,11 +292,16 @@ def _floored_cholesky(a: Tensor, floor: Optional[float] = None) -> Tensor:
     return out
 
 
-def _bridge_step(sde, x, th, z, y, H, variance, n, dt, root_dt):
-    """One guided Euler step of the module docstring: (x' before the clamp [B, S], the step's log-ratio [B])."""
+def _bridge_step(sde, x, th, z, y, H, variance, n, dt, root_dt, residual=None):
+    """One guided Euler step of the module docstring: (x' before the clamp [B, S], the step's log-ratio [B]).  ``residual``: (eta,
+    f(eta), eta_end) of the residual bridge, each [B, S]."""
     f, L = sde.drift(x, th), sde.diffusion(x, th)
     A = root_dt * (L if H is None else torch.einsum("ok,bki->boi", H, L))
-    ahead = x + (n * dt) * f
+    if residual is None:
+        ahead = x + (n * dt) * f
+    else:
+        eta, f_eta, eta_end = residual
+        ahead = eta_end + (x - eta) + (n * dt) * (f - f_eta)
     e = y[None, :] - (ahead if H is None else ahead @ H.T)
     O = A.shape[1]
     psi = n * (A @ A.transpose(1, 2)) + variance * torch.eye(O, device=x.device, dtype=x.dtype)
@@ -292,7 +316,20 @@ def _bridge_step(sde, x, th, z, y, H, variance, n, dt, root_dt):
     return x + f * dt + torch.einsum("bij,bj->bi", L, eps) * root_dt, lr
 
 
-def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, bridge=False) -> ParticleFilterResult:
+def _ode_step(eta, f_eta, dt, floor):
+    """One noise-free Euler step of the residual bridge's companion path, with the state's own clamp."""
+    eta = eta + f_eta * dt
+    return eta if floor is None else torch.maximum(eta, floor)
+
+
+def _ode_endpoint(sde, x, th, n_steps, dt, floor):
+    """``eta_end``: the companion path ``n_steps`` steps after a segment's start state x (the first pass of the residual bridge)."""
+    for _ in range(n_steps):
+        x = _ode_step(x, sde.drift(x, th), dt, floor)
+    return x
+
+
+def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, bridge=False, residual=False) -> ParticleFilterResult:
     dev, dtype = theta.device, theta.dtype
     M, P = theta.shape
     S = x0.shape[1]
@@ -310,14 +347,19 @@ def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, 
     H = None if H is None else H.to(device=dev, dtype=dtype)
     lr = torch.zeros(M * N, device=dev, dtype=dtype) if bridge else None
     for k in range(K):
+        if residual and t < rows[k]:
+            eta, eta_end = x, _ode_endpoint(sde, x, th, rows[k] - t, dt, floor)
         while t < rows[k]:
             if t // 4 != z_block:
                 z_block = t // 4
                 z = stream_normals(M * N, z_block, S, key).to(dtype)
             if bridge:
+                f_eta = sde.drift(eta, th) if residual else None
                 x, step_lr = _bridge_step(sde, x, th, z[..., t % 4], obs.values[k].to(dtype), H, float(like.variance), rows[k] - t,
-                                          dt, root_dt)
+                                          dt, root_dt, (eta, f_eta, eta_end) if residual else None)
                 lr = lr + step_lr
+                if residual:
+                    eta = _ode_step(eta, f_eta, dt, floor)
             else:
                 shock = torch.einsum("bij,bj->bi", sde.diffusion(x, th), z[..., t % 4])
                 x = x + sde.drift(x, th) * dt + shock * root_dt

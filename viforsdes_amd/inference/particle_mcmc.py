@@ -64,7 +64,8 @@ recomputed at the end).  With ``N`` particles, ``K`` observations at the grid ro
 9. after the loop every kept record is replayed as in ``particle_smoother``: segment k, the grid steps ``rows[k-1] .. rows[k] - 1``
    (segment 0 from step 0 and ``x0[c]``), starts at ``anchors[k-1]``, takes the normals of path ``noise_path[k]`` under the key
    ``fkey_{path_iteration}`` and the theta of the kept state, and runs the filter's step (Euler-Maruyama, or the bridge step towards
-   ``y_k`` for ``proposal="bridge"``, then the 1e-6 clamp).  The state after step t goes to ``paths[.., t + 1]``, ``paths[.., 0] =
+   ``y_k`` for ``proposal="bridge"`` / ``"residual_bridge"``, the latter with its companion path started at the anchor, then the
+   1e-6 clamp).  The state after step t goes to ``paths[.., t + 1]``, ``paths[.., 0] =
    x0[c]``; a dead record (a chain that never reached a finite target) gives NaN paths and ``path_iteration`` -1.
 
 With ``return_paths=False`` nothing of this happens: no store, no launch, no random number.
@@ -82,6 +83,7 @@ from __future__ import annotations
 import math
 from collections.abc import Sequence
 from dataclasses import dataclass
+from functools import partial
 from typing import Any, Optional
 
 import torch
@@ -116,7 +118,7 @@ class ParticleMCMCResult:
       NaN when fewer than 4 states were kept;
     * ``step_size``, ``proposal_scale_tril [P, P]``: the final values (what the kept chain ran with);
     * ``n_filters_dead``: proposals (over the whole run, warm-up included) whose every filter returned -inf -- many of them
-      means the filter, not the chain, is the problem: more particles, or ``proposal="bridge"``;
+      means the filter, not the chain, is the problem: more particles, or ``proposal="bridge"`` / ``"residual_bridge"``;
     * ``variational_mean`` / ``variational_std [P]``: plain moments of the q draws the chains started from
       (``refine_parameters`` only, else None);
     * with ``return_paths=True`` (else None): ``paths [n_path, C, T+1, S]``: the latent path of every ``path_thin``-th kept state
@@ -240,7 +242,7 @@ def _record_normals(paths: Tensor, block: int, state_dim: int, keys: Tensor) -> 
 
 
 def replay_path_records(sde, obs, like, theta: Tensor, x0: Tensor, anchors: Tensor, noise_path: Tensor, keys: Tensor, dt: float,
-                        pos: Sequence[int], bridge: bool) -> Tensor:
+                        pos: Sequence[int], bridge: bool, residual: bool = False) -> Tensor:
     """Step 9 of the module docstring in torch: ``paths [B, T+1, S]`` of the records ``(theta [B, P], x0 [B, S], anchors [B, K, S],
     noise_path [B, K] int64, keys [B, 2])``, the steps of ``particle_smoother``'s torch replay."""
     from ..core.euler_maruyama import _floor_vector
@@ -263,13 +265,19 @@ def replay_path_records(sde, obs, like, theta: Tensor, x0: Tensor, anchors: Tens
             continue
         x = x0 if k == 0 else start[:, k - 1]
         z, z_block = None, -1
+        if residual:
+            # the segment restarts from its anchor, so eta and eta_end are the filter's
+            eta, eta_end = x, _pf._ode_endpoint(sde, x, theta, rows[k] - row_prev, dt, floor)
         for t in range(row_prev, rows[k]):
             if t // 4 != z_block:
                 z_block = t // 4
                 z = _record_normals(noise[:, k], z_block, S, keys).to(dtype)
             if bridge:
+                f_eta = sde.drift(eta, theta) if residual else None
                 x, _ = _pf._bridge_step(sde, x, theta, z[..., t % 4], obs.values[k].to(dtype), H, float(like.variance), rows[k] - t, dt,
-                                        root_dt)
+                                        root_dt, (eta, f_eta, eta_end) if residual else None)
+                if residual:
+                    eta = _pf._ode_step(eta, f_eta, dt, floor)
             else:
                 shock = torch.einsum("bij,bj->bi", sde.diffusion(x, theta), z[..., t % 4])
                 x = x + sde.drift(x, theta) * dt + shock * root_dt
@@ -342,8 +350,8 @@ def _validate(sde, observations, observation_likelihood, initial_theta, time_ste
         raise ValueError("return_paths=True needs the particle filter's store: it cannot be combined with _estimator")
     if proposal not in _pf.PROPOSALS:
         raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
-    if proposal == "bridge" and not isinstance(observation_likelihood, GaussianObservationLikelihood):
-        raise ValueError("proposal='bridge' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
+    if proposal != "bootstrap" and not isinstance(observation_likelihood, GaussianObservationLikelihood):
+        raise ValueError(f"proposal='{proposal}' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
                          f"variance (got {type(observation_likelihood).__name__})")
     if thin < 1 or adapt_interval < 1 or filters_per_chain < 1:
         raise ValueError(f"thin, adapt_interval and filters_per_chain must be >= 1 (got {thin}, {adapt_interval}, {filters_per_chain})")
@@ -515,7 +523,8 @@ def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n
         return out
     B = n_path * C
     paths = replay_path_records(sde, obs, like, samples[::path_thin].reshape(B, P), x0[::R].repeat(n_path, 1), anchor_rows.reshape(B, K, S),
-                                noise_rows.reshape(B, K), filter_keys(iter_rows.reshape(B), key), dt, pos_state, proposal == "bridge")
+                                noise_rows.reshape(B, K), filter_keys(iter_rows.reshape(B), key), dt, pos_state, proposal != "bootstrap",
+                                proposal == "residual_bridge")
     return out + (paths.reshape(n_path, C, -1, S), torch.where(noise_rows[:, :, -1] == DEAD_PATH, torch.full_like(iter_rows, -1), iter_rows))
 
 
@@ -547,7 +556,9 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
     rows = torch.round(obs.times / dt).to(torch.int32)
     term = like.kernel_terms(obs.values) if type(like) in COUNT_LIKELIHOODS else float(like.variance)
     H = None if H is None else H.to(u0)
-    filt = _hip.guided_particle_filter if proposal == "bridge" else _hip.particle_filter
+    filt = _hip.particle_filter
+    if proposal != "bootstrap":
+        filt = partial(_hip.guided_particle_filter, residual=proposal == "residual_bridge")
     x0 = x0.contiguous()
     logliks, loglik, window_base, pending = [], None, 0, None
     store = None
@@ -616,8 +627,9 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
     B = n_path * C
     record = (x0[::R].repeat(n_path, 1), kernel_theta(network, samples[::path_thin].reshape(B, P)), rows)
     tail = (anchor_rows.view(B, K, S), noise_rows.view(B, K), filter_keys(iter_rows.view(B), key), dt, pos_state)
-    if proposal == "bridge":
-        paths = _hip.guided_anchored_replay(kind, *record, obs.values, H, float(like.variance), *tail, network=network, n_steps=n_steps)
+    if proposal != "bootstrap":
+        paths = _hip.guided_anchored_replay(kind, *record, obs.values, H, float(like.variance), *tail, network=network, n_steps=n_steps,
+                                            residual=proposal == "residual_bridge")
     else:
         paths = _hip.anchored_replay(kind, *record, *tail, network=network, n_steps=n_steps)
     return out + (paths.view(n_path, C, -1, S), torch.where(noise_rows[:, :, -1] == -1, torch.full_like(iter_rows, -1), iter_rows))

@@ -22,12 +22,13 @@ The rule, for filter ``m`` (``D = n_draws``, ``N = n_particles``, ``rows`` the g
 * replay: segment k covers the global grid steps ``rows[k-1] .. rows[k] - 1`` (segment 0: ``0 .. rows[0] - 1``, from ``x0[m]``).  For
   k >= 1 it starts at ``X[m, k-1, lineage[m, d, k-1]]``; its noise is that of path ``b = m N + lineage[m, d, k]`` (a slot keeps its
   own stream across resampling); its step is the filter's (Euler-Maruyama, or the bridge step towards ``y_k`` with
-  ``n = rows[k] - t`` for ``proposal="bridge"``, then the 1e-6 clamp of the positive dims).  The state after step t goes to
+  ``n = rows[k] - t`` for ``proposal="bridge"`` / ``"residual_bridge"``, then the 1e-6 clamp of the positive dims; the residual
+  bridge's companion path eta starts at the segment's stored start state, as in the filter).  The state after step t goes to
   ``paths[m, d, t+1]``, ``paths[m, d, 0] = x0[m]``; a zero-length segment (observations sharing a row) writes nothing;
 * a filter with ``log_likelihood[m] = -inf`` (some observation left no positive weight) has no smoothing sample: lineage -1, paths
   NaN, ``distinct_lineages`` 0.
 
-Under ``proposal="bridge"`` the draws are still draws of the model's smoothing distribution: the filter's weights carry the ratio
+Under ``proposal="bridge"`` or ``"residual_bridge"`` the draws are still draws of the model's smoothing distribution: the filter's weights carry the ratio
 model / proposal.
 
 The torch code below is the specification and runs anywhere.  Where ``particle_filter`` takes its kernel route (built-in SDEs and
@@ -110,9 +111,9 @@ def particle_smoother(sde: SDE, observations: Observations, observation_likeliho
     share ancestors (see ``SmoothedPaths.distinct_lineages``); draws of different filters are independent.  No gradients."""
     if proposal not in _pf.PROPOSALS:
         raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
-    bridge = proposal == "bridge"
+    bridge, residual = proposal != "bootstrap", proposal == "residual_bridge"
     if bridge and not isinstance(observation_likelihood, GaussianObservationLikelihood):
-        raise ValueError("proposal='bridge' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
+        raise ValueError(f"proposal='{proposal}' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
                          f"variance (got {type(observation_likelihood).__name__})")
     if n_draws < 1:
         raise ValueError(f"n_draws must be >= 1, got {n_draws}")
@@ -149,14 +150,15 @@ def particle_smoother(sde: SDE, observations: Observations, observation_likeliho
                 H = observation_likelihood.obs_matrix
                 paths, lineage = _hip.guided_filter_replay(kind, x0, th, rows, obs.values, None if H is None else H.to(theta),
                                                            float(observation_likelihood.variance), key32, float(time_step),
-                                                           res.particles, res.ancestors, last, pos, network=network)
+                                                           res.particles, res.ancestors, last, pos, network=network,
+                                                           residual=residual)
             else:
                 paths, lineage = _hip.filter_replay(kind, x0, th, rows, key32, float(time_step), res.particles, res.ancestors, last,
                                                     pos, network=network)
         else:
             lineage = _trace(res.ancestors, last)
             paths = _torch_replay(sde, obs, observation_likelihood, theta, float(time_step), x0, pos, key, bridge, res.particles,
-                                  lineage, rows.tolist())
+                                  lineage, rows.tolist(), residual)
         srt = torch.sort(lineage, dim=1).values
         distinct = 1 + (srt[:, 1:] != srt[:, :-1]).sum(dim=1)
         distinct = torch.where(dead[:, None], torch.zeros_like(distinct), distinct)
@@ -176,7 +178,7 @@ def _trace(ancestors: Tensor, last: Tensor) -> Tensor:
     return torch.stack(cols[::-1], dim=2).to(torch.int32)
 
 
-def _torch_replay(sde, obs, like, theta, dt, x0, pos, key, bridge, particles, lineage, rows) -> Tensor:
+def _torch_replay(sde, obs, like, theta, dt, x0, pos, key, bridge, particles, lineage, rows, residual=False) -> Tensor:
     dev, dtype = theta.device, theta.dtype
     M, P = theta.shape
     _, D, K = lineage.shape
@@ -203,13 +205,19 @@ def _torch_replay(sde, obs, like, theta, dt, x0, pos, key, bridge, particles, li
             x = torch.gather(particles[:, k - 1], 1, slot[:, :, k - 1, None].expand(-1, -1, S)).reshape(M * D, S)
         b = (base + slot[:, :, k]).reshape(M * D)
         z, z_block = None, -1
+        if residual:
+            # the segment restarts from its stored start state, so eta and eta_end are the filter's
+            eta, eta_end = x, _pf._ode_endpoint(sde, x, th, rows[k] - row_prev, dt, floor)
         for t in range(row_prev, rows[k]):
             if t // 4 != z_block:
                 z_block = t // 4
                 z = _path_normals(b, z_block, S, key).to(dtype)
             if bridge:
+                f_eta = sde.drift(eta, th) if residual else None
                 x, _ = _pf._bridge_step(sde, x, th, z[..., t % 4], obs.values[k].to(dtype), H, float(like.variance), rows[k] - t, dt,
-                                        root_dt)
+                                        root_dt, (eta, f_eta, eta_end) if residual else None)
+                if residual:
+                    eta = _pf._ode_step(eta, f_eta, dt, floor)
             else:
                 shock = torch.einsum("bij,bj->bi", sde.diffusion(x, th), z[..., t % 4])
                 x = x + sde.drift(x, th) * dt + shock * root_dt

@@ -438,7 +438,8 @@ class VariationalPosterior:
         ``filter_effective_sample_size.min()`` of a bootstrap run is near 1 -- the observations are then too informative for a
         proposal that does not look at them, and ``log p^`` too noisy for the weights to mean much.  The bridge extrapolates the
         drift linearly to the next observation: it pays when observations are a few steps apart or the drift changes little between
-        them, not across a long gap of a strongly nonlinear model (compare ``filter_effective_sample_size`` of the two)."""
+        them, not across a long gap of a strongly nonlinear model (compare ``filter_effective_sample_size`` of the two); there
+        ``"residual_bridge"`` (the same step around the noise-free Euler path of the segment) is the one to try."""
         from ..inference import particle_filter as _pf
         if proposal not in _pf.PROPOSALS:
             raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
