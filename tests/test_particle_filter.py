@@ -206,6 +206,17 @@ def test_noise_stream_and_uniforms_are_the_specified_ones():
     assert diff <= max(1, total // 1000)
 
 
+def test_path_normals_of_given_paths_and_per_row_keys_are_rows_of_the_stream():
+    from viforsdes_amd.inference import particle_filter as pf
+    key, S = _key(*KEY), 3
+    paths = torch.tensor([130, 7, 191, 0, 64, 65, 7], dtype=torch.int64)      # a permuted subset, one index twice
+    for block in (0, 5):
+        want = pf.stream_normals(192, block, S, key)
+        assert want.shape == (192, S, 4) and want.dtype == torch.float64 and bool(torch.isfinite(want).all())
+        assert torch.equal(pf.path_normals(paths, block, S, key), want[paths])
+        assert torch.equal(pf.path_normals(paths, block, S, key.expand(len(paths), 2)), want[paths])
+
+
 def test_validation():
     from viforsdes_amd import particle_filter
     from viforsdes_amd.examples.sdes import LinearDiagonalSDE

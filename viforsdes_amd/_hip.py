@@ -549,13 +549,31 @@ def guided_particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matri
                             time_step, n_particles, positive_dims, network, return_particles, store)
 
 
-def _filter_replay(entry: str, kind, x0, theta, obs_rows, model, key, time_step, particles, ancestors, last_slot, n_steps,
-                   positive_dims, network):
+def _replay_inputs(who: str, obs_rows, words_ok: bool, words: str, guided: bool, model, state_dim: int):
+    """What the two replays check alike: obs_rows is an int32 [K] tensor and the caller's integer words are what ``words`` says
+    (``words_ok``); then, for a guided form, the observation model (obs_values [K, O], obs_matrix [O, S] or None, variance) of the
+    filter launches.  Returns (O, the entry point's extra arguments, the fp32 casts they point into: the caller holds them until
+    the launch is queued)."""
+    if obs_rows.dtype != torch.int32 or obs_rows.ndim != 1 or not words_ok:
+        raise ValueError(f"{who}: obs_rows must be an int32 [K] tensor{words}")
+    if not guided:
+        return state_dim, (), None
+    obs_values, obs_matrix, variance = model
+    obs_values = _f32c(obs_values)
+    obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
+    if obs_values.ndim != 2 or obs_values.shape[0] != obs_rows.shape[0] \
+            or (obs_matrix is not None and tuple(obs_matrix.shape) != (obs_values.shape[1], state_dim)):
+        raise ValueError(f"{who}: obs_values [{obs_rows.shape[0]}, O] and obs_matrix [O, {state_dim}] expected")
+    return obs_values.shape[1], (_ptr(obs_values), _ptr(obs_matrix), ctypes.c_double(variance)), (obs_values, obs_matrix)
+
+
+def _filter_replay(entry: str, guided: bool, kind, x0, theta, obs_rows, model, key, time_step, particles, ancestors, last_slot,
+                   n_steps, positive_dims, network):
     lib = load()
     dev = _require_hip(x0, theta, obs_rows, key, particles, ancestors, last_slot, *model[:2])
     x0, theta, particles = _f32c(x0), _f32c(theta), _f32c(particles)
-    if obs_rows.dtype != torch.int32 or obs_rows.ndim != 1 or key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2:
-        raise ValueError("filter_replay: obs_rows must be an int32 [K] tensor and key two int32 words")
+    O, extra, held = _replay_inputs("filter_replay", obs_rows, key.dtype in (torch.int32, torch.uint32) and key.numel() == 2,
+                                    " and key two int32 words", guided, model, x0.shape[-1])
     if ancestors.dtype != torch.int32 or last_slot.dtype != torch.int32:
         raise ValueError("filter_replay: ancestors and last_slot must be int32 tensors")
     obs_rows, key, ancestors, last_slot = obs_rows.contiguous(), key.contiguous(), ancestors.contiguous(), last_slot.contiguous()
@@ -569,14 +587,6 @@ def _filter_replay(entry: str, kind, x0, theta, obs_rows, model, key, time_step,
     M, S = x0.shape
     N, D = particles.shape[2], last_slot.shape[1]
     T = int(obs_rows[-1]) if n_steps is None and K else int(n_steps or 0)
-    obs_values, obs_matrix, variance = model
-    O, extra = S, ()
-    if entry.startswith(("guided", "residual")):
-        obs_values = _f32c(obs_values)
-        obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
-        if obs_values.ndim != 2 or obs_values.shape[0] != K or (obs_matrix is not None and tuple(obs_matrix.shape) != (obs_values.shape[1], S)):
-            raise ValueError(f"filter_replay: obs_values [{K}, O] and obs_matrix [O, {S}] expected")
-        O, extra = obs_values.shape[1], (_ptr(obs_values), _ptr(obs_matrix), ctypes.c_double(variance))
     with torch.cuda.device(dev):
         ok = D >= 1 and T >= 0    # bad sizes are the entry point's to refuse: allocate nothing for them
         paths = torch.empty(M, D, T + 1, S, device=dev, dtype=torch.float32) if ok else None
@@ -594,7 +604,7 @@ def filter_replay(kind: str, x0, theta, obs_rows, key, time_step: float, particl
     key, time_step, positive_dims and network as given to ``particle_filter``, its particles [M, K, N, S] and ancestors [M, K, N],
     and last_slot [M, D] (int32; -1: no sample), the slot of each draw at the last observation.  ``n_steps``: obs_rows[K-1] when
     the caller knows it (saves reading it back from the device).  Returns (paths [M, D, T+1, S], lineage [M, D, K] int32)."""
-    return _filter_replay("filter_replay", kind, x0, theta, obs_rows, (None, None, None), key, time_step, particles, ancestors,
+    return _filter_replay("filter_replay", False, kind, x0, theta, obs_rows, (None, None, None), key, time_step, particles, ancestors,
                           last_slot, n_steps, positive_dims, network)
 
 
@@ -603,8 +613,9 @@ def guided_filter_replay(kind: str, x0, theta, obs_rows, obs_values, obs_matrix,
     """``filter_replay`` for the stored particles of ``guided_particle_filter`` (vsde_guided_filter_replay; S <= 4, O <= 4): the
     bridge steps need the observations, obs_matrix and variance of that call as well, and its ``residual``
     (vsde_residual_filter_replay)."""
-    return _filter_replay("residual_filter_replay" if residual else "guided_filter_replay", kind, x0, theta, obs_rows, (obs_values, obs_matrix, variance), key, time_step,
-                          particles, ancestors, last_slot, n_steps, positive_dims, network)
+    return _filter_replay("residual_filter_replay" if residual else "guided_filter_replay", True, kind, x0, theta, obs_rows,
+                          (obs_values, obs_matrix, variance), key, time_step, particles, ancestors, last_slot, n_steps, positive_dims,
+                          network)
 
 
 PMMH_MAX_PARAMS = 16
@@ -681,14 +692,14 @@ def pmmh_step_paths(iteration: int, scale_tril, step_size: float, prior_type: in
               _paths=(particles, ancestors, cur_anchor, cur_noise_path, cur_path_iteration, anchor_row, noise_row, iteration_row))
 
 
-def _anchored_replay(entry: str, kind, x0, theta, obs_rows, model, anchors, noise_path, keys, time_step, n_steps, positive_dims,
-                     network):
+def _anchored_replay(entry: str, guided: bool, kind, x0, theta, obs_rows, model, anchors, noise_path, keys, time_step, n_steps,
+                     positive_dims, network):
     lib = load()
     dev = _require_hip(x0, theta, obs_rows, anchors, noise_path, keys, *model[:2])
     x0, theta, anchors = _f32c(x0), _f32c(theta), _f32c(anchors)
     ints = (torch.int32, torch.uint32)
-    if obs_rows.dtype != torch.int32 or obs_rows.ndim != 1 or noise_path.dtype not in ints or keys.dtype not in ints:
-        raise ValueError("anchored_replay: obs_rows must be an int32 [K] tensor, noise_path [B, K] and keys [B, 2] int32 tensors")
+    O, extra, held = _replay_inputs("anchored_replay", obs_rows, noise_path.dtype in ints and keys.dtype in ints,
+                                    ", noise_path [B, K] and keys [B, 2] int32 tensors", guided, model, x0.shape[-1])
     obs_rows, noise_path, keys = obs_rows.contiguous(), noise_path.contiguous(), keys.contiguous()
     K = obs_rows.shape[0]
     if x0.ndim != 2 or theta.ndim != 2 or theta.shape[0] != x0.shape[0] or tuple(anchors.shape) != (x0.shape[0], K, x0.shape[1]) \
@@ -698,14 +709,6 @@ def _anchored_replay(entry: str, kind, x0, theta, obs_rows, model, anchors, nois
                          f"{tuple(noise_path.shape)}, {tuple(keys.shape)}")
     B, S = x0.shape
     T = int(obs_rows[-1]) if n_steps is None and K else int(n_steps or 0)
-    obs_values, obs_matrix, variance = model
-    O, extra = S, ()
-    if entry.startswith(("guided", "residual")):
-        obs_values = _f32c(obs_values)
-        obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
-        if obs_values.ndim != 2 or obs_values.shape[0] != K or (obs_matrix is not None and tuple(obs_matrix.shape) != (obs_values.shape[1], S)):
-            raise ValueError(f"anchored_replay: obs_values [{K}, O] and obs_matrix [O, {S}] expected")
-        O, extra = obs_values.shape[1], (_ptr(obs_values), _ptr(obs_matrix), ctypes.c_double(variance))
     with torch.cuda.device(dev):
         paths = torch.empty(B, T + 1, S, device=dev, dtype=torch.float32) if T >= 0 else None   # a bad T is the entry point's to refuse
         _call(*_sde_entry(lib, entry, kind, network), ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(theta.shape[1]), ctypes.c_int(K),
@@ -720,7 +723,7 @@ def anchored_replay(kind: str, x0, theta, obs_rows, anchors, noise_path, keys, t
     state x0 [B, S], theta [B, P] (the effective constants for a CrnKineticRoute), anchors [B, K, S], noise_path [B, K] and filter
     key keys [B, 2] (int32); ``kind``, obs_rows, time_step, positive_dims and network as given to the filter launches the records
     were drawn from.  ``n_steps``: obs_rows[K-1] when the caller knows it (saves reading it back from the device)."""
-    return _anchored_replay("anchored_replay", kind, x0, theta, obs_rows, (None, None, None), anchors, noise_path, keys, time_step,
+    return _anchored_replay("anchored_replay", False, kind, x0, theta, obs_rows, (None, None, None), anchors, noise_path, keys, time_step,
                             n_steps, positive_dims, network)
 
 
@@ -729,8 +732,8 @@ def guided_anchored_replay(kind: str, x0, theta, obs_rows, obs_values, obs_matri
     """``anchored_replay`` for records drawn from ``guided_particle_filter`` launches (vsde_guided_anchored_replay; S <= 4, O <= 4):
     the bridge steps need the observations, obs_matrix and variance of those launches as well, and their ``residual``
     (vsde_residual_anchored_replay)."""
-    return _anchored_replay("residual_anchored_replay" if residual else "guided_anchored_replay", kind, x0, theta, obs_rows, (obs_values, obs_matrix, variance), anchors,
-                            noise_path, keys, time_step, n_steps, positive_dims, network)
+    return _anchored_replay("residual_anchored_replay" if residual else "guided_anchored_replay", True, kind, x0, theta, obs_rows,
+                            (obs_values, obs_matrix, variance), anchors, noise_path, keys, time_step, n_steps, positive_dims, network)
 
 
 def _tail_args(x_obs, obs_values, obs_matrix, variance, theta, prior_type, prior_mean, prior_std, post_mean, post_log_std, theta_positive_dims):

@@ -135,21 +135,31 @@ def _key_words(key: Tensor) -> tuple[Tensor, Tensor]:
     return k[0], k[1]
 
 
-def stream_normals(n_paths: int, block: int, state_dim: int, key: Tensor) -> Tensor:
-    """The stream's normals of grid steps ``4 block .. 4 block + 3`` for paths ``0 .. n_paths - 1``: float64 ``[n_paths, S, 4]``
-    (Box-Muller on the word pairs (w0, w1), (w2, w3); u in fp32, log / sqrt / cos / sin in float64)."""
-    dev = key.device
-    k0, k1 = _key_words(key)
-    b = torch.arange(n_paths, device=dev, dtype=torch.int64)[:, None]
-    i = torch.arange(state_dim, device=dev, dtype=torch.int64)[None, :]
-    blk = torch.full((1, 1), int(block), device=dev, dtype=torch.int64)
-    w = philox4x32_10(blk, i, b, torch.zeros_like(blk), k0, k1)
+def _box_muller(w: Sequence[Tensor]) -> Tensor:
+    """Four normals per counter (float64, on a new last dim) from the four Philox words: Box-Muller on the word pairs (w0, w1),
+    (w2, w3); u in fp32, log / sqrt / cos / sin in float64."""
     out = []
     for wa, wb in ((w[0], w[1]), (w[2], w[3])):
         r = torch.sqrt(-2.0 * torch.log(_uniform(wa).double()))
         ang = 2.0 * math.pi * _uniform(wb).double()
         out += [r * torch.cos(ang), r * torch.sin(ang)]
     return torch.stack(out, dim=-1)
+
+
+def path_normals(paths: Tensor, block: int, state_dim: int, key: Tensor) -> Tensor:
+    """The stream's normals of grid steps ``4 block .. 4 block + 3`` for the path indices ``paths [B]`` (int64) under ``key``, two
+    words ``[2]`` for all paths or ``[B, 2]``, path b under ``key[b]``: float64 ``[B, S, 4]`` (``_box_muller`` of
+    ``philox4x32_10({block, i, path, 0}, key)``)."""
+    dev = paths.device
+    k = key.to(torch.int64) & _MASK
+    i = torch.arange(state_dim, device=dev, dtype=torch.int64)[None, :]
+    blk = torch.full((1, 1), int(block), device=dev, dtype=torch.int64)
+    return _box_muller(philox4x32_10(blk, i, paths[:, None], torch.zeros_like(blk), k[..., 0:1], k[..., 1:2]))
+
+
+def stream_normals(n_paths: int, block: int, state_dim: int, key: Tensor) -> Tensor:
+    """``path_normals`` for paths ``0 .. n_paths - 1``: float64 ``[n_paths, S, 4]``."""
+    return path_normals(torch.arange(n_paths, device=key.device, dtype=torch.int64), block, state_dim, key)
 
 
 def resampling_uniforms(n_filters: int, k: int, key: Tensor) -> Tensor:
@@ -208,42 +218,65 @@ def particle_filter(sde: SDE, observations: Observations, observation_likelihood
     words (a tensor); default: drawn from torch's generator on theta's device, so ``torch.manual_seed`` makes the call repeatable
     and a call captured in a HIP graph draws a fresh key per replay.  ``proposal``: "bootstrap", or "bridge" / "residual_bridge" for
     the guided filters of the module docstring.  No gradients."""
-    if proposal not in PROPOSALS:
-        raise ValueError(f"proposal must be one of {PROPOSALS}, got {proposal!r}")
-    bridge, residual = proposal != "bootstrap", proposal == "residual_bridge"
-    if bridge and not isinstance(observation_likelihood, GaussianObservationLikelihood):
-        raise ValueError(f"proposal='{proposal}' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
-                         f"variance (got {type(observation_likelihood).__name__})")
+    bridge, residual = _proposal_flags(proposal, observation_likelihood)
     theta, x0 = _validate(sde, observations, theta, time_step, n_particles, initial_state)
     dev = theta.device
     obs = observations if observations.values.device == dev else observations.to(dev)
-    if key is None:
-        key = torch.randint(-2 ** 31, 2 ** 31, (2,), device=dev, dtype=torch.int32)
-    else:
-        key = torch.as_tensor(key).to(dev)
-        if key.numel() != 2 or key.is_floating_point():
-            raise ValueError("key must hold two 32-bit integer words")
-        key = key.reshape(2)
+    key = _call_key(key, dev)
     pos = tuple(positive_dims)
     with torch.no_grad():
         route = _kernel_route(sde, obs, observation_likelihood, theta, n_particles, proposal)
         if route is not None:
-            from .. import _hip
             kind, network = route
-            H = observation_likelihood.obs_matrix
-            rows = torch.round(obs.times / time_step).to(torch.int32)
-            count = type(observation_likelihood) in COUNT_LIKELIHOODS
-            term = observation_likelihood.kernel_terms(obs.values) if count else float(observation_likelihood.variance)
-            args = (kind, x0, kernel_theta(network, theta), rows, obs.values, None if H is None else H.to(theta), term, key.to(torch.int32) if key.dtype != torch.int32 else key,
-                    float(time_step), n_particles, pos)
+            rows, model = _launch_model(obs, observation_likelihood, theta, time_step)
+            out = _kernel_call("particle_filter", proposal, (kind, x0, kernel_theta(network, theta), rows), model,
+                               key.to(torch.int32) if key.dtype != torch.int32 else key, float(time_step), n_particles, pos,
+                               network=network, return_particles=return_particles)
             if bridge:
-                return ParticleFilterResult(*_hip.guided_particle_filter(*args, network=network, return_particles=return_particles,
-                                                                         residual=residual))
-            out = _hip.particle_filter(*args, network=network, return_particles=return_particles)
+                return ParticleFilterResult(*out)
             lw = _gaussian_log_weights(observation_likelihood, obs.values, out[5]) if return_particles else None
             return ParticleFilterResult(*out, lw)
         return _torch_filter(sde, obs, observation_likelihood, theta, float(time_step), n_particles, x0, pos, return_particles, key,
                              bridge, residual)
+
+
+def _proposal_flags(proposal, like) -> tuple[bool, bool]:
+    """``(bridge, residual)`` of a valid ``proposal``: whether the steps are guided, and by the residual bridge."""
+    if proposal not in PROPOSALS:
+        raise ValueError(f"proposal must be one of {PROPOSALS}, got {proposal!r}")
+    if proposal != "bootstrap" and not isinstance(like, GaussianObservationLikelihood):
+        raise ValueError(f"proposal='{proposal}' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
+                         f"variance (got {type(like).__name__})")
+    return proposal != "bootstrap", proposal == "residual_bridge"
+
+
+def _call_key(key, dev) -> Tensor:
+    """A call's two key words ``[2]`` on ``dev``: the caller's, or drawn from torch's generator there."""
+    if key is None:
+        return torch.randint(-2 ** 31, 2 ** 31, (2,), device=dev, dtype=torch.int32)
+    key = torch.as_tensor(key).to(dev)
+    if key.numel() != 2 or key.is_floating_point():
+        raise ValueError("key must hold two 32-bit integer words")
+    return key.reshape(2)
+
+
+def _launch_model(obs, like, like_theta, time_step):
+    """The fixed arguments of the kernel launches: ``(rows [K] int32, (observed values, obs_matrix cast to theta's dtype and device
+    or None, the Gaussian variance or the count likelihood's kernel terms))``."""
+    H = like.obs_matrix
+    rows = torch.round(obs.times / time_step).to(torch.int32)
+    term = like.kernel_terms(obs.values) if type(like) in COUNT_LIKELIHOODS else float(like.variance)
+    return rows, (obs.values, None if H is None else H.to(like_theta), term)
+
+
+def _kernel_call(name, proposal, head, model, *tail, **keywords):
+    """``_hip.<name>(*head, *tail)`` for the bootstrap proposal, ``_hip.guided_<name>(*head, *model, *tail, residual=...)`` for the
+    guided ones: the bindings are looked up in ``_hip`` at every call.  The plain filter takes the observation model as well (it
+    weighs with it); the plain replays have no use for it."""
+    from .. import _hip
+    if proposal != "bootstrap":
+        return getattr(_hip, "guided_" + name)(*head, *model, *tail, residual=proposal == "residual_bridge", **keywords)
+    return getattr(_hip, name)(*head, *(model if name == "particle_filter" else ()), *tail, **keywords)
 
 
 def _gaussian_log_weights(like, values, particles):
@@ -329,34 +362,34 @@ def _ode_endpoint(sde, x, th, n_steps, dt, floor):
     return x
 
 
-def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, bridge=False, residual=False) -> ParticleFilterResult:
+def _segment_propagator(sde, obs, like, theta, dt, pos, bridge, residual):
+    """The step of the module docstring, stated once for the filter and the two replays (``particle_smoother``, ``particle_mcmc``).
+    Returns ``advance(x, th, t0, k, row, paths, key, out=None)``: the states ``x [B, S]`` with parameters ``th [B, P]`` taken over the
+    grid steps ``t0 .. row - 1`` towards observation ``k`` at grid row ``row`` (the guided steps look ``row - t`` steps ahead), path b
+    on the normals of ``path_normals(paths [B], ., S, key)``; ``out [B, row - t0, S]``: where every state after a step is kept as
+    well.  It gives (the end state, the summed log-ratio ``lr [B]`` of the guided steps or None); a segment without steps returns x
+    as it is."""
     dev, dtype = theta.device, theta.dtype
-    M, P = theta.shape
-    S = x0.shape[1]
-    rows = torch.round(obs.times / dt).long().tolist()
-    K = len(rows)
-    x = x0[:, None, :].expand(M, N, S).reshape(M * N, S).clone()
-    th = theta[:, None, :].expand(M, N, P).reshape(M * N, P)
+    S = int(sde.state_dim)
     floor = _floor_vector(list(pos), S, dev, dtype) if pos else None
     root_dt = dt ** 0.5
-    slot = torch.arange(N, device=dev)
-    neg_inf = torch.tensor(float("-inf"), device=dev, dtype=dtype)
-    incr, ess, means, stds, parts, ancs, lws = [], [], [], [], [], [], []
-    t, z, z_block = 0, None, -1
     H = like.obs_matrix if bridge else None
     H = None if H is None else H.to(device=dev, dtype=dtype)
-    lr = torch.zeros(M * N, device=dev, dtype=dtype) if bridge else None
-    for k in range(K):
-        if residual and t < rows[k]:
-            eta, eta_end = x, _ode_endpoint(sde, x, th, rows[k] - t, dt, floor)
-        while t < rows[k]:
+
+    def advance(x, th, t0, k, row, paths, key, out=None):
+        lr = torch.zeros(x.shape[0], device=dev, dtype=dtype) if bridge else None
+        if residual and t0 < row:
+            # a segment starts from a state both the filter and the replays hold, so eta and eta_end are the same in all of them
+            eta, eta_end = x, _ode_endpoint(sde, x, th, row - t0, dt, floor)
+        z, z_block = None, -1
+        for t in range(t0, row):
             if t // 4 != z_block:
                 z_block = t // 4
-                z = stream_normals(M * N, z_block, S, key).to(dtype)
+                z = path_normals(paths, z_block, S, key).to(dtype)
             if bridge:
                 f_eta = sde.drift(eta, th) if residual else None
-                x, step_lr = _bridge_step(sde, x, th, z[..., t % 4], obs.values[k].to(dtype), H, float(like.variance), rows[k] - t,
-                                          dt, root_dt, (eta, f_eta, eta_end) if residual else None)
+                x, step_lr = _bridge_step(sde, x, th, z[..., t % 4], obs.values[k].to(dtype), H, float(like.variance), row - t, dt,
+                                          root_dt, (eta, f_eta, eta_end) if residual else None)
                 lr = lr + step_lr
                 if residual:
                     eta = _ode_step(eta, f_eta, dt, floor)
@@ -365,10 +398,33 @@ def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, 
                 x = x + sde.drift(x, th) * dt + shock * root_dt
             if floor is not None:
                 x = torch.maximum(x, floor)
-            t += 1
+            if out is not None:
+                out[:, t - t0] = x
+        return x, lr
+
+    return advance
+
+
+def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, bridge=False, residual=False) -> ParticleFilterResult:
+    dev, dtype = theta.device, theta.dtype
+    M, P = theta.shape
+    S = x0.shape[1]
+    rows = torch.round(obs.times / dt).long().tolist()
+    K = len(rows)
+    x = x0[:, None, :].expand(M, N, S).reshape(M * N, S).clone()
+    th = theta[:, None, :].expand(M, N, P).reshape(M * N, P)
+    advance = _segment_propagator(sde, obs, like, theta, dt, pos, bridge, residual)
+    b = torch.arange(M * N, device=dev, dtype=torch.int64)          # slot j of filter m draws the normals of path m N + j
+    slot = torch.arange(N, device=dev)
+    neg_inf = torch.tensor(float("-inf"), device=dev, dtype=dtype)
+    incr, ess, means, stds, parts, ancs, lws = [], [], [], [], [], [], []
+    t = 0
+    for k in range(K):
+        x, lr = advance(x, th, t, k, rows[k], b, key)
+        t = max(t, rows[k])
         lw = like.log_prob(obs.values[k].to(dtype).unsqueeze(0).expand(M * N, -1), x)
         if bridge:
-            lw, lr = lw + lr, torch.zeros_like(lr)
+            lw = lw + lr
         lw = lw.reshape(M, N)
         lw = torch.where(torch.isnan(lw), neg_inf, lw)
         mx = lw.max(dim=1, keepdim=True).values

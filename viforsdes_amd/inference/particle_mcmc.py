@@ -63,10 +63,10 @@ recomputed at the end).  With ``N`` particles, ``K`` observations at the grid ro
    6 in the fourth slot is new); at a kept state whose index is a multiple of ``path_thin`` the record is kept with it;
 9. after the loop every kept record is replayed as in ``particle_smoother``: segment k, the grid steps ``rows[k-1] .. rows[k] - 1``
    (segment 0 from step 0 and ``x0[c]``), starts at ``anchors[k-1]``, takes the normals of path ``noise_path[k]`` under the key
-   ``fkey_{path_iteration}`` and the theta of the kept state, and runs the filter's step (Euler-Maruyama, or the bridge step towards
-   ``y_k`` for ``proposal="bridge"`` / ``"residual_bridge"``, the latter with its companion path started at the anchor, then the
-   1e-6 clamp).  The state after step t goes to ``paths[.., t + 1]``, ``paths[.., 0] =
-   x0[c]``; a dead record (a chain that never reached a finite target) gives NaN paths and ``path_iteration`` -1.
+   ``fkey_{path_iteration}`` and the theta of the kept state, and runs the filter's steps towards observation k from the anchor (the
+   rule: the module docstring of ``particle_filter``; the code: ``particle_filter._segment_propagator``, for every proposal).  The
+   state after step t goes to ``paths[.., t + 1]``, ``paths[.., 0] = x0[c]``; a dead record (a chain that never reached a finite
+   target) gives NaN paths and ``path_iteration`` -1.
 
 With ``return_paths=False`` nothing of this happens: no store, no launch, no random number.
 
@@ -83,13 +83,12 @@ from __future__ import annotations
 import math
 from collections.abc import Sequence
 from dataclasses import dataclass
-from functools import partial
 from typing import Any, Optional
 
 import torch
 from torch import Tensor
 
-from ..core.observations import COUNT_LIKELIHOODS, GaussianObservationLikelihood, ObservationLikelihood, Observations
+from ..core.observations import ObservationLikelihood, Observations
 from ..core.priors import Prior, PriorType
 from ..core.sde import SDE, kernel_theta
 from . import particle_filter as _pf
@@ -160,13 +159,7 @@ def proposal_normals(n_chains: int, n_params: int, iteration: int, key: Tensor) 
     dev = key.device
     c = torch.arange(n_chains, device=dev, dtype=torch.int64)[:, None]
     blk = torch.arange((n_params + 3) // 4, device=dev, dtype=torch.int64)[None, :]
-    w = _words(key, iteration, blk, c, 3)
-    out = []
-    for wa, wb in ((w[0], w[1]), (w[2], w[3])):
-        r = torch.sqrt(-2.0 * torch.log(_pf._uniform(wa).double()))
-        ang = 2.0 * math.pi * _pf._uniform(wb).double()
-        out += [r * torch.cos(ang), r * torch.sin(ang)]
-    return torch.stack(out, dim=-1).reshape(n_chains, -1)[:, :n_params]
+    return _pf._box_muller(_words(key, iteration, blk, c, 3)).reshape(n_chains, -1)[:, :n_params]
 
 
 def acceptance_log_uniforms(n_chains: int, iteration: int, key: Tensor) -> Tensor:
@@ -225,27 +218,10 @@ def draw_path_records(loglik: Tensor, particles: Tensor, ancestors: Tensor, iter
             torch.where(dead, torch.full_like(noise, DEAD_PATH), noise))
 
 
-def _record_normals(paths: Tensor, block: int, state_dim: int, keys: Tensor) -> Tensor:
-    """``particle_filter.stream_normals`` for the path indices ``paths [B]`` (int64), record b under its own key ``keys[b]``:
-    float64 ``[B, S, 4]``."""
-    dev = paths.device
-    k = keys.to(torch.int64) & 0xFFFFFFFF
-    i = torch.arange(state_dim, device=dev, dtype=torch.int64)[None, :]
-    blk = torch.full((1, 1), int(block), device=dev, dtype=torch.int64)
-    w = _pf.philox4x32_10(blk, i, paths[:, None], torch.zeros_like(blk), k[:, 0:1], k[:, 1:2])
-    out = []
-    for wa, wb in ((w[0], w[1]), (w[2], w[3])):
-        r = torch.sqrt(-2.0 * torch.log(_pf._uniform(wa).double()))
-        ang = 2.0 * math.pi * _pf._uniform(wb).double()
-        out += [r * torch.cos(ang), r * torch.sin(ang)]
-    return torch.stack(out, dim=-1)
-
-
 def replay_path_records(sde, obs, like, theta: Tensor, x0: Tensor, anchors: Tensor, noise_path: Tensor, keys: Tensor, dt: float,
                         pos: Sequence[int], bridge: bool, residual: bool = False) -> Tensor:
     """Step 9 of the module docstring in torch: ``paths [B, T+1, S]`` of the records ``(theta [B, P], x0 [B, S], anchors [B, K, S],
-    noise_path [B, K] int64, keys [B, 2])``, the steps of ``particle_smoother``'s torch replay."""
-    from ..core.euler_maruyama import _floor_vector
+    noise_path [B, K] int64, keys [B, 2])``, segment by segment on ``particle_filter._segment_propagator`` like ``particle_smoother``'s torch replay."""
     dev, dtype = theta.device, theta.dtype
     B, K, S = anchors.shape
     rows = torch.round(obs.times / dt).long().tolist()
@@ -253,37 +229,14 @@ def replay_path_records(sde, obs, like, theta: Tensor, x0: Tensor, anchors: Tens
     dead = noise_path[:, -1] == DEAD_PATH
     noise = torch.where(dead[:, None], torch.zeros_like(noise_path), noise_path)
     start = torch.where(dead[:, None, None], torch.zeros_like(anchors), anchors)
-    floor = _floor_vector(list(pos), S, dev, dtype) if pos else None
-    root_dt = dt ** 0.5
-    H = like.obs_matrix if bridge else None
-    H = None if H is None else H.to(device=dev, dtype=dtype)
+    advance = _pf._segment_propagator(sde, obs, like, theta, dt, pos, bridge, residual)
     paths = torch.empty(B, T + 1, S, device=dev, dtype=dtype)
     paths[:, 0] = x0
     row_prev = 0
     for k in range(K):
         if rows[k] == row_prev:
             continue
-        x = x0 if k == 0 else start[:, k - 1]
-        z, z_block = None, -1
-        if residual:
-            # the segment restarts from its anchor, so eta and eta_end are the filter's
-            eta, eta_end = x, _pf._ode_endpoint(sde, x, theta, rows[k] - row_prev, dt, floor)
-        for t in range(row_prev, rows[k]):
-            if t // 4 != z_block:
-                z_block = t // 4
-                z = _record_normals(noise[:, k], z_block, S, keys).to(dtype)
-            if bridge:
-                f_eta = sde.drift(eta, theta) if residual else None
-                x, _ = _pf._bridge_step(sde, x, theta, z[..., t % 4], obs.values[k].to(dtype), H, float(like.variance), rows[k] - t, dt,
-                                        root_dt, (eta, f_eta, eta_end) if residual else None)
-                if residual:
-                    eta = _pf._ode_step(eta, f_eta, dt, floor)
-            else:
-                shock = torch.einsum("bij,bj->bi", sde.diffusion(x, theta), z[..., t % 4])
-                x = x + sde.drift(x, theta) * dt + shock * root_dt
-            if floor is not None:
-                x = torch.maximum(x, floor)
-            paths[:, t + 1] = x
+        advance(x0 if k == 0 else start[:, k - 1], theta, row_prev, k, rows[k], noise[:, k], keys, out=paths[:, row_prev + 1:rows[k] + 1])
         row_prev = rows[k]
     return torch.where(dead[:, None, None], torch.full_like(paths, float("nan")), paths)
 
@@ -348,11 +301,7 @@ def _validate(sde, observations, observation_likelihood, initial_theta, time_ste
         raise ValueError(f"path_thin must be >= 1, got {path_thin}")
     if return_paths and estimator is not None:
         raise ValueError("return_paths=True needs the particle filter's store: it cannot be combined with _estimator")
-    if proposal not in _pf.PROPOSALS:
-        raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
-    if proposal != "bootstrap" and not isinstance(observation_likelihood, GaussianObservationLikelihood):
-        raise ValueError(f"proposal='{proposal}' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
-                         f"variance (got {type(observation_likelihood).__name__})")
+    _pf._proposal_flags(proposal, observation_likelihood)
     if thin < 1 or adapt_interval < 1 or filters_per_chain < 1:
         raise ValueError(f"thin, adapt_interval and filters_per_chain must be >= 1 (got {thin}, {adapt_interval}, {filters_per_chain})")
     if warmup < 0 or n_iterations <= warmup:
@@ -415,13 +364,7 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
     C, P = theta0.shape
     R = int(filters_per_chain)
     obs = observations if observations.values.device == dev else observations.to(dev)
-    if key is None:
-        key = torch.randint(-2 ** 31, 2 ** 31, (2,), device=dev, dtype=torch.int32)
-    else:
-        key = torch.as_tensor(key).to(dev)
-        if key.numel() != 2 or key.is_floating_point():
-            raise ValueError("key must hold two 32-bit integer words")
-        key = key.reshape(2)
+    key = _pf._call_key(key, dev)
     with torch.no_grad():
         u0 = unconstrain(theta0, mask)
         if proposal_scale_tril is not None:
@@ -551,14 +494,7 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
     history = torch.empty(max(w2 - w4, 0), C, P, **f32) if adapt else None
     L_host = L.detach().float().cpu().contiguous()
     prior_args = (1 if prior.type == PriorType.LOG_NORMAL else 0, float(prior.mean), float(prior.std), pos_theta)
-    # the filter launch's fixed arguments, formed once (particle_filter.particle_filter forms them per call)
-    H = like.obs_matrix
-    rows = torch.round(obs.times / dt).to(torch.int32)
-    term = like.kernel_terms(obs.values) if type(like) in COUNT_LIKELIHOODS else float(like.variance)
-    H = None if H is None else H.to(u0)
-    filt = _hip.particle_filter
-    if proposal != "bootstrap":
-        filt = partial(_hip.guided_particle_filter, residual=proposal == "residual_bridge")
+    rows, model = _pf._launch_model(obs, like, u0, dt)                 # formed once for every launch of the loop
     x0 = x0.contiguous()
     logliks, loglik, window_base, pending = [], None, 0, None
     store = None
@@ -612,8 +548,8 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
             step_launch(i, None)                           # open iteration i again with the new step size / L
         if i == warmup:
             n_acc.zero_()
-        out = filt(kind, x0, kernel_theta(network, theta_prop), rows, obs.values, H, term, fkey, dt, N, pos_state, network=network,
-                   store=store)
+        out = _pf._kernel_call("particle_filter", proposal, (kind, x0, kernel_theta(network, theta_prop), rows), model, fkey, dt, N,
+                               pos_state, network=network, store=store)
         loglik = out[0].view(C, R)
         logliks.append(loglik)
         if trace is not None:
@@ -625,13 +561,9 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
     if not path_thin:
         return out
     B = n_path * C
-    record = (x0[::R].repeat(n_path, 1), kernel_theta(network, samples[::path_thin].reshape(B, P)), rows)
-    tail = (anchor_rows.view(B, K, S), noise_rows.view(B, K), filter_keys(iter_rows.view(B), key), dt, pos_state)
-    if proposal != "bootstrap":
-        paths = _hip.guided_anchored_replay(kind, *record, obs.values, H, float(like.variance), *tail, network=network, n_steps=n_steps,
-                                            residual=proposal == "residual_bridge")
-    else:
-        paths = _hip.anchored_replay(kind, *record, *tail, network=network, n_steps=n_steps)
+    record = (kind, x0[::R].repeat(n_path, 1), kernel_theta(network, samples[::path_thin].reshape(B, P)), rows)
+    paths = _pf._kernel_call("anchored_replay", proposal, record, model, anchor_rows.view(B, K, S), noise_rows.view(B, K),
+                             filter_keys(iter_rows.view(B), key), dt, pos_state, network=network, n_steps=n_steps)
     return out + (paths.view(n_path, C, -1, S), torch.where(noise_rows[:, :, -1] == -1, torch.full_like(iter_rows, -1), iter_rows))
 
 

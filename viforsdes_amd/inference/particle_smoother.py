@@ -21,10 +21,10 @@ The rule, for filter ``m`` (``D = n_draws``, ``N = n_particles``, ``rows`` the g
 * trace: ``lineage[m, d, k-1] = a[m, k-1, lineage[m, d, k]]`` for k = K-1 .. 1;
 * replay: segment k covers the global grid steps ``rows[k-1] .. rows[k] - 1`` (segment 0: ``0 .. rows[0] - 1``, from ``x0[m]``).  For
   k >= 1 it starts at ``X[m, k-1, lineage[m, d, k-1]]``; its noise is that of path ``b = m N + lineage[m, d, k]`` (a slot keeps its
-  own stream across resampling); its step is the filter's (Euler-Maruyama, or the bridge step towards ``y_k`` with
-  ``n = rows[k] - t`` for ``proposal="bridge"`` / ``"residual_bridge"``, then the 1e-6 clamp of the positive dims; the residual
-  bridge's companion path eta starts at the segment's stored start state, as in the filter).  The state after step t goes to
-  ``paths[m, d, t+1]``, ``paths[m, d, 0] = x0[m]``; a zero-length segment (observations sharing a row) writes nothing;
+  own stream across resampling); its steps are the filter's towards observation k, for every proposal: the rule is the module
+  docstring of ``particle_filter`` and the code is the filter's own (``particle_filter._segment_propagator``), started from the
+  segment's stored start state.  The state after step t goes to ``paths[m, d, t+1]``, ``paths[m, d, 0] = x0[m]``; a zero-length
+  segment (observations sharing a row) writes nothing;
 * a filter with ``log_likelihood[m] = -inf`` (some observation left no positive weight) has no smoothing sample: lineage -1, paths
   NaN, ``distinct_lineages`` 0.
 
@@ -38,7 +38,6 @@ case runs the torch route silently, and ``particle_filter.HIP_FILTER = False`` f
 in torch on both routes."""
 from __future__ import annotations
 
-import math
 from collections.abc import Sequence
 from dataclasses import dataclass
 from typing import Optional
@@ -46,8 +45,7 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from ..core.euler_maruyama import _floor_vector
-from ..core.observations import GaussianObservationLikelihood, ObservationLikelihood, Observations
+from ..core.observations import ObservationLikelihood, Observations
 from ..core.sde import SDE, kernel_theta
 from . import particle_filter as _pf
 
@@ -88,45 +86,19 @@ def systematic_draws(weights: Tensor, u: Tensor, n_draws: int) -> Tensor:
     return torch.searchsorted(cum.contiguous(), tau.contiguous(), right=True).clamp(max=N - 1)
 
 
-def _path_normals(paths: Tensor, block: int, state_dim: int, key: Tensor) -> Tensor:
-    """``particle_filter.stream_normals`` for the given path indices (int64 ``[B]``): float64 ``[B, S, 4]``."""
-    dev = key.device
-    k0, k1 = _pf._key_words(key)
-    i = torch.arange(state_dim, device=dev, dtype=torch.int64)[None, :]
-    blk = torch.full((1, 1), int(block), device=dev, dtype=torch.int64)
-    w = _pf.philox4x32_10(blk, i, paths[:, None], torch.zeros_like(blk), k0, k1)
-    out = []
-    for wa, wb in ((w[0], w[1]), (w[2], w[3])):
-        r = torch.sqrt(-2.0 * torch.log(_pf._uniform(wa).double()))
-        ang = 2.0 * math.pi * _pf._uniform(wb).double()
-        out += [r * torch.cos(ang), r * torch.sin(ang)]
-    return torch.stack(out, dim=-1)
-
-
 def particle_smoother(sde: SDE, observations: Observations, observation_likelihood: ObservationLikelihood, theta: Tensor,
                       time_step: float, n_particles: int = 1024, n_draws: int = 1, initial_state: Optional[Tensor] = None,
                       positive_dims: Sequence[int] = (), key: Optional[Tensor] = None, proposal: str = "bootstrap") -> SmoothedPaths:
     """``n_draws`` smoothed paths per row of ``theta`` from the genealogy of ``particle_filter`` (the module docstring has the
     rule).  Arguments, validation, ``key`` and ``proposal`` are those of ``particle_filter``; ``n_draws >= 1``.  Draws of one filter
     share ancestors (see ``SmoothedPaths.distinct_lineages``); draws of different filters are independent.  No gradients."""
-    if proposal not in _pf.PROPOSALS:
-        raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
-    bridge, residual = proposal != "bootstrap", proposal == "residual_bridge"
-    if bridge and not isinstance(observation_likelihood, GaussianObservationLikelihood):
-        raise ValueError(f"proposal='{proposal}' needs a GaussianObservationLikelihood: the proposal is derived from its obs_matrix and "
-                         f"variance (got {type(observation_likelihood).__name__})")
+    bridge, residual = _pf._proposal_flags(proposal, observation_likelihood)
     if n_draws < 1:
         raise ValueError(f"n_draws must be >= 1, got {n_draws}")
     theta, x0 = _pf._validate(sde, observations, theta, time_step, n_particles, initial_state)
     dev = theta.device
     obs = observations if observations.values.device == dev else observations.to(dev)
-    if key is None:
-        key = torch.randint(-2 ** 31, 2 ** 31, (2,), device=dev, dtype=torch.int32)
-    else:
-        key = torch.as_tensor(key).to(dev)
-        if key.numel() != 2 or key.is_floating_point():
-            raise ValueError("key must hold two 32-bit integer words")
-        key = key.reshape(2)
+    key = _pf._call_key(key, dev)
     pos = tuple(positive_dims)
     M, N, D = theta.shape[0], int(n_particles), int(n_draws)
     with torch.no_grad():
@@ -139,26 +111,17 @@ def particle_smoother(sde: SDE, observations: Observations, observation_likeliho
         w = torch.where(live, torch.exp(lw - torch.where(live, mx, torch.zeros_like(mx))), torch.ones_like(lw))
         last = systematic_draws(w, smoothing_uniforms(M, key), D)
         last = torch.where(dead[:, None], torch.full_like(last, -1), last).to(torch.int32)
-        rows = torch.round(obs.times / time_step).to(torch.int32)
         route = _pf._kernel_route(sde, obs, observation_likelihood, theta, N, proposal)
         if route is not None:
-            from .. import _hip
             kind, network = route
-            key32 = key.to(torch.int32) if key.dtype != torch.int32 else key
-            th = kernel_theta(network, theta)
-            if bridge:
-                H = observation_likelihood.obs_matrix
-                paths, lineage = _hip.guided_filter_replay(kind, x0, th, rows, obs.values, None if H is None else H.to(theta),
-                                                           float(observation_likelihood.variance), key32, float(time_step),
-                                                           res.particles, res.ancestors, last, pos, network=network,
-                                                           residual=residual)
-            else:
-                paths, lineage = _hip.filter_replay(kind, x0, th, rows, key32, float(time_step), res.particles, res.ancestors, last,
-                                                    pos, network=network)
+            rows, model = _pf._launch_model(obs, observation_likelihood, theta, time_step)
+            paths, lineage = _pf._kernel_call("filter_replay", proposal, (kind, x0, kernel_theta(network, theta), rows), model,
+                                              key.to(torch.int32) if key.dtype != torch.int32 else key, float(time_step),
+                                              res.particles, res.ancestors, last, pos, network=network)
         else:
             lineage = _trace(res.ancestors, last)
             paths = _torch_replay(sde, obs, observation_likelihood, theta, float(time_step), x0, pos, key, bridge, res.particles,
-                                  lineage, rows.tolist(), residual)
+                                  lineage, torch.round(obs.times / time_step).long().tolist(), residual)
         srt = torch.sort(lineage, dim=1).values
         distinct = 1 + (srt[:, 1:] != srt[:, :-1]).sum(dim=1)
         distinct = torch.where(dead[:, None], torch.zeros_like(distinct), distinct)
@@ -188,41 +151,20 @@ def _torch_replay(sde, obs, like, theta, dt, x0, pos, key, bridge, particles, li
     dead = lin[:, :, -1] < 0                                                   # [M, D]
     slot = lin.clamp(min=0)
     th = theta[:, None, :].expand(M, D, P).reshape(M * D, P)
-    floor = _floor_vector(list(pos), S, dev, dtype) if pos else None
-    root_dt = dt ** 0.5
-    H = like.obs_matrix if bridge else None
-    H = None if H is None else H.to(device=dev, dtype=dtype)
+    advance = _pf._segment_propagator(sde, obs, like, theta, dt, pos, bridge, residual)
     base = torch.arange(M, device=dev, dtype=torch.int64)[:, None] * N
-    paths = torch.empty(M, D, T + 1, S, device=dev, dtype=dtype)
-    paths[:, :, 0] = x0[:, None, :]
+    x_first = x0[:, None, :].expand(M, D, S).reshape(M * D, S)
+    paths = torch.empty(M * D, T + 1, S, device=dev, dtype=dtype)
+    paths[:, 0] = x_first
     row_prev = 0
     for k in range(K):
         if rows[k] == row_prev:
             continue
         if k == 0:
-            x = x0[:, None, :].expand(M, D, S).reshape(M * D, S)
+            x = x_first
         else:
             x = torch.gather(particles[:, k - 1], 1, slot[:, :, k - 1, None].expand(-1, -1, S)).reshape(M * D, S)
-        b = (base + slot[:, :, k]).reshape(M * D)
-        z, z_block = None, -1
-        if residual:
-            # the segment restarts from its stored start state, so eta and eta_end are the filter's
-            eta, eta_end = x, _pf._ode_endpoint(sde, x, th, rows[k] - row_prev, dt, floor)
-        for t in range(row_prev, rows[k]):
-            if t // 4 != z_block:
-                z_block = t // 4
-                z = _path_normals(b, z_block, S, key).to(dtype)
-            if bridge:
-                f_eta = sde.drift(eta, th) if residual else None
-                x, _ = _pf._bridge_step(sde, x, th, z[..., t % 4], obs.values[k].to(dtype), H, float(like.variance), rows[k] - t, dt,
-                                        root_dt, (eta, f_eta, eta_end) if residual else None)
-                if residual:
-                    eta = _pf._ode_step(eta, f_eta, dt, floor)
-            else:
-                shock = torch.einsum("bij,bj->bi", sde.diffusion(x, th), z[..., t % 4])
-                x = x + sde.drift(x, th) * dt + shock * root_dt
-            if floor is not None:
-                x = torch.maximum(x, floor)
-            paths[:, :, t + 1] = x.reshape(M, D, S)
+        advance(x, th, row_prev, k, rows[k], (base + slot[:, :, k]).reshape(M * D), key, out=paths[:, row_prev + 1:rows[k] + 1])
         row_prev = rows[k]
+    paths = paths.reshape(M, D, T + 1, S)
     return torch.where(dead[:, :, None, None], torch.full_like(paths, float("nan")), paths)
