@@ -873,6 +873,31 @@ int vsde_crn_kinetic_residual_anchored_replay(const vsde_crn_network *net, const
                                               const uint32_t *noise_path, const uint32_t *keys, double time_step,
                                               const uint8_t *positive_mask_host, float *paths, void *stream);
 
+/* Exact simulation of the Markov jump process of a reaction network on integer copy numbers, the process whose diffusion
+ * approximation the entry points above run (Gillespie's direct method; viforsdes_amd/core/jump_process.py is the specification).
+ * B trajectories, a thread each: x0[B][S] (int32, 0 .. 2^30), theta[B][P] (P = R; the kinetic entry point takes rates[B][2R]),
+ * out_times[K] (DEVICE float64, non-decreasing, >= 0), key: 2 words in DEVICE memory.  Propensity of reaction j at the state x:
+ *   mass action  a_j = k_j prod_i x_i (x_i - 1) .. (x_i - r_ji + 1)   (falling factorial, in species order; no 1 / r!)
+ *   rate law     the h_j of vsde_crn_kinetics with u = x_s, times 1[x_i >= r_ji for all i]
+ * Event e (0-based) of path b: c_j = a_0 + .. + a_j in reaction order (fp32), a0 = c_{R-1}; a0 == 0: the state is absorbed and
+ * fills every remaining output; else t += -log(u1) / a0 (the quotient in fp32, the clock t in float64), the reaction is the
+ * smallest j with u2 a0 < c_j (none: the last j with a_j > 0), x += nu_j.  (u1, u2) are the uniforms ((w >> 8) + 0.5) 2^-24 of
+ * words 2 (e & 1), 2 (e & 1) + 1 of philox4x32_10(counter {e >> 1, 0, b, 7}, key).  states[b][k] is the state after every event
+ * with time <= out_times[k].
+ *   status[b]: 0 complete; 1 the path fired max_events events before its last output time (outputs not reached: -1); 2 a
+ * propensity was NaN, infinite or negative (outputs not reached: -1).  n_events[b]: the events fired.  E > 0: event_times[B][E]
+ * (float64) and event_reactions[B][E] take the first E events of each path (NaN / -1 past the last); E = 0: both may be NULL.
+ *   VSDE_E_BADARG before any HIP call: a bad descriptor (S, R, orders, rate laws) or one that disagrees with S / P; B or K < 1,
+ * E < 0, max_events outside 1 .. 2^23 (with |nu| <= 127 and x0 <= 2^30 the int32 state cannot overflow), a NULL pointer, a NULL log
+ * pointer with E > 0. */
+int vsde_crn_jump_process(const vsde_crn_network *net, int B, int S, int P, int K, int E, const int32_t *x0, const float *theta,
+                          const double *out_times, const uint32_t *key, int max_events, int32_t *states, int32_t *n_events,
+                          int32_t *status, double *event_times, int32_t *event_reactions, void *stream);
+int vsde_crn_kinetic_jump_process(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int S, int P, int K, int E,
+                                  const int32_t *x0, const float *rates, const double *out_times, const uint32_t *key,
+                                  int max_events, int32_t *states, int32_t *n_events, int32_t *status, double *event_times,
+                                  int32_t *event_reactions, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

@@ -13,6 +13,8 @@ _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 from .config import AmpDtype, EncoderConfig, HeadConfig, PretrainConfig, TrainingConfig, YamlConfig
 from .core.observations import (GaussianObservationLikelihood, NegativeBinomialObservationLikelihood, ObservationLikelihood,
                                 Observations, PoissonObservationLikelihood)
+from .core.jump_process import (DiffusionApproximationCheck, JumpProcessResult, diffusion_approximation_check,
+                                jump_process)
 from .core.priors import Prior, PriorType
 from .core.reaction_network import Hill, MichaelisMenten, ReactionNetworkSDE
 from .core.sde import SDE, FunctionalSDE, make_sde
@@ -28,5 +30,6 @@ __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "Trainin
            "ObservationLikelihood", "Observations", "Prior", "PriorType", "SDE",
            "FunctionalSDE", "Hill", "MichaelisMenten", "ReactionNetworkSDE", "make_sde", "InferenceConfig", "infer", "VariationalPosterior",
            "EvidenceEstimate", "PosteriorPredictive", "ParameterReweighting", "ParticleFilterResult", "particle_filter",
-           "PathReweighting", "SmoothedPaths", "particle_smoother", "ParticleMCMCResult", "particle_mcmc"]
+           "PathReweighting", "SmoothedPaths", "particle_smoother", "ParticleMCMCResult", "particle_mcmc", "JumpProcessResult",
+           "jump_process", "DiffusionApproximationCheck", "diffusion_approximation_check"]
 __version__ = "0.1.0"

@@ -78,6 +78,7 @@ EXPORTS = (
     "vsde_residual_particle_filter", "vsde_crn_residual_particle_filter", "vsde_crn_kinetic_residual_particle_filter",
     "vsde_residual_filter_replay", "vsde_crn_residual_filter_replay", "vsde_crn_kinetic_residual_filter_replay",
     "vsde_residual_anchored_replay", "vsde_crn_residual_anchored_replay", "vsde_crn_kinetic_residual_anchored_replay",
+    "vsde_crn_jump_process", "vsde_crn_kinetic_jump_process",
     "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
@@ -443,6 +444,36 @@ def forecast(kind: str, x_start, theta, n_steps: int, out_steps, key, time_step:
               ctypes.c_int(theta.shape[1]), ctypes.c_int(K), _ptr(x_start), _ptr(theta), _ptr(out_steps), _ptr(key),
               ctypes.c_double(time_step), _mask_bytes(positive_dims, S), _ptr(out), _stream(dev))
     return out
+
+
+def jump_process(x0, theta, out_times, key, max_events: int, record_events: int = 0, network=None):
+    """Gillespie trajectories of a reaction network (include/vsde_hip.h: vsde_crn_jump_process): x0 int32 [B, S], theta fp32
+    [B, P] (the effective constants [B, 2R] for a CrnKineticRoute), out_times float64 [K] and key (2 int32 words), all on the
+    device.  Returns ``(states int32 [B, K, S], n_events int32 [B], status int32 [B], event_times float64 [B, E] or None,
+    event_reactions int32 [B, E] or None)`` with E = ``record_events``."""
+    lib = load()
+    dev = _require_hip(x0, theta, out_times, key)
+    if x0.dtype != torch.int32 or x0.ndim != 2 or out_times.dtype != torch.float64 or out_times.ndim != 1:
+        raise ValueError("jump_process: x0 must be an int32 [B, S] tensor and out_times a float64 [K] tensor")
+    if key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2:
+        raise ValueError("jump_process: key must be two int32 words")
+    x0, theta, out_times, key = x0.contiguous(), _f32c(theta), out_times.contiguous(), key.contiguous()
+    B, S = x0.shape
+    K, E = out_times.shape[0], int(record_events)
+    if theta.ndim != 2 or theta.shape[0] != B:
+        raise ValueError(f"jump_process: theta {tuple(theta.shape)} does not have one row for each of the {B} start states")
+    if B < 1 or K < 1 or E < 0:
+        raise ValueError(f"jump_process: bad dims B={B} K={K} E={E}")
+    with torch.cuda.device(dev):
+        states = torch.empty(B, K, S, device=dev, dtype=torch.int32)
+        n_events = torch.empty(B, device=dev, dtype=torch.int32)
+        status = torch.empty(B, device=dev, dtype=torch.int32)
+        ev_t = torch.empty(B, E, device=dev, dtype=torch.float64) if E else None
+        ev_r = torch.empty(B, E, device=dev, dtype=torch.int32) if E else None
+        _call(*_sde_entry(lib, "jump_process", "reaction_network", network), ctypes.c_int(B), ctypes.c_int(S),
+              ctypes.c_int(theta.shape[1]), ctypes.c_int(K), ctypes.c_int(E), _ptr(x0), _ptr(theta), _ptr(out_times), _ptr(key),
+              ctypes.c_int(int(max_events)), _ptr(states), _ptr(n_events), _ptr(status), _ptr(ev_t), _ptr(ev_r), _stream(dev))
+    return states, n_events, status, ev_t, ev_r
 
 
 def _observation_term(variance, n_rows: int, dev):

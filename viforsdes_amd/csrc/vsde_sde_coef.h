@@ -209,6 +209,45 @@ __device__ __forceinline__ float crn_propensity(const CrnNet &n, int j, const fl
     return th[j] * m;
 }
 
+// propensity a_j of the jump process (core/jump_process.py) at the integer state xi [S], xf = (float)xi: mass action with the
+// falling factorial x (x - 1) .. (x - r + 1) in place of x^r (0 once x < r); a rate law as in crn_propensity with u = x_s (never
+// negative here), times the gate 1[x_i >= r_ji for all i]: its reactant row still consumes.  `orders` is the reaction's reactant
+// row packed 2 bits per species (crn_pack_orders), one opaque uniform word per reaction and event (crn_rl): the 3 S comparisons
+// made with a plain table entry are loop-invariant in the event loop and their masks would be hoisted into spilled SGPRs.
+template <int S, int NR, bool KIN>
+__device__ __forceinline__ float crn_jump_propensity(const CrnNet &n, uint32_t orders, int j, const int *xi, const float *xf,
+                                                     const float *th) {
+    orders = (uint32_t)crn_rl((int)orders);
+    if constexpr (KIN) {
+        const int law = crn_rl(n.law[j]);
+        if (law != VSDE_CRN_LAW_MASS_ACTION) {
+            const int e = crn_rl(n.hill_n[j]);
+            const float u = crn_pick<S>(xf, crn_rl(n.mod[j]));
+            const float a = crn_hpow(u, e), c = crn_hpow(th[NR + j], e);
+            bool open = true;
+#pragma unroll
+            for (int i = 0; i < S; ++i) open = open && xi[i] >= (int)((orders >> (2 * i)) & 3u);
+            return th[j] * ((law == VSDE_CRN_LAW_HILL_ACTIVATION ? a : c) / (c + a)) * (open ? 1.f : 0.f);
+        }
+    }
+    float m = 1.f;
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        const uint32_t r = (orders >> (2 * i)) & 3u;
+        if (r >= 1u) m *= xf[i];
+        if (r >= 2u) m *= xf[i] - 1.f;
+        if (r >= 3u) m *= xf[i] - 2.f;
+    }
+    return th[j] * m;
+}
+
+// host: a descriptor's reactant row (orders 0..3, already checked by crn_net) packed 2 bits per species
+static inline uint32_t crn_pack_orders(const vsde_crn_network *d, int j) {
+    uint32_t w = 0;
+    for (int i = 0; i < d->S; ++i) w |= (uint32_t)d->order[j][i] << (2 * i);
+    return w;
+}
+
 // drift f [S] and the lower triangle of Sigma = sum_j h_j nu_j nu_j^T in sig [S][S]
 template <int S, int NR, bool KIN = false>
 __device__ __forceinline__ void crn_drift_cov(const CrnNet &n, const float *x, const float *th, float *f, float *sig) {
