@@ -898,6 +898,41 @@ int vsde_crn_kinetic_jump_process(const vsde_crn_network *net, const vsde_crn_ki
                                   int max_events, int32_t *states, int32_t *n_events, int32_t *status, double *event_times,
                                   int32_t *event_reactions, void *stream);
 
+/* Bootstrap particle filter whose particles are exact trajectories of the jump process above: log p^(y | theta) with no time step
+ * and no diffusion approximation (viforsdes_amd/inference/jump_filter.py is the specification).  M filters, a workgroup each, N
+ * particles (a multiple of 64; the limit depends on the network: 1024, and 512 for rate laws with more than 8 reactions), a
+ * thread each: x0[M][S] (int32, 0 .. 2^30), theta[M][P] (the kinetic entry point: rates[M][2R]), obs_times[K] (DEVICE float64,
+ * non-decreasing, >= 0), obs_values[K][O], obs_matrix[O][S] or NULL (O == S), key: 2 words in DEVICE memory.
+ *   Segment k, from obs_times[k-1] (0 for k = 0) to obs_times[k], of particle slot j of filter m (path b = m N + j): the float64
+ * clock restarts at exactly obs_times[k-1] and the event counter at 0; event e is the event of vsde_crn_jump_process on the
+ * uniforms of philox4x32_10(counter {e >> 1, k, b, 7}, key) (the jump process is segment 0 of this stream); the segment ends as
+ * soon as obs_times[k] < t + tau.  A particle that meets a NaN, infinite or negative propensity, or has fired max_events events
+ * (counted per particle and per segment) short of obs_times[k], is stopped: it keeps its state, its log-weight at k is -inf, and
+ * it carries on from that state only if the whole filter is dead.
+ *   Observation k: lik_kind VSDE_LIK_GAUSSIAN (variance), VSDE_LIK_POISSON or VSDE_LIK_NEGATIVE_BINOMIAL (scale, dispersion,
+ * row_const[K] as in vsde_count_particle_filter) on the state converted to fp32; NaN counts as -inf; then increments, ESS,
+ * weighted moments before resampling, and systematic resampling, all by the rules of vsde_particle_filter (a dead filter: ancestors
+ * = identity, increment -inf, ESS 0, moments NaN).  stopped[M][K] counts the stopped particles of segment k, mean_events[M][K]
+ * the events per particle.  Optional outputs (NULL: not written): particles[M][K][N][S] (int32, before resampling),
+ * ancestors[M][K][N], log_weights[M][K][N], events[M][K][N] (int32).
+ *   VSDE_E_BADARG before any HIP call: a bad descriptor or one that disagrees with S / P; M or K < 1, N not a multiple of 64 or
+ * above the network's limit, M N >= 2^32, O outside 1..16, O != S without obs_matrix, max_events outside 1 .. 2^23, an unknown
+ * lik_kind, a variance / scale / dispersion <= 0, a NULL pointer among the required ones. */
+#define VSDE_LIK_GAUSSIAN 0
+int vsde_crn_jump_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const int32_t *x0,
+                                  const float *theta, const double *obs_times, const float *obs_values, const float *obs_matrix,
+                                  int lik_kind, double variance, double scale, double dispersion, const float *row_const,
+                                  const uint32_t *key, int max_events, float *log_likelihood, float *increments, float *ess,
+                                  float *filtered_mean, float *filtered_std, int32_t *stopped, float *mean_events,
+                                  int32_t *particles, int *ancestors, float *log_weights, int32_t *events, void *stream);
+int vsde_crn_kinetic_jump_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P, int K,
+                                          int O, const int32_t *x0, const float *rates, const double *obs_times,
+                                          const float *obs_values, const float *obs_matrix, int lik_kind, double variance,
+                                          double scale, double dispersion, const float *row_const, const uint32_t *key,
+                                          int max_events, float *log_likelihood, float *increments, float *ess, float *filtered_mean,
+                                          float *filtered_std, int32_t *stopped, float *mean_events, int32_t *particles,
+                                          int *ancestors, float *log_weights, int32_t *events, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

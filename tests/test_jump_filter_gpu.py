@@ -1,0 +1,411 @@
+"""GPU: the jump-process particle-filter kernel (csrc/vsde_jump_filter.hip) through the public ``jump_particle_filter`` and
+``particle_mcmc(..., dynamics="jump")``.
+
+As in test_particle_filter_gpu.py the kernel is compared STAGE BY STAGE against float64 on its own previous stage, never the whole
+filter at once: one flipped ancestor or reaction legitimately changes everything after it.
+
+* propagation: segment k is run again in float64 (tests/jump_filter_reference.py, the reference uniforms) from the kernel's
+  particles at k - 1 gathered through the kernel's ancestors.  The reference flags a (particle, segment) as undecidable when an
+  event has ``u2 a0`` within ``1e-5 a0`` of a boundary ``c_j`` or a tested instant within ``1e-5 (t_next - T_{k-1})`` of ``T_k``;
+  at most 2e-2 of the pairs may be flagged (asserted first) and every other pair matches the kernel exactly, state and event count;
+* weights and summaries from the kernel's particles in float64, with the bounds test_particle_filter_gpu.py and
+  test_count_likelihood_gpu.py state for the same stages: log-weights and increments within 1e-5 max(1, largest finite |lw|); ESS,
+  mean, std to 1e-4 relative -- the mean relative to the weighted mean of |x|, the std with a floor of 1e-6 of that size;
+* ancestors against float64 systematic resampling of those weights with the specified uniform: at most 1e-3 of the entries
+  differ, each by exactly 1, and they never decrease in j; the float64 particle ESS is asserted above N / 20 first;
+* segment 0 equals the ``jump_process`` kernel bit for bit; the exact likelihood of immigration-death (M = 512, N = 256: std(r) <=
+  0.5, then |mean(r) - 1| <= 4.5 std(r) / sqrt(M)); kernel route against torch route on SIR (two-sample z <= 4.5); the edge rules;
+  the calls the kernel does not take; PMMH through ``_trace``; and the exact posterior of a one-parameter immigration-death model.
+
+The propagation reference costs a Python iteration per event, so N = 192 (three waves: the wave totals go through LDS at a count
+that is no power of two) runs on bd, sir, net4 and chain8 (S = 1, 2, 4, 8) and every network runs at N = 64, kinetic_chain8 (16
+reactions with rate laws, some 18 events a segment) there alone; the stage after the event loop does not depend on the reactions.  Every call runs with ``max_events <= 4096``."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import jump_filter_reference as ref
+import jump_process_reference as jref
+import particle_filter_reference as pref
+from reaction_networks import BD, SIR
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+TIMES = [0.0, 0.25, 0.25, 1.0]
+CASES = jref.cases()
+H1 = [[1.0, 0.5]]
+H2 = [[1.0, 1.0], [0.0, 1.0]]
+# (network, N, likelihood): observations sit near the start state, so that the filters stay alive
+LIKES = {
+    "poisson": ("poisson", 0.9, None), "gauss": ("gaussian", 25.0, None), "gauss_h": ("gaussian", 16.0, np.array(H1)),
+    "nb_h": ("nb", 5.0, 1.0, np.array(H2)), "gauss_wide": ("gaussian", 2500.0, None),   # wide: kinetic_chain8 is fed 50 molecules a unit time
+}
+RUN_LIST = [("bd", 64, "poisson"), ("sir", 64, "poisson"), ("net4", 64, "gauss"), ("chain8", 64, "gauss"), ("kinetic_chain8", 64, "gauss_wide"),
+            ("bd", 192, "poisson"), ("sir", 192, "gauss_h"), ("net4", 192, "poisson"), ("chain8", 192, "gauss"), ("sir", 192, "nb_h"),
+            ("sir", 192, "gauss")]
+
+
+def _key(k0, k1, dev=DEV):
+    return torch.from_numpy(np.array([k0, k1], dtype=np.uint32).view(np.int32)).to(dev)
+
+
+def _likelihood(spec):
+    from viforsdes_amd import GaussianObservationLikelihood, NegativeBinomialObservationLikelihood, PoissonObservationLikelihood
+    H = None if spec[-1] is None else torch.tensor(spec[-1], dtype=torch.float32)
+    if spec[0] == "gaussian":
+        return GaussianObservationLikelihood(variance=spec[1], obs_matrix=H)
+    if spec[0] == "poisson":
+        return PoissonObservationLikelihood(scale=spec[1], obs_matrix=H)
+    return NegativeBinomialObservationLikelihood(dispersion=spec[1], scale=spec[2], obs_matrix=H)
+
+
+def _counted(monkeypatch=None):
+    """A list that receives one entry per launch of the kernel through ``_hip.jump_particle_filter``."""
+    from viforsdes_amd import _hip
+    calls, real = [], _hip.jump_particle_filter
+    wrapped = lambda *a, **k: (calls.append(1), real(*a, **k))[1]
+    if monkeypatch is not None:
+        monkeypatch.setattr(_hip, "jump_particle_filter", wrapped)
+    return calls, real, wrapped
+
+
+_RUNS = {}
+
+
+def _cached(name, N, like_name):
+    """(net, theta fp32 [3, P], x0 [3, S], ys [K, O], likelihood spec, result, key) of one kernel-route run, made once."""
+    if (name, N, like_name) not in _RUNS:
+        from viforsdes_amd import Observations, ReactionNetworkSDE, _hip, jump_particle_filter
+        spec, x0, theta = CASES[name]
+        net = ReactionNetworkSDE(**spec)
+        xs, th = jref.per_path_inputs(x0, theta, 3, seed=len(name))
+        th = torch.from_numpy(th).float()
+        like = LIKES[like_name]
+        rng = np.random.default_rng(N)
+        base = np.asarray(x0, dtype=np.float64) if like[-1] is None else like[-1] @ np.asarray(x0, dtype=np.float64)
+        ys = np.round(base[None, :] + rng.integers(0, 3, size=(len(TIMES), len(base)))).astype(np.float64)
+        obs = Observations(times=torch.tensor(TIMES, dtype=torch.float64), values=torch.tensor(ys, dtype=torch.float32))
+        key = (0x9E3779B9 ^ N, 0x7F4A7C15 + len(name))
+        calls, real, wrapped = _counted()
+        _hip.jump_particle_filter = wrapped
+        try:
+            res = jump_particle_filter(net, obs.to(DEV), _likelihood(like), th.to(DEV), n_particles=N, initial_state=torch.from_numpy(xs).to(DEV),
+                                       return_particles=True, key=_key(*key), max_events=4096)
+        finally:
+            _hip.jump_particle_filter = real
+        assert calls == [1]                                         # the public function took the kernel route
+        assert res.particles.dtype == torch.int32 and res.events.dtype == torch.int32 and res.stopped.dtype == torch.int32
+        _RUNS[(name, N, like_name)] = (net, th, xs, ys, like, res, key)
+    return _RUNS[(name, N, like_name)]
+
+
+# ------------------------------------------------------------------------------------------------------------- 1. propagation
+@pytest.mark.parametrize("name,N,like_name", [r for r in RUN_LIST if r[2] != "nb_h" and r != ("sir", 192, "gauss")])
+def test_propagation_matches_float64_gillespie_on_the_kernels_previous_stage(name, N, like_name):
+    net, th, xs, ys, like, res, key = _cached(name, N, like_name)
+    tab = jref.tables(net)
+    rates = net.kernel_parameters(th.double()).numpy()
+    parts, anc, events = res.particles.cpu().numpy().astype(np.int64), res.ancestors.cpu().numpy().astype(np.int64), res.events.cpu().numpy()
+    M, K = parts.shape[:2]
+    assert int(res.stopped.sum()) == 0
+    flagged, checked = 0, []
+    for m in range(M):
+        for k in range(K):
+            start = np.repeat(xs[m][None], N, axis=0) if k == 0 else parts[m, k - 1][anc[m, k - 1]]
+            for j in range(N):
+                x, fired, status, near = ref.run_segment(tab, start[j], rates[m], TIMES[k - 1] if k else 0.0, TIMES[k], k, m * N + j, key, 4096)
+                assert status == 0
+                flagged += bool(near)
+                if not near:
+                    checked.append(bool(np.array_equal(x, parts[m, k, j])) and fired == events[m, k, j])
+    total = M * K * N
+    print(f"{name} N={N}: the reference flags {flagged} of {total} (particle, segment) pairs ({flagged / total:.1e}); "
+          f"{len(checked) - sum(checked)} of the other {len(checked)} differ; mean events {float(res.mean_events.mean()):.1f}")
+    assert flagged <= 2e-2 * total                                  # the reference's own share first: a cap, not a tolerance
+    assert all(checked)
+    assert events.sum() > total                                     # something happened
+    mean_events = events.reshape(M, K, N).mean(axis=2)
+    np.testing.assert_allclose(res.mean_events.cpu().numpy(), mean_events, rtol=1e-5, atol=1e-6)
+
+
+# --------------------------------------------------------------------------------------------------- 2. weights and summaries
+@pytest.mark.parametrize("name,N,like_name", RUN_LIST)
+def test_weights_and_summaries_match_float64_on_the_kernels_particles(name, N, like_name):
+    net, th, xs, ys, like, res, key = _cached(name, N, like_name)
+    parts = res.particles.double().cpu().numpy()
+    M, K = parts.shape[:2]
+    got = [t.double().cpu().numpy() for t in (res.increments, res.effective_sample_size, res.filtered_mean, res.filtered_std, res.log_weights)]
+    e_lw = e_inc = e_ess = e_mean = e_std = 0.0
+    for m in range(M):
+        for k in range(K):
+            lw = ref.log_weights(like, ys[k], parts[m, k])
+            inc, ess, mean, std, w = pref.observation_stage(lw, parts[m, k])
+            size = (w[:, None] * np.abs(parts[m, k])).sum(axis=0) / w.sum()          # weighted mean of |x|, per dim
+            scale = max(1.0, np.abs(lw[np.isfinite(lw)]).max())
+            e_lw = max(e_lw, float(np.abs(got[4][m, k] - lw).max()) / scale)
+            e_inc = max(e_inc, abs(got[0][m, k] - inc) / scale)
+            e_ess = max(e_ess, abs(got[1][m, k] - ess) / ess)
+            e_mean = max(e_mean, float((np.abs(got[2][m, k] - mean) / np.maximum(size, 1e-30)).max()))
+            e_std = max(e_std, float((np.abs(got[3][m, k] - std) / (std + 1e-2 * size + 1e-30)).max()))
+    print(f"{name} N={N} {like_name}: log-weights {e_lw:.2e}, increments {e_inc:.2e} (of max(1, |lw|), bound 1e-5), ESS {e_ess:.2e}, "
+          f"mean {e_mean:.2e}, std {e_std:.2e} (relative, bound 1e-4)")
+    assert e_lw <= 1e-5 and e_inc <= 1e-5
+    assert e_ess <= 1e-4 and e_mean <= 1e-4 and e_std <= 1e-4
+    total = res.increments.double().sum(dim=1)
+    assert torch.allclose(res.log_likelihood.double(), total, rtol=1e-6, atol=1e-5 * float(res.increments.abs().max()))
+
+
+# --------------------------------------------------------------------------------------------------------------- 3. ancestors
+@pytest.mark.parametrize("name,N,like_name", RUN_LIST)
+def test_ancestors_match_float64_systematic_resampling(name, N, like_name):
+    net, th, xs, ys, like, res, key = _cached(name, N, like_name)
+    parts = res.particles.double().cpu().numpy()
+    anc = res.ancestors.cpu().numpy().astype(np.int64)
+    M, K = parts.shape[:2]
+    u = pref.resampling_uniforms(M, K, key)
+    differ, low, worst = 0, float("inf"), 0
+    for m in range(M):
+        for k in range(K):
+            lw = ref.log_weights(like, ys[k], parts[m, k])
+            w = np.exp(lw - lw.max())
+            low = min(low, w.sum() ** 2 / (w * w).sum())
+            d = np.abs(anc[m, k] - pref.systematic_ancestors(w, u[m, k]))
+            worst, differ = max(worst, int(d.max())), differ + int((d != 0).sum())
+    print(f"{name} N={N} {like_name}: {differ} of {anc.size} ancestors differ from float64 ({differ / anc.size:.1e}), largest difference "
+          f"{worst}; smallest float64 ESS {low:.1f}")
+    assert low > N / 20                                            # there was something to compare
+    assert anc.min() >= 0 and anc.max() < N and (np.diff(anc, axis=-1) >= 0).all()      # never decrease in j
+    assert worst <= 1 and differ <= 1e-3 * anc.size
+
+
+# ------------------------------------------------------------------------------------------------------- 4. other kernel checks
+@pytest.mark.parametrize("name", ["bd", "autoreg"])
+def test_segment_zero_is_the_jump_process_kernel(name, monkeypatch):
+    from viforsdes_amd import Observations, PoissonObservationLikelihood, ReactionNetworkSDE, jump_particle_filter, jump_process
+    spec, x0, theta = CASES[name]
+    net = ReactionNetworkSDE(**spec)
+    M, N = 3, 64
+    xs, th = jref.per_path_inputs(x0, theta, M, seed=4)
+    xs, th = torch.from_numpy(xs).to(DEV), torch.from_numpy(th).float().to(DEV)
+    obs = Observations(times=torch.tensor([0.7, 1.1], dtype=torch.float64), values=torch.tensor([x0, x0], dtype=torch.float32)).to(DEV)
+    calls = _counted(monkeypatch)[0]
+    res = jump_particle_filter(net, obs, PoissonObservationLikelihood(), th, n_particles=N, initial_state=xs, return_particles=True,
+                               key=_key(7, 8), max_events=4096)
+    assert calls == [1]
+    jp = jump_process(net, xs.repeat_interleave(N, 0), th.repeat_interleave(N, 0), obs.times[:1], key=_key(7, 8), max_events=4096)
+    assert torch.equal(res.particles[:, 0].reshape(M * N, -1), jp.states[:, 0])
+    assert torch.equal(res.events[:, 0].reshape(-1), jp.n_events) and bool(jp.complete.all()) and int(jp.n_events.sum()) > M * N
+
+
+def _immigration_death(M, dtype=torch.float32):
+    from viforsdes_amd import Observations, PoissonObservationLikelihood, ReactionNetworkSDE
+    obs = Observations(times=torch.tensor(ref.IMMIGRATION_DEATH_TIMES, dtype=torch.float64),
+                       values=torch.tensor(ref.IMMIGRATION_DEATH_COUNTS, dtype=dtype)[:, None]).to(DEV)
+    return ReactionNetworkSDE(**BD), obs, PoissonObservationLikelihood(), torch.tensor([10.0, 0.5, 0.0], dtype=dtype, device=DEV).expand(M, 3)
+
+
+def test_likelihood_of_immigration_death_is_unbiased_on_the_device(monkeypatch):
+    from viforsdes_amd import jump_particle_filter
+    M, N = 512, 256
+    net, obs, like, theta = _immigration_death(M)
+    exact = ref.immigration_death_log_likelihood(10.0, 0.5, 30, ref.IMMIGRATION_DEATH_TIMES, ref.IMMIGRATION_DEATH_COUNTS)
+    calls = _counted(monkeypatch)[0]
+    res = jump_particle_filter(net, obs, like, theta, n_particles=N, key=_key(21, 22), max_events=4096)
+    assert calls == [1] and int(res.stopped.sum()) == 0
+    r = np.exp(res.log_likelihood.double().cpu().numpy() - exact)
+    sd = r.std(ddof=1)
+    print(f"immigration-death on the device: exact {exact:.4f}, std(r) {sd:.3f}, z {(r.mean() - 1.0) / (sd / math.sqrt(M)):.2f}, "
+          f"events per segment {float(res.mean_events.mean()):.1f}")
+    assert sd <= 0.5
+    assert abs(r.mean() - 1.0) <= 4.5 * sd / math.sqrt(M)
+
+
+def test_kernel_route_and_torch_route_agree_on_sir(monkeypatch):
+    from viforsdes_amd import Observations, PoissonObservationLikelihood, ReactionNetworkSDE, jump_particle_filter
+    from viforsdes_amd.inference import jump_filter as jf
+    M, N = 256, 128
+    net = ReactionNetworkSDE(**SIR)
+    obs = Observations(times=torch.tensor(TIMES, dtype=torch.float64),
+                       values=torch.tensor([[95.0, 5.0], [93.0, 6.0], [92.0, 7.0], [84.0, 12.0]])).to(DEV)
+    theta = torch.tensor([0.02, 0.5], device=DEV).expand(M, 2)
+    run = lambda k: jump_particle_filter(net, obs, PoissonObservationLikelihood(), theta, n_particles=N, key=_key(*k),
+                                         max_events=4096).log_likelihood.double().cpu().numpy()
+    calls = _counted(monkeypatch)[0]
+    a = run((31, 32))
+    monkeypatch.setattr(jf, "HIP_JUMP_FILTER", False)
+    b = run((33, 34))
+    assert calls == [1]
+    z = abs(a.mean() - b.mean()) / math.sqrt(a.var(ddof=1) / M + b.var(ddof=1) / M)
+    print(f"SIR: mean log p^ kernel {a.mean():.4f}, torch {b.mean():.4f}, two-sample z {z:.2f}")
+    assert z <= 4.5
+
+
+def _bd_run(theta, times, ys, like=None, N=64, max_events=4096):
+    from viforsdes_amd import Observations, PoissonObservationLikelihood, ReactionNetworkSDE, jump_particle_filter
+    obs = Observations(times=torch.tensor(times, dtype=torch.float64), values=torch.tensor(ys, dtype=torch.float32)).to(DEV)
+    return jump_particle_filter(ReactionNetworkSDE(**BD), obs, like or PoissonObservationLikelihood(), torch.tensor(theta, device=DEV),
+                                n_particles=N, initial_state=torch.tensor([5]), return_particles=True, key=_key(1, 2), max_events=max_events)
+
+
+def test_edge_rules_on_the_device(monkeypatch):
+    from viforsdes_amd import GaussianObservationLikelihood, Observations, PoissonObservationLikelihood, ReactionNetworkSDE, jump_particle_filter
+    calls = _counted(monkeypatch)[0]
+    N, inf = 64, float("inf")
+    # a NaN observation: a dead filter, identity ancestors, NaN moments; the particles carry on
+    res = _bd_run([4.0, 0.5, 0.0], [0.5, 1.0, 1.5], [[6.0], [float("nan")], [7.0]], GaussianObservationLikelihood(variance=4.0))
+    assert bool(torch.isneginf(res.log_weights[0, 1]).all()) and res.increments[0, 1] == -inf and res.effective_sample_size[0, 1] == 0
+    assert bool(torch.isnan(res.filtered_mean[0, 1]).all()) and bool(torch.isnan(res.filtered_std[0, 1]).all())
+    assert res.ancestors[0, 1].tolist() == list(range(N)) and res.log_likelihood[0] == -inf
+    assert bool(torch.isfinite(res.increments[0, [0, 2]]).all()) and int(res.stopped.sum()) == 0 and int(res.events[0, 2].sum()) > 0
+    # the event cap: stopped == N, a dead filter whose particles carry on from the state they stopped in
+    res = _bd_run([200.0, 0.1, 0.0], [0.0, 10.0, 20.0], [[5.0], [30.0], [40.0]], max_events=3)
+    assert res.stopped.tolist() == [[0, N, N]] and res.events[0].tolist() == [[0] * N, [3] * N, [3] * N]
+    assert res.increments[0, 1:].tolist() == [-inf] * 2 and res.ancestors[0, 1].tolist() == list(range(N))
+    assert bool(((res.particles[0, 2] - res.particles[0, 1]).abs().sum(dim=-1) > 0).all()) and res.mean_events.tolist() == [[0.0, 3.0, 3.0]]
+    # a negative or NaN theta row: status 2 throughout
+    res = _bd_run([[4.0, 0.5, 0.0], [4.0, -0.5, 0.0], [float("nan"), 0.5, 0.0]], [0.0, 0.5, 1.0], [[5.0], [6.0], [6.0]])
+    assert res.stopped.tolist() == [[0] * 3, [N] * 3, [N] * 3] and bool(torch.isfinite(res.log_likelihood[0]))
+    assert res.log_likelihood[1:].tolist() == [-inf] * 2 and int(res.events[1:].sum()) == 0 and bool((res.particles[1:] == 5).all())
+    # a0 == 0: absorbed, the particle stays
+    obs = Observations(times=torch.tensor([0.0, 1.0, 2.0], dtype=torch.float64), values=torch.tensor([[40.0, 0.0]] * 3)).to(DEV)
+    res = jump_particle_filter(ReactionNetworkSDE(**SIR), obs, PoissonObservationLikelihood(), torch.tensor([0.01, 0.2], device=DEV),
+                               n_particles=N, return_particles=True, key=_key(1, 2))
+    assert bool((res.particles == torch.tensor([40, 0], dtype=torch.int32, device=DEV)).all()) and int(res.events.sum()) == 0
+    assert int(res.stopped.sum()) == 0 and bool(torch.isfinite(res.log_likelihood).all())
+    # a copy number that fp32 cannot hold survives resampling: the LDS rows hold the integer
+    big = 2 ** 30 - 1
+    obs = Observations(times=torch.tensor([0.0, 0.0], dtype=torch.float64), values=torch.tensor([[float(big), 0.0]] * 2)).to(DEV)
+    res = jump_particle_filter(ReactionNetworkSDE(**SIR), obs, GaussianObservationLikelihood(variance=1.0), torch.tensor([0.0, 0.0], device=DEV),
+                               n_particles=N, initial_state=torch.tensor([big, 0]), return_particles=True, key=_key(1, 2))
+    assert bool((res.particles[..., 0] == big).all())
+    assert calls == [1] * 5
+    # the same key gives the same result, another key another
+    a, b = (_bd_run([4.0, 0.5, 0.0], [0.5, 1.0], [[6.0], [7.0]]) for _ in range(2))
+    assert torch.equal(a.particles, b.particles) and torch.equal(a.log_likelihood, b.log_likelihood) and torch.equal(a.ancestors, b.ancestors)
+
+
+def test_calls_the_kernel_does_not_take_run_the_torch_route(monkeypatch):
+    from viforsdes_amd import Observations, PoissonObservationLikelihood, ReactionNetworkSDE, _hip, jump_particle_filter
+    calls = _counted(monkeypatch)[0]
+    like = PoissonObservationLikelihood()
+    obs1 = Observations(times=torch.tensor([0.1, 0.2], dtype=torch.float64), values=torch.tensor([[5.0], [6.0]])).to(DEV)
+    bd = ReactionNetworkSDE(**BD)
+    theta = torch.tensor([[4.0, 0.5, 0.0]] * 2, device=DEV)
+    cap = _hip.jump_filter_max_particles(1, 3, False)
+    assert cap % 64 == 0 and cap >= 64
+    nine = ReactionNetworkSDE(reactants=[[0] * 9] + [[int(i == k) for i in range(9)] for k in range(9)],
+                              products=[[1] + [0] * 8] + [[int(i == k + 1) for i in range(9)] for k in range(9)])
+    obs9 = Observations(times=torch.tensor([0.1, 0.2], dtype=torch.float64), values=torch.ones(2, 9)).to(DEV)
+    runs = [(bd, obs1, theta, 96, 1), (bd, obs1, theta, cap + 64, 1), (nine, obs9, torch.ones(2, 10, device=DEV), 64, 9)]
+    for net, obs, th, N, S in runs:
+        res = jump_particle_filter(net, obs, like, th, n_particles=N, initial_state=torch.ones(S, dtype=torch.int64), return_particles=True,
+                                   key=_key(3, 4), max_events=256)
+        assert res.particles.shape == (2, 2, N, S) and res.particles.dtype == torch.int32 and res.particles.is_cuda
+        assert res.ancestors.shape == (2, 2, N) and res.ancestors.dtype == torch.int32 and res.events.dtype == torch.int32
+        assert res.stopped.shape == (2, 2) and res.stopped.dtype == torch.int32 and res.mean_events.shape == (2, 2)
+        assert res.log_likelihood.shape == (2,) and res.log_likelihood.dtype == torch.float32 and res.log_weights.shape == (2, 2, N)
+        assert res.filtered_mean.shape == (2, 2, S) and bool(torch.isfinite(res.log_likelihood).all())
+    assert calls == []
+    res = jump_particle_filter(bd, obs1, like, theta, n_particles=64, initial_state=torch.ones(1), return_particles=True, key=_key(3, 4))
+    assert calls == [1] and res.particles.shape == (2, 2, 64, 1) and res.log_likelihood.dtype == torch.float32
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5. PMMH
+def test_pmmh_on_the_device_launches_the_jump_filter(monkeypatch):
+    from viforsdes_amd import Prior, PriorType, jump_particle_filter, particle_mcmc
+    from viforsdes_amd.inference import particle_mcmc as mc
+    C, N, n_it = 16, 64, 12
+    net, obs, like, _ = _immigration_death(C)
+    prior = Prior(type=PriorType.LOG_NORMAL, mean=0.0, std=2.0, dim=3)
+    g = torch.Generator().manual_seed(3)
+    theta0 = (torch.tensor([10.0, 0.5, 0.01]) * (0.8 + 0.4 * torch.rand(C, 3, generator=g))).to(DEV)
+    key = _key(11, 12)
+    calls, trace = _counted(monkeypatch)[0], []
+    res = particle_mcmc(net, obs, like, prior, None, theta0, n_it, n_particles=N, theta_positive_dims=(0, 1, 2), key=key, dynamics="jump",
+                        max_events=4096, _trace=trace)
+    assert calls == [1] * n_it and len(trace) == n_it and res.samples.shape == (n_it, C, 3) and res.samples.is_cuda
+    before = torch.full((C,), float("-inf"), dtype=torch.float64, device=DEV)
+    undecided = 0
+    for i, t in enumerate(trace):
+        assert torch.equal(t["filter_key"].cpu(), mc.filter_key(i, key).cpu())
+        direct = jump_particle_filter(net, obs, like, t["theta_prop"], n_particles=N, key=t["filter_key"], max_events=4096)
+        assert torch.equal(direct.log_likelihood, t["loglik"].reshape(-1))              # bit for bit
+        target = t["prop_log_prior"].double() + mc.log_mean_exp(t["loglik"].double())
+        log_u = mc.acceptance_log_uniforms(C, i, key).to(DEV)
+        want = ~torch.isnan(target) if i == 0 else torch.isfinite(target) & (log_u < target - before)
+        decidable = torch.ones_like(want) if i == 0 else ((target - before - log_u).abs() > 1e-4) | ~torch.isfinite(target)
+        undecided += int((~decidable).sum())
+        assert torch.equal(t["accept"][decidable], want[decidable])
+        before = torch.where(t["accept"], target, before)
+        assert torch.allclose(t["cur_log_target"].double(), before, rtol=1e-5, atol=1e-4)
+    assert undecided <= 2
+    assert bool(torch.isfinite(res.log_likelihood).all())
+    with pytest.raises(ValueError):
+        particle_mcmc(net, obs, like, prior, None, theta0, n_it, n_particles=N, theta_positive_dims=(0, 1, 2), dynamics="jump", return_paths=True)
+
+
+def _birth_posterior(death, x0, times, ys, grid, prior):
+    """The exact posterior of the birth rate on ``grid`` (uniform) for immigration-death observed with Poisson noise: the forward
+    algorithm on 200 states.  The death part of a transition (binomial thinning) does not depend on the birth rate, so its matrix is
+    formed once per time gap; the immigration part is a convolution with a Poisson vector."""
+    size = 200
+    gaps = sorted({round(b - a, 12) for a, b in zip([0.0] + list(times[:-1]), times) if b > a})
+    thin = {}
+    for dt in gaps:
+        q = math.exp(-death * dt)                                   # a molecule survives the gap
+        thin[dt] = np.array([[math.comb(n, k) * q ** k * (1 - q) ** (n - k) if k <= n else 0.0 for k in range(size)] for n in range(size)])
+    states = np.arange(size, dtype=np.float64)
+    lam = np.maximum(states, 1e-6)
+    lgam = np.array([math.lgamma(k + 1.0) for k in range(size)])
+    logp = np.zeros(len(grid))
+    for g, birth in enumerate(grid):
+        alpha = np.zeros(size)
+        alpha[int(x0)] = 1.0
+        t_prev, ll = 0.0, 0.0
+        for t, y in zip(times, ys):
+            dt = round(t - t_prev, 12)
+            if dt > 0:
+                mu = birth / death * (1.0 - math.exp(-death * dt))
+                pois = np.exp(states * math.log(mu) - mu - lgam)
+                alpha = np.convolve(alpha @ thin[dt], pois)[:size]
+            t_prev = t
+            alpha = alpha * np.exp(y * np.log(lam) - lam - math.lgamma(y + 1.0))
+            ll += math.log(alpha.sum())
+            alpha = alpha / alpha.sum()
+        logp[g] = ll
+    logp = logp + prior.log_prob(torch.tensor(grid, dtype=torch.float64)[:, None]).reshape(-1).numpy()
+    p = np.exp(logp - logp.max())
+    return p / p.sum(), logp
+
+
+def test_exact_posterior_of_the_birth_rate(monkeypatch):
+    from viforsdes_amd import Observations, PoissonObservationLikelihood, Prior, PriorType, ReactionNetworkSDE, particle_mcmc
+    net = ReactionNetworkSDE(reactants=[[0], [1]], products=[[1], [0]], rate_constants=["birth", 0.5])
+    times, ys = ref.IMMIGRATION_DEATH_TIMES, ref.IMMIGRATION_DEATH_COUNTS
+    prior = Prior(type=PriorType.LOG_NORMAL, mean=2.0, std=1.0, dim=1)
+    grid = np.linspace(0.01, 40.0, 1000)
+    p, logp = _birth_posterior(0.5, 30, times, ys, grid, prior)
+    # the fast forward algorithm against the one built on immigration_death_pmf rows, at one grid point
+    slow = ref.immigration_death_log_likelihood(grid[100], 0.5, 30, times, ys)
+    fast = logp[100] - float(prior.log_prob(torch.tensor([[grid[100]]], dtype=torch.float64)).reshape(-1)[0])
+    assert abs(slow - fast) <= 1e-9
+    assert p[0] < 1e-6 * p.max() and p[-1] < 1e-6 * p.max()        # the grid holds the posterior
+    exact_mean = float((p * grid).sum())
+    exact_std = math.sqrt(float((p * (grid - exact_mean) ** 2).sum()))
+    C, N = 64, 128
+    rng = np.random.default_rng(5)
+    start = rng.choice(grid, size=C, p=p) + rng.uniform(-0.5, 0.5, size=C) * (grid[1] - grid[0])     # stationary from iteration 0
+    obs = Observations(times=torch.tensor(times, dtype=torch.float64), values=torch.tensor(ys, dtype=torch.float32)[:, None]).to(DEV)
+    calls = _counted(monkeypatch)[0]
+    scale = torch.tensor([[exact_std / exact_mean]])                # the posterior's spread in log theta
+    res = particle_mcmc(net, obs, PoissonObservationLikelihood(), prior, None, torch.tensor(start, dtype=torch.float32, device=DEV)[:, None], 200,
+                        warmup=0, n_particles=N, theta_positive_dims=(0,), proposal_scale_tril=scale, key=_key(41, 42), dynamics="jump",
+                        max_events=4096)
+    assert calls == [1] * 200
+    rate = float(res.acceptance_rate.mean())
+    print(f"birth rate: exact mean {exact_mean:.4f} (std {exact_std:.3f}), chains {float(res.mean[0]):.4f} +- "
+          f"{float(res.mean_standard_error[0]):.4f}, acceptance {rate:.3f}, dead {res.n_filters_dead}")
+    assert abs(float(res.mean[0]) - exact_mean) <= 4.5 * float(res.mean_standard_error[0])
+    assert 0.05 < rate < 0.9

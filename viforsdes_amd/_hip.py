@@ -78,7 +78,7 @@ EXPORTS = (
     "vsde_residual_particle_filter", "vsde_crn_residual_particle_filter", "vsde_crn_kinetic_residual_particle_filter",
     "vsde_residual_filter_replay", "vsde_crn_residual_filter_replay", "vsde_crn_kinetic_residual_filter_replay",
     "vsde_residual_anchored_replay", "vsde_crn_residual_anchored_replay", "vsde_crn_kinetic_residual_anchored_replay",
-    "vsde_crn_jump_process", "vsde_crn_kinetic_jump_process",
+    "vsde_crn_jump_process", "vsde_crn_kinetic_jump_process", "vsde_crn_jump_particle_filter", "vsde_crn_kinetic_jump_particle_filter",
     "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
@@ -578,6 +578,63 @@ def guided_particle_filter(kind: str, x0, theta, obs_rows, obs_values, obs_matri
     bridge (vsde_residual_particle_filter)."""
     return _particle_filter("residual_particle_filter" if residual else "guided_particle_filter", True, kind, x0, theta, obs_rows, obs_values, obs_matrix, variance, key,
                             time_step, n_particles, positive_dims, network, return_particles, store)
+
+
+def jump_filter_max_particles(state_dim: int, n_reactions: int, kinetic: bool = False) -> int:
+    """The largest ``n_particles`` (a multiple of 64) the jump-process filter kernel takes for a network of ``state_dim`` species
+    and ``n_reactions`` reactions, with rate laws or without (csrc/vsde_jump_filter.hip: jf_max_n): every instantiation fits the
+    128 registers of a 1024-thread workgroup, so 1024 throughout today."""
+    if not (1 <= state_dim <= CRN_MAX_SPECIES and 1 <= n_reactions <= CRN_MAX_REACTIONS):
+        raise ValueError(f"jump_filter_max_particles: {state_dim} species / {n_reactions} reactions outside 1..{CRN_MAX_SPECIES} / "
+                         f"1..{CRN_MAX_REACTIONS}")
+    return PF_MAX_PARTICLES
+
+
+def jump_particle_filter(x0, theta, obs_times, obs_values, obs_matrix, variance, key, max_events: int, n_particles: int,
+                         network=None, return_particles: bool = False):
+    """Bootstrap particle filters on the exact jump process of a reaction network (include/vsde_hip.h:
+    vsde_crn_jump_particle_filter), one per row of theta fp32 [M, P] (the effective constants [M, 2R] for a CrnKineticRoute) from
+    the start states x0 int32 [M, S], against obs_values fp32 [K, O] at obs_times float64 [K], with a Gaussian observation term
+    (obs_matrix [O, S] or None; ``variance``: a number) or a count term (``variance``: the likelihood's ``CountKernelTerms``); key:
+    2 int32 words; everything on the device.  Returns (log_likelihood [M], increments [M, K], effective_sample_size [M, K],
+    filtered_mean [M, K, S], filtered_std [M, K, S], stopped int32 [M, K], mean_events [M, K], and with ``return_particles``, else
+    None: particles int32 [M, K, N, S], ancestors int32 [M, K, N], log_weights [M, K, N], events int32 [M, K, N])."""
+    lib = load()
+    dev = _require_hip(x0, theta, obs_times, obs_values, obs_matrix, key)
+    if x0.dtype != torch.int32 or x0.ndim != 2 or obs_times.dtype != torch.float64 or obs_times.ndim != 1:
+        raise ValueError("jump_particle_filter: x0 must be an int32 [M, S] tensor and obs_times a float64 [K] tensor")
+    if key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2:
+        raise ValueError("jump_particle_filter: key must be two int32 words")
+    x0, theta, obs_times, obs_values, key = x0.contiguous(), _f32c(theta), obs_times.contiguous(), _f32c(obs_values), key.contiguous()
+    obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
+    if theta.ndim != 2 or theta.shape[0] != x0.shape[0] or obs_values.ndim != 2 or obs_values.shape[0] != obs_times.shape[0]:
+        raise ValueError(f"jump_particle_filter: x0 [M, S], theta [M, P], obs_values [K, O], obs_times [K] expected, got "
+                         f"{tuple(x0.shape)}, {tuple(theta.shape)}, {tuple(obs_values.shape)}, {tuple(obs_times.shape)}")
+    M, S = x0.shape
+    K, O = obs_values.shape
+    N = int(n_particles)
+    if obs_matrix is not None and tuple(obs_matrix.shape) != (O, S):
+        raise ValueError(f"jump_particle_filter: obs_matrix must be [{O}, {S}], got {tuple(obs_matrix.shape)}")
+    with torch.cuda.device(dev):
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        loglik, incr, ess = torch.empty(M, **f32), torch.empty(M, K, **f32), torch.empty(M, K, **f32)
+        mean, std = torch.empty(M, K, S, **f32), torch.empty(M, K, S, **f32)
+        stopped, mean_events = torch.empty(M, K, **i32), torch.empty(M, K, **f32)
+        keep = return_particles and 0 < N <= PF_MAX_PARTICLES   # a bad N is the entry point's to refuse: allocate nothing for it
+        particles = torch.empty(M, K, N, S, **i32) if keep else None
+        ancestors, events = (torch.empty(M, K, N, **i32), torch.empty(M, K, N, **i32)) if keep else (None, None)
+        log_weights = torch.empty(M, K, N, **f32) if keep else None
+        prefix, term = _observation_term(variance, K, dev)
+        if prefix:      # (lik_kind, scale, dispersion, row_const) -> lik_kind, variance, scale, dispersion, row_const
+            term = (term[0], ctypes.c_double(1.0)) + term[1:]
+        else:
+            term = (ctypes.c_int(0),) + term + (ctypes.c_double(1.0), ctypes.c_double(1.0), _ptr(None))
+        _call(*_sde_entry(lib, "jump_particle_filter", "reaction_network", network), ctypes.c_int(M), ctypes.c_int(N), ctypes.c_int(S),
+              ctypes.c_int(theta.shape[1]), ctypes.c_int(K), ctypes.c_int(O), _ptr(x0), _ptr(theta), _ptr(obs_times), _ptr(obs_values),
+              _ptr(obs_matrix), *term, _ptr(key), ctypes.c_int(int(max_events)), _ptr(loglik), _ptr(incr), _ptr(ess), _ptr(mean),
+              _ptr(std), _ptr(stopped), _ptr(mean_events), _ptr(particles), _ptr(ancestors), _ptr(log_weights), _ptr(events),
+              _stream(dev))
+    return loglik, incr, ess, mean, std, stopped, mean_events, particles, ancestors, log_weights, events
 
 
 def _replay_inputs(who: str, obs_rows, words_ok: bool, words: str, guided: bool, model, state_dim: int):

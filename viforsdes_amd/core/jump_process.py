@@ -25,7 +25,9 @@ that never ends), the reaction is the smallest j with ``u2 * a0 < c_j`` (none af
 
 Stream: ``w = philox4x32_10(counter {e >> 1, 0, b, 7}, key)``, ``u1 = U(w[2 (e & 1)])``, ``u2 = U(w[2 (e & 1) + 1])`` with
 ``U(w) = ((w >> 8) + 0.5) * 2^-24`` formed in fp32.  Fourth counter words 0..6 are the path normals, the resampling uniforms, the
-smoother's final draw and the four PMMH draws; 7 is this stream.  The same key gives the same result on a route.
+smoother's final draw and the four PMMH draws; 7 is this stream.  The same key gives the same result on a route.  The free second
+counter word carries the segment index of the jump-process particle filter (``jump_segment``, inference/jump_filter.py), whose
+segment 0 is this process.
 
 The torch code below is the specification.  It is vectorised over the B paths with a live mask, one Python iteration per event,
 and runs on any device in theta's dtype.  A ``kernel_compatible`` network with CUDA fp32 theta runs ONE HIP kernel instead
@@ -178,6 +180,54 @@ def _jump_process_torch(net, x0: Tensor, rates: Tensor, times: Tensor, key: Tens
         n_events = n_events + live.to(torch.int32)
     status[live] = STATUS_EVENT_CAP
     return states, n_events, status, ev_t, ev_r
+
+
+def jump_segment(net, x: Tensor, rates: Tensor, t_start: float, t_end: float, segment: int, paths: Tensor, key: Tensor,
+                 max_events: int) -> tuple[Tensor, Tensor, Tensor]:
+    """The event rule of the module docstring over ONE segment ``(t_start, t_end]``, for the jump-process particle filter
+    (inference/jump_filter.py): the integer states ``x [B, S]`` (int64) with the effective constants ``rates``, path b = ``paths
+    [B]`` (int64) on the uniforms of ``philox4x32_10({e >> 1, segment, paths[b], 7}, key)``.  The float64 clock starts at exactly
+    ``t_start`` (the waiting times are memoryless) and the event counter at 0; a path ends the segment as soon as ``t_end < t +
+    tau`` (``a0 == 0``: at once, absorbed), stops with status 2 at an invalid propensity and with status 1 once it has fired
+    ``max_events`` events short of ``t_end``; a stopped path keeps the state it stopped in.  Returns ``(x [B, S] int64, n_events
+    [B] int32, status [B] int32)``.  Segment 0 from ``t_start = 0`` is ``jump_process`` read at ``[t_end]``."""
+    dev, dtype = rates.device, rates.dtype
+    B, R = x.shape[0], net.num_reactions
+    k0, k1 = _key_words(key)
+    nu = torch.tensor(net.change, dtype=torch.int64, device=dev)
+    t = torch.full((B,), float(t_start), dtype=torch.float64, device=dev)
+    n_events = torch.zeros(B, dtype=torch.int32, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    live = torch.ones(B, dtype=torch.bool, device=dev)
+    zero = torch.zeros_like(paths)
+    inf = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
+    w = None
+    for e in range(max_events):
+        if not bool(live.any()):
+            break
+        a = jump_propensities(net, x, rates)
+        c = [a[:, 0]]
+        for j in range(1, R):
+            c.append(c[-1] + a[:, j])
+        c = torch.stack(c, dim=-1)
+        a0 = c[:, -1]
+        bad = live & ((~(a >= 0) | torch.isinf(a)).any(dim=-1) | torch.isinf(a0))
+        status[bad] = STATUS_INVALID
+        live = live & ~bad
+        if e % 2 == 0:
+            w = philox4x32_10(zero + (e >> 1), zero + int(segment), paths, zero + STREAM_WORD, k0, k1)
+        u1, u2 = _uniform(w[2 * (e & 1)], dtype), _uniform(w[2 * (e & 1) + 1], dtype)
+        t_next = torch.where(a0 == 0, inf, t + (-torch.log(u1) / a0).to(torch.float64))
+        live = live & ~(t_end < t_next)
+        below = (u2 * a0).unsqueeze(-1) < c
+        first = below.to(torch.int8).argmax(dim=-1)
+        last_positive = (R - 1) - (a > 0).flip(-1).to(torch.int8).argmax(dim=-1)
+        j = torch.where(below.any(dim=-1), first, last_positive)
+        x = torch.where(live.unsqueeze(-1), x + nu[j], x)
+        t = torch.where(live, t_next, t)
+        n_events = n_events + live.to(torch.int32)
+    status[live] = STATUS_EVENT_CAP
+    return x, n_events, status
 
 
 def _rows(name: str, t: Tensor, width: int, what: str) -> Tensor:

@@ -405,6 +405,29 @@ def _segment_propagator(sde, obs, like, theta, dt, pos, bridge, residual):
     return advance
 
 
+def observation_stage(lw: Tensor, xm: Tensor, k: int, key: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """What a filter does at observation ``k`` once the log-weights ``lw [M, N]`` (no NaN) of its particles ``xm [M, N, S]`` (in the
+    dtype of ``lw``) are formed, stated once for ``particle_filter`` and ``jump_particle_filter``: ``(increment [M], ESS [M],
+    weighted mean [M, S], weighted std [M, S], ancestors [M, N] int64)`` by the rule of the module docstring, with the dead-filter
+    rule (increment -inf, ESS 0, NaN moments, ancestors = identity)."""
+    M, N = lw.shape
+    neg_inf = torch.tensor(float("-inf"), device=lw.device, dtype=lw.dtype)
+    slot = torch.arange(N, device=lw.device)
+    mx = lw.max(dim=1, keepdim=True).values
+    dead = torch.isneginf(mx)
+    w = torch.exp(lw - torch.where(dead, torch.zeros_like(mx), mx))
+    s1, s2 = w.sum(dim=1), (w * w).sum(dim=1)
+    has = (w > 0)[..., None]
+    mean = torch.where(has, w[..., None] * xm, torch.zeros_like(xm)).sum(dim=1) / s1[:, None]
+    dx = xm - mean[:, None, :]
+    var = torch.where(has, w[..., None] * dx * dx, torch.zeros_like(xm)).sum(dim=1) / s1[:, None]
+    incr = torch.where(dead[:, 0], neg_inf, mx[:, 0] + torch.log(s1) - math.log(N))
+    ess = torch.where(dead[:, 0], torch.zeros_like(s1), s1 * s1 / s2)
+    safe = torch.where(dead, torch.ones_like(w), w)          # a dead filter keeps its particles: its row is overwritten below
+    anc = systematic_ancestors(safe, resampling_uniforms(M, k, key))
+    return incr, ess, mean, var.sqrt(), torch.where(dead, slot[None, :], anc)
+
+
 def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, bridge=False, residual=False) -> ParticleFilterResult:
     dev, dtype = theta.device, theta.dtype
     M, P = theta.shape
@@ -415,7 +438,6 @@ def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, 
     th = theta[:, None, :].expand(M, N, P).reshape(M * N, P)
     advance = _segment_propagator(sde, obs, like, theta, dt, pos, bridge, residual)
     b = torch.arange(M * N, device=dev, dtype=torch.int64)          # slot j of filter m draws the normals of path m N + j
-    slot = torch.arange(N, device=dev)
     neg_inf = torch.tensor(float("-inf"), device=dev, dtype=dtype)
     incr, ess, means, stds, parts, ancs, lws = [], [], [], [], [], [], []
     t = 0
@@ -427,22 +449,12 @@ def _torch_filter(sde, obs, like, theta, dt, N, x0, pos, return_particles, key, 
             lw = lw + lr
         lw = lw.reshape(M, N)
         lw = torch.where(torch.isnan(lw), neg_inf, lw)
-        mx = lw.max(dim=1, keepdim=True).values
-        dead = torch.isneginf(mx)
-        w = torch.exp(lw - torch.where(dead, torch.zeros_like(mx), mx))
-        s1, s2 = w.sum(dim=1), (w * w).sum(dim=1)
         xm = x.reshape(M, N, S)
-        has = (w > 0)[..., None]
-        mean = torch.where(has, w[..., None] * xm, torch.zeros_like(xm)).sum(dim=1) / s1[:, None]
-        dx = xm - mean[:, None, :]
-        var = torch.where(has, w[..., None] * dx * dx, torch.zeros_like(xm)).sum(dim=1) / s1[:, None]
-        incr.append(torch.where(dead[:, 0], neg_inf, mx[:, 0] + torch.log(s1) - math.log(N)))
-        ess.append(torch.where(dead[:, 0], torch.zeros_like(s1), s1 * s1 / s2))
+        inc_k, ess_k, mean, std, anc = observation_stage(lw, xm, k, key)
+        incr.append(inc_k)
+        ess.append(ess_k)
         means.append(mean)
-        stds.append(var.sqrt())
-        safe = torch.where(dead, torch.ones_like(w), w)          # a dead filter keeps its particles: its row is overwritten below
-        anc = systematic_ancestors(safe, resampling_uniforms(M, k, key))
-        anc = torch.where(dead, slot[None, :], anc)
+        stds.append(std)
         if return_particles:
             parts.append(xm)
             ancs.append(anc.to(torch.int32))

@@ -77,7 +77,15 @@ GPU and follows the dtype of ``initial_theta``.  Where ``particle_filter`` takes
 rate-law map of a kinetic network, and the filter launch with the device key the step kernel wrote.  With paths the same kernel
 draws the record of every chain it accepts from the particles and ancestors the filter launch stored (buffers allocated once), and
 ONE replay launch after the loop (csrc/vsde_anchored.hip: ar_kernel, a thread per (observation, record)) turns the kept records
-into paths.  ``HIP_MCMC = False`` forces the torch step (around whatever route the filter takes) for A/B."""
+into paths.  ``HIP_MCMC = False`` forces the torch step (around whatever route the filter takes) for A/B.
+
+``dynamics="jump"`` (a ``ReactionNetworkSDE``).  Everything above holds with ONE thing replaced: the estimator of step 2 is
+``jump_particle_filter`` (inference/jump_filter.py), the bootstrap filter whose particles are exact trajectories of the network's
+jump process, under the same per-iteration key.  The chains then sample the exact theta posterior of the jump process itself
+(Golightly and Wilkinson 2011): there is no grid, so ``time_step`` and ``positive_dims`` are not used, ``proposal`` must be
+``"bootstrap"``, the start state must hold integers, and paths are not kept (``return_paths=True`` raises).  Both loops take it:
+the torch loop through its estimator slot, the kernel loop by launching the jump filter's kernel where it launches the SDE
+filter's, so an iteration is still the step kernel and one filter launch."""
 from __future__ import annotations
 
 import math
@@ -97,6 +105,7 @@ HIP_MCMC = True   # set False to force the torch step (A/B tests); the filter ke
 DEFAULT_TARGET_ACCEPT = 0.15
 COVARIANCE_JITTER = 1e-8
 DEFAULT_SCALE_FLOOR = 1e-3
+DYNAMICS = ("diffusion", "jump")   # what the filter propagates: the Euler-Maruyama SDE, or the exact jump process of a reaction network
 DEAD_PATH = 0xFFFFFFFF   # noise_path of a record without a path
 _ITERATION_HOOK = None   # measurement aid (tools/particle_mcmc_bench.py): called with i at the top of every iteration of either loop
 
@@ -296,7 +305,13 @@ def adapted_scale_tril(u_history: Tensor, current: Tensor) -> Tensor:
 
 def _validate(sde, observations, observation_likelihood, initial_theta, time_step, n_iterations, warmup, n_particles,
               filters_per_chain, thin, theta_positive_dims, initial_state, proposal, proposal_scale_tril, step_size, target_accept,
-              adapt_interval, return_paths=False, path_thin=1, estimator=None):
+              adapt_interval, return_paths=False, path_thin=1, estimator=None, dynamics="diffusion", max_events=2 ** 16):
+    if dynamics not in DYNAMICS:
+        raise ValueError(f"dynamics must be one of {DYNAMICS}, got {dynamics!r}")
+    if dynamics == "jump" and proposal != "bootstrap":
+        raise ValueError(f"dynamics='jump' runs the bootstrap filter on the jump process: proposal must be 'bootstrap', got {proposal!r}")
+    if dynamics == "jump" and return_paths:
+        raise ValueError("return_paths=True is not available with dynamics='jump': jump-process paths are not kept")
     if path_thin < 1:
         raise ValueError(f"path_thin must be >= 1, got {path_thin}")
     if return_paths and estimator is not None:
@@ -319,7 +334,11 @@ def _validate(sde, observations, observation_likelihood, initial_theta, time_ste
     x0 = initial_state
     if x0 is not None and x0.ndim == 2 and initial_theta.ndim == 2 and x0.shape[0] == initial_theta.shape[0]:
         x0 = x0.repeat_interleave(R, dim=0)
-    rows, x0 = _pf._validate(sde, observations, rows, time_step, n_particles, x0)
+    if dynamics == "jump":
+        from . import jump_filter as _jf
+        rows, x0, _ = _jf._validate(sde, observations, rows, n_particles, x0, max_events)
+    else:
+        rows, x0 = _pf._validate(sde, observations, rows, time_step, n_particles, x0)
     C, P = initial_theta.shape
     pos = sorted({int(d) for d in theta_positive_dims})
     if any(d < 0 or d >= P for d in pos):
@@ -345,7 +364,8 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
                   initial_state: Optional[Tensor] = None, proposal: str = "bootstrap", proposal_scale_tril: Optional[Tensor] = None,
                   step_size: Optional[float] = None, adapt: bool = True, target_accept: float = DEFAULT_TARGET_ACCEPT,
                   adapt_interval: int = 25, key: Optional[Tensor] = None, return_paths: bool = False, path_thin: int = 1,
-                  _estimator=None, _trace: Optional[list] = None) -> ParticleMCMCResult:
+                  _estimator=None, _trace: Optional[list] = None, dynamics: str = "diffusion",
+                  max_events: int = 2 ** 16) -> ParticleMCMCResult:
     """``C`` independent PMMH chains, one per row of ``initial_theta [C, P]``, run in lock-step for ``n_iterations`` iterations of
     which the first ``warmup`` adapt and are dropped; every ``thin``-th state after them is kept (the module docstring has the
     rule).  ``prior``: the package's ``Prior`` or any object with ``log_prob(theta [C, P])``; ``theta_positive_dims``: the dims of
@@ -355,11 +375,19 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
     ``u' = u + step_size L z`` (defaults in the module docstring); ``adapt``: whether L is re-estimated once in warm-up (the step size
     adapts in warm-up either way); ``key``: two int32 words (default: drawn from torch's generator on theta's device).  The same key
     gives the same chains.  ``return_paths``: every ``path_thin``-th kept state also gets the latent path accepted with it (the
-    ``paths`` fields of the result; ``path_thin >= 1``); the theta chain is the same with and without.  No gradients."""
+    ``paths`` fields of the result; ``path_thin >= 1``); the theta chain is the same with and without.  No gradients.
+
+    ``dynamics="jump"`` (``sde`` must be a ``ReactionNetworkSDE``): the estimator of every iteration is ``jump_particle_filter``
+    under ``filter_key(i, key)``, the bootstrap filter on the exact jump process with ``max_events`` events per particle and
+    segment, so the chains target the theta posterior of the jump process itself, with no time step and no diffusion approximation.
+    ``time_step`` and ``positive_dims`` are ignored (``None`` is accepted), ``proposal`` must be ``"bootstrap"``, ``initial_state``
+    must hold integers in ``0 .. 2^30`` (default: the first observation, if it does), and ``return_paths=True`` raises
+    ``ValueError``: jump-process paths are not kept."""
     theta0, x0, mask, pos_theta = _validate(sde, observations, observation_likelihood, initial_theta, time_step, n_iterations, warmup,
                                             n_particles, filters_per_chain, thin, theta_positive_dims, initial_state, proposal,
                                             proposal_scale_tril, step_size, target_accept, adapt_interval, return_paths, path_thin,
-                                            _estimator)
+                                            _estimator, dynamics, max_events)
+    jump, estimator_given = dynamics == "jump", _estimator is not None
     dev, dtype = theta0.device, theta0.dtype
     C, P = theta0.shape
     R = int(filters_per_chain)
@@ -373,18 +401,26 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
             L = torch.diag(u0.std(dim=0).clamp(min=DEFAULT_SCALE_FLOOR))
         else:
             L = torch.eye(P, device=dev, dtype=dtype)
-        run = dict(sde=sde, obs=obs, like=observation_likelihood, prior=prior, dt=float(time_step), u0=u0, x0=x0, mask=mask,
-                   pos_theta=pos_theta, pos_state=tuple(positive_dims), n_iterations=int(n_iterations), warmup=int(warmup),
+        if jump and not estimator_given:
+            from .jump_filter import jump_particle_filter
+            _estimator = lambda rows, i, fkey: jump_particle_filter(sde, obs, observation_likelihood, rows, n_particles=int(n_particles),
+                                                                    initial_state=x0, key=fkey, max_events=int(max_events)).log_likelihood
+        run = dict(sde=sde, obs=obs, like=observation_likelihood, prior=prior, dt=0.0 if jump else float(time_step), u0=u0, x0=x0, mask=mask,
+                   pos_theta=pos_theta, pos_state=() if jump else tuple(positive_dims), n_iterations=int(n_iterations), warmup=int(warmup),
                    N=int(n_particles), R=R, thin=int(thin), proposal=proposal, L=L,
                    step=float(step_size) if step_size is not None else 2.38 / math.sqrt(P), adapt=bool(adapt) and C > P,
                    target_accept=float(target_accept), interval=int(adapt_interval), key=key, estimator=_estimator, trace=_trace,
                    path_thin=int(path_thin) if return_paths else 0)
         route = None
-        if HIP_MCMC and _estimator is None and theta0.is_cuda and dtype == torch.float32 and type(prior) is Prior and prior.dim == P:
+        if HIP_MCMC and not estimator_given and theta0.is_cuda and dtype == torch.float32 and type(prior) is Prior and prior.dim == P:
             from .. import _hip
-            if P <= _hip.PMMH_MAX_PARAMS:
+            if P <= _hip.PMMH_MAX_PARAMS and not jump:
                 route = _pf._kernel_route(sde, obs, observation_likelihood, theta0.repeat_interleave(R, dim=0), int(n_particles), proposal)
-        out = _torch_loop(**run) if route is None else _kernel_loop(route, **run)
+            elif P <= _hip.PMMH_MAX_PARAMS:
+                from . import jump_filter as _jf
+                if _jf._kernel_route(sde, obs, observation_likelihood, theta0.repeat_interleave(R, dim=0), int(n_particles)):
+                    route = ("reaction_network", sde.kernel_descriptor())
+        out = _torch_loop(**run) if route is None else _kernel_loop(route, **run, max_events=int(max_events) if jump else 0)
         return _result(*out[:7], mask, *out[7:])
 
 
@@ -472,12 +508,13 @@ def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n
 
 
 def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n_iterations, warmup, N, R, thin, proposal, L,
-                 step, adapt, target_accept, interval, key, estimator, trace, path_thin=0):
+                 step, adapt, target_accept, interval, key, estimator, trace, path_thin=0, max_events=0):
     """The loop with the step kernel: launch i closes iteration i - 1 and opens iteration i, the filter launch follows.  When the
     step size or L changes before iteration i (warm-up only) the proposal is opened again with the new values: the open half is a
     pure function of (state, i, key, step size, L).  With paths the filter stores particles and ancestors into two buffers
     allocated here, launch i draws the records of the chains it accepts from them (the filter launch of iteration i overwrites
-    them only afterwards), and one replay launch after the loop turns the kept records into paths."""
+    them only afterwards), and one replay launch after the loop turns the kept records into paths.  ``max_events > 0`` (``dynamics="jump"``): the filter
+    launch is the jump-process filter's (csrc/vsde_jump_filter.hip); everything else is the same loop."""
     from .. import _hip
     kind, network = route
     dev = u0.device
@@ -494,8 +531,17 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
     history = torch.empty(max(w2 - w4, 0), C, P, **f32) if adapt else None
     L_host = L.detach().float().cpu().contiguous()
     prior_args = (1 if prior.type == PriorType.LOG_NORMAL else 0, float(prior.mean), float(prior.std), pos_theta)
-    rows, model = _pf._launch_model(obs, like, u0, dt)                 # formed once for every launch of the loop
-    x0 = x0.contiguous()
+    if max_events:
+        from . import jump_filter as _jf
+        times, model = obs.times.to(torch.float64), _jf._launch_model(obs, like, u0)   # formed once for every launch of the loop
+        x0 = x0.to(torch.int32).contiguous()
+        filter_launch = lambda: _hip.jump_particle_filter(x0, kernel_theta(network, theta_prop), times, *model, fkey, max_events, N,
+                                                          network=network)
+    else:
+        rows, model = _pf._launch_model(obs, like, u0, dt)                 # formed once for every launch of the loop
+        x0 = x0.contiguous()
+        filter_launch = lambda: _pf._kernel_call("particle_filter", proposal, (kind, x0, kernel_theta(network, theta_prop), rows), model,
+                                                 fkey, dt, N, pos_state, network=network, store=store)
     logliks, loglik, window_base, pending = [], None, 0, None
     store = None
     if path_thin:
@@ -548,9 +594,7 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
             step_launch(i, None)                           # open iteration i again with the new step size / L
         if i == warmup:
             n_acc.zero_()
-        out = _pf._kernel_call("particle_filter", proposal, (kind, x0, kernel_theta(network, theta_prop), rows), model, fkey, dt, N,
-                               pos_state, network=network, store=store)
-        loglik = out[0].view(C, R)
+        loglik = filter_launch()[0].view(C, R)
         logliks.append(loglik)
         if trace is not None:
             pending = dict(prop_u=prop_u.clone(), theta_prop=theta_prop.clone(), prop_log_prior=prop_lp.clone(), loglik=loglik,

@@ -427,7 +427,8 @@ class VariationalPosterior:
     @torch.no_grad()
     def reweight_parameters(self, sde: SDE, observation_likelihood: ObservationLikelihood, n_samples: int = 1024,
                             n_particles: int = 512, chunk_size: int = 256, return_draws: bool = True,
-                            proposal: str = "bootstrap") -> ParameterReweighting:
+                            proposal: str = "bootstrap", dynamics: str = "diffusion",
+                            max_events: int = 2 ** 16) -> ParameterReweighting:
         """Is q(theta) any good?  Draws theta ~ q with the EMA weights as ``sample()`` draws them, estimates ``log p(y | theta)`` of
         the Euler-Maruyama-discretised model on this posterior's grid with a bootstrap particle filter (``particle_filter``:
         ``n_particles`` particles per theta, ``chunk_size`` thetas per call, start state = first observation as in
@@ -439,10 +440,19 @@ class VariationalPosterior:
         proposal that does not look at them, and ``log p^`` too noisy for the weights to mean much.  The bridge extrapolates the
         drift linearly to the next observation: it pays when observations are a few steps apart or the drift changes little between
         them, not across a long gap of a strongly nonlinear model (compare ``filter_effective_sample_size`` of the two); there
-        ``"residual_bridge"`` (the same step around the noise-free Euler path of the segment) is the one to try."""
+        ``"residual_bridge"`` (the same step around the noise-free Euler path of the segment) is the one to try.
+        ``dynamics="jump"`` (a ``ReactionNetworkSDE``): ``log p(y | theta)`` is that of the exact jump process instead
+        (``jump_particle_filter`` with ``max_events`` events per particle and segment; ``proposal`` must be ``"bootstrap"``); the
+        start state is the first observation, which must hold integers."""
+        from ..inference import jump_filter as _jf
         from ..inference import particle_filter as _pf
+        from ..inference.particle_mcmc import DYNAMICS
         if proposal not in _pf.PROPOSALS:
             raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
+        if dynamics not in DYNAMICS:
+            raise ValueError(f"dynamics must be one of {DYNAMICS}, got {dynamics!r}")
+        if dynamics == "jump" and proposal != "bootstrap":
+            raise ValueError(f"dynamics='jump' runs the bootstrap filter on the jump process: proposal must be 'bootstrap', got {proposal!r}")
         if n_samples < 1 or chunk_size < 1 or n_particles < 1:
             raise ValueError(f"n_samples, n_particles and chunk_size must be >= 1 (got {n_samples}, {n_particles}, {chunk_size})")
         q = self.model.sde_parameter_posterior
@@ -460,9 +470,13 @@ class VariationalPosterior:
         loglik = torch.empty(n_samples, device=theta.device, dtype=theta.dtype)
         min_ess = torch.empty(n_samples, device=theta.device, dtype=theta.dtype)
         for lo in range(0, n_samples, chunk_size):
-            res = _pf.particle_filter(sde, self.observations, observation_likelihood, theta[lo:lo + chunk_size], self.time_step,
-                                      n_particles=n_particles, initial_state=x0, positive_dims=self.state_space.positive_dims,
-                                      proposal=proposal)
+            if dynamics == "jump":
+                res = _jf.jump_particle_filter(sde, self.observations, observation_likelihood, theta[lo:lo + chunk_size],
+                                               n_particles=n_particles, initial_state=x0, max_events=max_events)
+            else:
+                res = _pf.particle_filter(sde, self.observations, observation_likelihood, theta[lo:lo + chunk_size], self.time_step,
+                                          n_particles=n_particles, initial_state=x0, positive_dims=self.state_space.positive_dims,
+                                          proposal=proposal)
             loglik[lo:lo + chunk_size] = res.log_likelihood
             min_ess[lo:lo + chunk_size] = res.effective_sample_size.min(dim=1).values
         log_w = log_prior.double() + loglik.double() - log_q
@@ -555,7 +569,8 @@ class VariationalPosterior:
     @torch.no_grad()
     def refine_parameters(self, sde: SDE, observation_likelihood: ObservationLikelihood, n_chains: int = 256,
                           n_iterations: int = 600, warmup: int = 300, n_particles: int = 512, filters_per_chain: int = 1,
-                          thin: int = 1, proposal: str = "bootstrap", return_paths: bool = False, path_thin: int = 1):
+                          thin: int = 1, proposal: str = "bootstrap", return_paths: bool = False, path_thin: int = 1,
+                          dynamics: str = "diffusion", max_events: int = 2 ** 16):
         """When ``reweight_parameters`` says q(theta) is poor (a small ``effective_sample_size``: a mean-field q cannot follow a
         correlated posterior), this gives something better: ``n_chains`` independent particle-MCMC chains (``particle_mcmc``) started
         at draws of q under the EMA weights, as ``reweight_parameters`` draws them, which sample the exact theta posterior of the
@@ -566,7 +581,9 @@ class VariationalPosterior:
         before trusting them.  ``return_paths=True``: every ``path_thin``-th kept state also gets the latent path accepted with it
         (``paths [n_path, C, T+1, S]`` and the ``path_*`` fields of the result): exact draws of the path to set beside
         ``summary().diffusion_path_mean``, where ``smooth_paths`` is an importance sample around q.  It runs on a CPU posterior too (the torch route) and touches none of ``sample()``'s caches or
-        graphs."""
+        graphs.  ``dynamics="jump"`` (a ``ReactionNetworkSDE``): the chains target the theta posterior of the exact jump process
+        (``particle_mcmc(..., dynamics="jump", max_events=...)``): the start state is the first observation, which must hold
+        integers, ``proposal`` must be ``"bootstrap"`` and paths are not kept."""
         import dataclasses
         from ..inference import particle_mcmc as _mc
         if n_chains < 1:
@@ -583,7 +600,7 @@ class VariationalPosterior:
                                 warmup=warmup, n_particles=n_particles, filters_per_chain=filters_per_chain, thin=thin,
                                 theta_positive_dims=q._positive_dims, positive_dims=self.state_space.positive_dims,
                                 initial_state=self.observations.values[0], proposal=proposal, proposal_scale_tril=scale,
-                                return_paths=return_paths, path_thin=path_thin)
+                                return_paths=return_paths, path_thin=path_thin, dynamics=dynamics, max_events=max_events)
         v_std = theta.std(dim=0) if n_chains > 1 else torch.zeros_like(theta[0])
         return dataclasses.replace(res, variational_mean=theta.mean(dim=0), variational_std=v_std)
 
