@@ -35,3 +35,53 @@ KINETIC_CHAIN8 = dict(reactants=[[0] * 8, [0] * 8] + [[int(i == k) for i in rang
 # S = 2 with the modifier A at 0 and below: 0 -> A (keeps Sigma_AA > 0), 0 -> B activated by A, 0 -> B repressed by A, B -> 0
 CLAMP2 = dict(reactants=[[0, 0], [0, 0], [0, 0], [0, 1]], products=[[1, 0], [0, 1], [0, 1], [0, 0]],
               rate_laws={1: Hill(0, "K1", n=1), 2: Hill(0, "K2", n=3, repression=True)})
+
+
+# --- generated networks of the particle-filter sweep (tests/filter_sweep_reference.py): one per (species count, reaction bin of
+# the kind-4 dispatch: R <= 4, R <= 8, R <= 16)
+SWEEP_REACTIONS = {4: 3, 8: 7, 16: 12}
+
+
+def sweep_network(S, NR, kinetic=False):
+    """(ReactionNetworkSDE arguments, base theta, start state) of the sweep's network with S in 1..8 species and R = 3, 7 or 12
+    reactions (NR = 4, 8, 16).  Three core reactions change every species between them: the feed 0 -> X_i (i % 3 == 0), the
+    first-order conversion X_0 -> X_i (i % 3 == 1; a decay at S = 1) and the second-order X_0 + X_1 -> X_i (i % 3 == 2; 2 X_0 ->
+    X_0 at S = 1).  Then the decays X_i -> 0 and conversions X_i -> X_i+1, and past those the same stoichiometries again, each
+    with a constant of its own.  ``kinetic``: a Hill law (repression by the last species, n = 2) on the feed, Michaelis-Menten in
+    X_0 on the conversion where S > 1, one shared decay constant.  The propensities are of order 1 at the start state (a few
+    molecules per unit time against populations of 6..10): with fewer reactions than species the diffusion's covariance is
+    singular, and the fp32 rounding of its floored Cholesky pivots grows with the propensities."""
+    R = SWEEP_REACTIONS[NR]
+    unit = lambda *idx: [sum(int(i == j) for j in idx) for i in range(S)]
+    group = lambda r: [int(i % 3 == r) for i in range(S)]
+    second = unit(0, 1) if S > 1 else unit(0, 0)
+    reactants = [unit(), unit(0), second]
+    products = [group(0), group(1), group(2) if S > 1 else unit(0)]
+    theta = [2.0, 0.1, 0.01]
+    extra = [(unit(i), unit(), 0.05) for i in range(S)] + [(unit(i), unit(i + 1), 0.04) for i in range(S - 1)]
+    j = 0
+    while len(reactants) < R:
+        a, b, k = extra[j % len(extra)]
+        reactants.append(a), products.append(b), theta.append(k * (1.0 + 0.25 * (j // len(extra))))
+        j += 1
+    start = [6.0 + 2.0 * (i % 3) for i in range(S)]
+    kw = dict(reactants=reactants, products=products)
+    if kinetic:
+        names = [f"k{j}" for j in range(R)]
+        laws = {0: Hill(S - 1, "K", n=2, repression=True)}
+        theta[0] = 4.0
+        if S > 1:
+            laws[1] = MichaelisMenten(0, "Km")
+            theta[1] = 1.5
+        for j in range(3, min(R, 3 + S)):
+            names[j] = "d"                                       # the first round of decays shares one constant
+        free = []
+        for n, v in zip(names, theta):
+            if n not in [f for f, _ in free]:
+                free.append((n, v))
+        free.append(("K", 8.0))
+        if S > 1:
+            free.append(("Km", 5.0))
+        kw.update(rate_laws=laws, rate_constants=names)
+        theta = [v for _, v in free]
+    return kw, theta, start

@@ -170,7 +170,8 @@ __global__ void __launch_bounds__(pf_max_n(KIND, NS, NO > 0, RES)) pf_kernel(PfP
                 pf_block_sum<CH + 1>(v, red, lane, wave, nwaves);
                 s2 = v[0];
 #pragma unroll
-                for (int i = 0; i < CH; ++i) mean[i0 + i] = v[1 + i] / total;
+                for (int i = 0; i < CH; ++i)
+                    if (i0 + i < NS) mean[i0 + i] = v[1 + i] / total;   // the last chunk of an NS that is no multiple of CH is short
             }
         }
 #pragma unroll
@@ -179,7 +180,8 @@ __global__ void __launch_bounds__(pf_max_n(KIND, NS, NO > 0, RES)) pf_kernel(PfP
                 float d[CH];
 #pragma unroll
                 for (int i = 0; i < CH; ++i) {
-                    const float dx = x[i0 + i] - mean[i0 + i];
+                    float dx = 0.f;
+                    if (i0 + i < NS) dx = x[i0 + i] - mean[i0 + i];
                     d[i] = (i0 + i < S && w > 0.f) ? w * dx * dx : 0.f;
                 }
                 pf_block_sum<CH>(d, red, lane, wave, nwaves);
