@@ -42,16 +42,18 @@ CLAMP2 = dict(reactants=[[0, 0], [0, 0], [0, 0], [0, 1]], products=[[1, 0], [0, 
 SWEEP_REACTIONS = {4: 3, 8: 7, 16: 12}
 
 
-def sweep_network(S, NR, kinetic=False):
+def sweep_network(S, NR, kinetic=False, R=None):
     """(ReactionNetworkSDE arguments, base theta, start state) of the sweep's network with S in 1..8 species and R = 3, 7 or 12
-    reactions (NR = 4, 8, 16).  Three core reactions change every species between them: the feed 0 -> X_i (i % 3 == 0), the
+    reactions (NR = 4, 8, 16), or the ``R`` given (any count of the bin of NR: the SDE / jump sweep runs R = NR and the lower edges
+    R = 5 and 9, tests/sde_sweep_reference.py).  Three core reactions change every species between them: the feed 0 -> X_i (i % 3 == 0), the
     first-order conversion X_0 -> X_i (i % 3 == 1; a decay at S = 1) and the second-order X_0 + X_1 -> X_i (i % 3 == 2; 2 X_0 ->
     X_0 at S = 1).  Then the decays X_i -> 0 and conversions X_i -> X_i+1, and past those the same stoichiometries again, each
     with a constant of its own.  ``kinetic``: a Hill law (repression by the last species, n = 2) on the feed, Michaelis-Menten in
     X_0 on the conversion where S > 1, one shared decay constant.  The propensities are of order 1 at the start state (a few
     molecules per unit time against populations of 6..10): with fewer reactions than species the diffusion's covariance is
     singular, and the fp32 rounding of its floored Cholesky pivots grows with the propensities."""
-    R = SWEEP_REACTIONS[NR]
+    R = SWEEP_REACTIONS[NR] if R is None else R
+    assert {4: 1, 8: 5, 16: 9}[NR] <= R <= NR, (NR, R)
     unit = lambda *idx: [sum(int(i == j) for j in idx) for i in range(S)]
     group = lambda r: [int(i % 3 == r) for i in range(S)]
     second = unit(0, 1) if S > 1 else unit(0, 0)
@@ -85,3 +87,26 @@ def sweep_network(S, NR, kinetic=False):
         kw.update(rate_laws=laws, rate_constants=names)
         theta = [v for _, v in free]
     return kw, theta, start
+
+
+# --- the cells of the SDE / jump sweep (tests/sde_sweep_reference.py) by name: sw-S<S>-NR<NR>[-k][-R<R>], "-k": with rate laws, R
+# given where it is not the cell's own (R = NR at even S, SWEEP_REACTIONS[NR] at odd S)
+def sweep_reactions(S, NR):
+    return NR if S % 2 == 0 else SWEEP_REACTIONS[NR]
+
+
+def sweep_name(S, NR, kinetic=False, R=None):
+    own = R is None or R == sweep_reactions(S, NR)
+    return f"sw-S{S}-NR{NR}" + ("-k" if kinetic else "") + ("" if own else f"-R{R}")
+
+
+def is_sweep_name(name):
+    return isinstance(name, str) and name.startswith("sw-S")
+
+
+def sweep_cell(name):
+    """(S, NR, kinetic, R) of a cell's name."""
+    parts = name.split("-")
+    S, NR = int(parts[1][1:]), int(parts[2][2:])
+    R = [int(p[1:]) for p in parts[3:] if p.startswith("R")]
+    return S, NR, "k" in parts[3:], R[0] if R else sweep_reactions(S, NR)

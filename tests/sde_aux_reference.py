@@ -44,12 +44,19 @@ case of tests/test_sde_aux_ops_gpu.py, rounded up:
     coefficient VJP (kind 4)          20.54             83      30.48
     forecast step (kinds 1..3)         6.22             25       4.81
     forecast step (kind 4)             4.41             18       4.59
+    the kind-4 sweep (every <4, S, NR, KIN>, tests/sde_sweep_reference.py, on the cases of tests/test_sde_sweep_gpu.py):
+    log weight                         0.37             28       0.33
+    coefficient forward, mass action   3.07             13.5     3.07
+    coefficient forward, rate laws     3.98             16       3.98     (C_COEF_FWD_KIN of the sweep's module)
+    coefficient VJP                   12.44             83      12.95
+    forecast step                      3.31             18       3.23
 
 tests/test_sde_aux_bounds.py asserts that the CPU ratios stay within c / 4.
 
 Inputs.  Log weights take z, means, chol (kind 0: drift, diffusion) from ``sde_reference.path_case`` -- saturated z on rows 1..5 of
 path 0, NaN above the diagonals; a network's latent path stays near 1 instead (``lw_case``), and every third Lotka-Volterra path
-holds z = -30 on the prey (and on the predator in its second half) so that both radicands of the factor are floored decisively;
+holds z = -30 on the prey (and on the predator in its second half) so that both radicands of the factor are floored decisively; a
+cell of the kind-4 sweep takes a trajectory of its own network and the quadratic form to first order (``lw_case``, ``lw_formulas``);
 obs_rows holds row 0, a repeated row, row T and a row above T, which the kernel clamps to T.  Lotka-Volterra coefficient rows
 cycle over t through u = 0 (with v = 1e-9 on every other such row, which floors the second radicand too), u = 1e-9 (first radicand
 below half the floor) and both populations >= 1; every quantity a floor or a clamp gate tests is below half the floor or above
@@ -81,10 +88,19 @@ C_LW = 28.0
 C_LW_COUNT = 4.5
 
 # case name -> (kernel kind, S); the model of a name is what em_step / crn_sde know it as
-KINDS = {"ou": ("ornstein_uhlenbeck", 1), "lv": ("lotka_volterra", 2), "diag1": ("linear_diagonal", 1), "diag5": ("linear_diagonal", 5),
-         "diag8": ("linear_diagonal", 8), "diag32": ("linear_diagonal", 32), "sir": ("reaction_network", 2),
-         "net3": ("reaction_network", 3), "chain8": ("reaction_network", 8), "autoreg": ("reaction_network", 2),
-         "repress3": ("reaction_network", 3), "chain8k": ("reaction_network", 8), "clamp2": ("reaction_network", 2)}
+class _Kinds(dict):
+    """A cell of the kind-4 sweep (tests/sde_sweep_reference.py) is looked up by its name, e.g. ``sw-S5-NR4-k``, and is not listed."""
+
+    def __missing__(self, name):
+        if not R.is_sweep(name):
+            raise KeyError(name)
+        return R.EM_KINDS[name][:2]
+
+
+KINDS = _Kinds({"ou": ("ornstein_uhlenbeck", 1), "lv": ("lotka_volterra", 2), "diag1": ("linear_diagonal", 1), "diag5": ("linear_diagonal", 5),
+                "diag8": ("linear_diagonal", 8), "diag32": ("linear_diagonal", 32), "sir": ("reaction_network", 2),
+                "net3": ("reaction_network", 3), "chain8": ("reaction_network", 8), "autoreg": ("reaction_network", 2),
+                "repress3": ("reaction_network", 3), "chain8k": ("reaction_network", 8), "clamp2": ("reaction_network", 2)})
 
 
 def model(name):
@@ -92,7 +108,7 @@ def model(name):
 
 
 def is_crn(name):
-    return KINDS.get(name, ("", 0))[0] == "reaction_network"
+    return R.is_sweep(name) or KINDS.get(name, ("", 0))[0] == "reaction_network"
 
 
 def param_dim(name):
@@ -124,6 +140,8 @@ def _theta(name, rng, B):
         return np.stack([rng.uniform(0.5, 1.0, B), rng.standard_normal(B), rng.uniform(0.3, 0.6, B)], 1)
     if name == "lv":
         return np.array([0.8, 0.0025, 0.3]) * (1 + 0.1 * rng.random((B, 3)))
+    if R.is_sweep(name):
+        return R.sweep_theta(name, rng, B)
     if name in R.CRN_KINETIC:
         sde = R.crn_sde(name)
         lo, hi = (1.0, 5.0) if name in ("repress3", "chain8k") else (0.2, 1.2)
@@ -168,6 +186,8 @@ def coef_case(name, B, T):
         x = rng.uniform(0.5, 3.0, (B, T + 1, S))
         if name == "clamp2":
             x[:, :, 0] = np.array([0.0, -0.7, 0.0, 1.3])[t % 4]
+    elif R.is_sweep(name):
+        x = R.sweep_states(name, rng, (B, T + 1))
     elif is_crn(name):
         x = rng.uniform(1.6, 2.4, (B, T + 1, S))
     else:
@@ -178,6 +198,8 @@ def coef_case(name, B, T):
             theta[B - 1, 2 * S - 1] = -25.0
     x[:, T] = np.nan
     g_diff = rng.standard_normal((B, T, S, S))
+    if R.is_sweep(name):
+        g_diff[..., R.sweep_zeroed(name)] = 0.0            # the columns of the floored pivots of a cell with two or more of them
     up = np.triu_indices(S, 1)
     g_diff[..., up[0], up[1]] = np.nan
     f = lambda a: np.asarray(a, F32)
@@ -422,6 +444,8 @@ def fc_case(name, B, T, mask):
         x0 = np.array([120.0, 200.0]) * (0.9 + 0.2 * rng.random((B, 2)))
     elif m in ("autoreg",):
         x0 = rng.uniform(0.5, 3.0, (B, S))
+    elif R.is_sweep(m):
+        x0 = R.sweep_states(m, rng, (B,))
     elif is_crn(m):
         x0 = rng.uniform(1.6, 2.4, (B, S))
     else:
@@ -430,7 +454,7 @@ def fc_case(name, B, T, mask):
     # kinds 2 and 4: every other path starts small, and of a network only the species of FC_SMALL_SPECIES (every Cholesky radicand
     # then either stays clear of its floor or is a sum of like-signed terms: see fc_gates_ok)
     rows = np.arange(B) % 2 == 0 if (m == "lv" or is_crn(m)) else np.ones(B, bool)
-    for i in ([FC_SMALL_SPECIES[m]] if is_crn(m) else pos):
+    for i in ([R.sweep_hit_dim(m)] if R.is_sweep(m) else [FC_SMALL_SPECIES[m]] if is_crn(m) else pos):
         x0[rows, i] = small[rows, i]
     if name == "ou0":
         theta[:, 0], theta[:, 1], x0[:] = 0.0, 0.0, 0.0
@@ -583,6 +607,9 @@ def lw_sde(model, S):
             else R.crn_sde(model))
 
 
+LW_SWEEP_NOISE = 0.5
+
+
 @functools.lru_cache(maxsize=8)
 def lw_case(model, S, B, T, smask, K, obs, tmask, lognormal, count):
     """float32 inputs of the log-weight kernel: z, means, chol (and for kind 0 drift, diffusion) of ``sde_reference.path_case``
@@ -600,7 +627,28 @@ def lw_case(model, S, B, T, smask, K, obs, tmask, lognormal, count):
         # magnitude of that one step would swamp the path's sum
         z = (1.0 + 0.2 * rng.standard_normal(z.shape)).astype(F32)
     rates = None
-    if model == "k0":
+    dt = pc["dt"]
+    if R.is_sweep(model):
+        # the tail takes P <= 16 and reads theta for the prior / posterior terms alone: a rate-law cell's drift and diffusion read
+        # ``rates``, so its theta is cut to 16 columns where the network has 17 parameters (S 2, R 16)
+        sde = R.crn_sde(model)
+        theta = (sde.base_theta * (1 + R.SWEEP_JITTER * rng.uniform(-1, 1, (B, len(sde.base_theta))))).astype(F32)
+        full = theta
+        if not sde.plain:
+            rates, theta = sde.rates_of(torch.tensor(theta)).numpy(), theta[:, :16]
+        # a cell of the sweep: x is a trajectory of the network itself (float64 Euler-Maruyama from the jittered start state under
+        # N(0, 1) increments, dt = 0.05) and z = softplus^-1(x), so every residual lies in the span of the factor's columns and
+        # its solve is of order 1 in every direction, the floored ones included (1e-3 sqrt(dt) times a unit normal).  A path drawn
+        # independently per step has residuals of order 1 along a floored direction, each divided by 1e-3: log w of -1e10, a
+        # magnitude 1e7 times that, and a bound that an all-zero output meets.
+        dt = 0.05
+        sim = dict(name=model, B=B, T=T, S=S, ch=R.EM_KINDS[model][2], dt=dt, x0=R.sweep_states(model, rng, (B,)),
+                   theta=full if rates is None else rates, noise=LW_SWEEP_NOISE * rng.standard_normal((B, T, S)))
+        sim["noise"][..., R.sweep_zeroed(model)] = 0.0
+        x = R.em_simulate(sim, F64)
+        assert (x > 0.5).all(), "a species of the latent path nearly vanishes: change the input"
+        z = (x + np.log(-np.expm1(-x))).astype(F32)
+    elif model == "k0":
         theta = rng.uniform(0.1, 0.9, (B, 3))
     elif model == "diag":
         theta = np.concatenate([rng.uniform(0.2, 0.5, (B, S)), rng.uniform(0.2, 1.0, (B, S))], 1)
@@ -616,7 +664,7 @@ def lw_case(model, S, B, T, smask, K, obs, tmask, lognormal, count):
     P = theta.shape[1]
     O = S if obs == "id" else 16 if obs == "wide16" else min(16, S + 3) if obs == "wide" else max(1, S - 1)
     f = lambda a: np.asarray(a, F32)
-    c = dict(model=model, kind=LW_MODELS[model], S=S, B=B, T=T, K=K, O=O, P=P, smask=smask, pos=pc["pos"], dt=pc["dt"], z=z,
+    c = dict(model=model, kind="reaction_network" if R.is_sweep(model) else LW_MODELS[model], S=S, B=B, T=T, K=K, O=O, P=P, smask=smask, pos=pc["pos"], dt=dt, z=z,
              means=pc["means"], chol=pc["chol"], drift=pc["drift"] if model == "k0" else None,
              diffusion=pc["diffusion"] if model == "k0" else None, theta=f(theta), rates=rates, obs_rows=lw_rows(K, T),
              obs_values=f(rng.integers(0, 7, (K, O))) if count else f(rng.standard_normal((K, O)) + 1.0),
@@ -674,6 +722,15 @@ def lw_formulas(c, dtype=F64, defect=None):
         # sqrt(dt) v_i w_j - [i = j] / G_ii.  (Running the solve itself on the pairs (G, m(G)) multiplies the inflation of every
         # Cholesky level into the next -- 10^7 of the value for a 3-species network -- and the bound would see nothing.)
         w, v, lps = R._tri(xV[:, 1:], xV[:, :-1], VM(drift.v), VM(diff.v), dt, s, S, raw)
+        if R.is_sweep(model):
+            # a cell of the sweep: the quadratic form to first order, |w_i| m(w_i) in place of m(w_i)^2 / 2, where that is smaller.  A
+            # solve through a floored pivot has m(w_i) = 16 / (1e-3 sqrt(dt)) = 1e5 against w_i of order 1: its square is 1e10 a
+            # step, where a correct evaluation's w_i^2 moves by 2 |w_i| m(w_i) roundings, and a bound made from the square holds
+            # the kernel to nothing
+            first = np.full((B, T), 0.5 * S * R.LOG_2PI, dtype)
+            for i in range(S):
+                first = first + np.abs(w[i].v) * w[i].m + np.abs(np.log(np.abs(diff.v[..., i, i] * s)))
+            lps = VM(lps.v, np.minimum(lps.m, first).astype(dtype))
         extra = np.zeros((B, T), dtype)
         for i in range(S):
             extra = extra + np.abs(v[i].v) * dt * (drift.m[..., i] - np.abs(drift.v[..., i]))

@@ -32,6 +32,10 @@ __logf / __expf / fast_rcp and the kernels' summation trees:
     EM step (kinds 1..4)          2.53             10.5    2.62
     EM adjoint (kinds 1..3)       4.88             20      4.88
     EM adjoint (kind 4)          28.80             120     53.48
+    the kind-4 sweep (every <4, S, NR, KIN>, tests/sde_sweep_reference.py, on the cases of tests/test_sde_sweep_gpu.py):
+    EM step, S != 2               2.57             10.5    4.48
+    EM step, S = 2                3.77             15.5    3.01     (C_EM_STEP_S2 of the sweep's module)
+    EM adjoint                   18.48             120     3.90
 
 The path-forward ratio is the oracle's own: it adds the S T same-sign log-sigmoid terms of a path one after the other (9,600 at
 S 16, T 600), while the kernel sums 256 partial sums in a tree.  Kind 4 has a sixth constant because the magnitudes of its
@@ -44,6 +48,11 @@ The simulator's inputs (``em_case``) keep the noise small (0.01 N(0, 1)) except 
 chunk, the first step of the next, and step T -- where the noise of every third path and of the last path is -100 on one
 dimension, and at the step after a site, where it is +100: a clamped state leaves the floor decisively, so that every one-step
 value is below half the floor or above twice it (asserted on the reference, no element is excused).
+
+A cell of the kind-4 sweep (``sw-S<S>-NR<NR>[-k][-R<R>]``, tests/sde_sweep_reference.py) is a name ``crn_sde``, ``EM_KINDS`` and
+``em_case`` take like a named network; its inputs, the species it clamps, its kick and the magnitude of its diffusion factor are
+read off the float64 reference (``sweep_theta`` .. ``sweep_big``, ``_first_order_factor``), and a rate-law cell takes the kind-4
+reverse step on the effective constants [B, 2R].
 """
 import functools
 
@@ -64,13 +73,24 @@ C_EM_ADJ = 20.0
 C_EM_ADJ_CRN = 120.0     # kind 4: the magnitudes of its adjoint are |a| |J| with J from autograd, blind to the cancellation inside J
 
 
+def is_sweep(name):
+    """Whether ``name`` is a cell of the kind-4 sweep (tests/sde_sweep_reference.py), e.g. ``sw-S5-NR4-k``."""
+    import reaction_networks as N
+    return N.is_sweep_name(name)
+
+
 def is_crn(name):
     """Whether ``name`` is a reaction network of ``crn_sde``."""
-    return name in CRN or name in CRN_KINETIC or name == "sir"
+    return name in CRN or name in CRN_KINETIC or name == "sir" or is_sweep(name)
+
+
+def em_crn(name):
+    """Whether the simulator case ``name`` runs kind 4: the networks of ``CRN`` and every cell of the sweep, rate laws included."""
+    return name in CRN or is_sweep(name)
 
 
 def em_adj_c(name):
-    return C_EM_ADJ_CRN if name in CRN else C_EM_ADJ
+    return C_EM_ADJ_CRN if em_crn(name) else C_EM_ADJ
 
 
 # ------------------------------------------------------------------------------------------------------ (value, magnitude)
@@ -561,8 +581,24 @@ def tail_shapes():
 
 
 # ============================================================================================================= simulator
-EM_KINDS = {"ou": ("ornstein_uhlenbeck", 1, 32), "lv": ("lotka_volterra", 2, 32), "diag5": ("linear_diagonal", 5, 8),
-            "diag8": ("linear_diagonal", 8, 8)}                       # name -> (kernel kind, S, CH = em_chunk(S))
+def em_chunk(S):
+    """csrc/vsde_sde.hip: em_chunk, the steps the simulator stages in LDS at a time."""
+    return 32 if S <= 2 else 16 if S <= 4 else 8
+
+
+class _EmKinds(dict):
+    """name -> (kernel kind, S, CH = em_chunk(S)); a cell of the kind-4 sweep is looked up by its name and is not listed."""
+
+    def __missing__(self, name):
+        import reaction_networks as N
+        if not N.is_sweep_name(name):
+            raise KeyError(name)
+        S = N.sweep_cell(name)[0]
+        return ("reaction_network", S, em_chunk(S))
+
+
+EM_KINDS = _EmKinds({"ou": ("ornstein_uhlenbeck", 1, 32), "lv": ("lotka_volterra", 2, 32), "diag5": ("linear_diagonal", 5, 8),
+                     "diag8": ("linear_diagonal", 8, 8)})
 EM_KINDS.update({"net3": ("reaction_network", 3, 16), "chain8": ("reaction_network", 8, 8)})
 CRN = ("net3", "chain8")
 ORACLE_KIND = {"ou": "ou", "lv": "lv", "diag5": "linear_diagonal", "diag8": "linear_diagonal"}
@@ -641,9 +677,21 @@ def crn_sde(name):
 
     import reaction_networks as N
     from viforsdes_amd import ReactionNetworkSDE
-    if name in CRN_KINETIC:
-        spec = ReactionNetworkSDE(**getattr(N, CRN_KINETIC[name]))
+    if is_sweep(name):
+        # a cell of the sweep: reaction_networks.sweep_network; base_theta [P] and start [S] are its constants and start state
+        S, NR, kinetic, Rn = N.sweep_cell(name)
+        kw, base, start = N.sweep_network(S, NR, kinetic, Rn)
+        spec = ReactionNetworkSDE(**kw)
+        if not kinetic:
+            spec.rate_dim = spec.num_reactions
+            spec.base_theta, spec.start = np.asarray(base, F64), np.asarray(start, F64)
+            return spec
+    if name in CRN_KINETIC or is_sweep(name):
+        if name in CRN_KINETIC:
+            spec = ReactionNetworkSDE(**getattr(N, CRN_KINETIC[name]))
         sde = copy.copy(spec)
+        if is_sweep(name):
+            sde.base_theta, sde.start = np.asarray(base, F64), np.asarray(start, F64)
         sde.rates_of = spec.kernel_parameters                   # theta [.., P] -> effective constants [.., 2R]
         sde.kernel_parameters = lambda rates: rates
         sde.autograd_propensities = sde._propensities           # the package's own, for the pin of _HillFactor
@@ -670,6 +718,8 @@ def em_case(name, B, T, seed=0):
     elif name == "lv":
         theta = np.array([0.8, 0.0025, 0.3]) * (1 + 0.1 * rng.random((B, 3)))
         x0 = np.array([120.0, 200.0]) * (0.9 + 0.2 * rng.random((B, 2)))
+    elif is_sweep(name):
+        theta, x0 = sweep_theta(name, rng, B), sweep_states(name, rng, (B,))
     elif name in CRN:
         theta = rng.uniform(0.3, 0.8, (B, crn_sde(name).sde_param_dim))
         x0 = rng.uniform(1.6, 2.4, (B, S))
@@ -679,14 +729,20 @@ def em_case(name, B, T, seed=0):
     noise = 0.01 * rng.standard_normal((B, T, S))
     sites = em_sites(name, T)
     # (path, dimension) pairs that are clamped at the sites; kind 4: the last species, whose noise enters no other row of G
-    hit = [(b, S - 1 if name in CRN else b % S) for b in range(B) if b % 3 == 0 or b == B - 1]
+    # (a cell of the sweep: the last species whose pivot is not floored -- a floored pivot is 1e-3 and moves nothing)
+    last = sweep_hit_dim(name) if is_sweep(name) else S - 1
+    hit = [(b, last if em_crn(name) else b % S) for b in range(B) if b % 3 == 0 or b == B - 1]
+    big = sweep_big(name) if is_sweep(name) else EM_BIG
+    if is_sweep(name):
+        noise[..., sweep_zeroed(name)] = 0.0
     for b, d in hit:
         for t in sites:
-            noise[b, t - 1, d] = -EM_BIG
-            if t + 1 <= T and t + 1 not in sites:
-                noise[b, t, d] = EM_BIG
+            noise[b, t - 1, d] = -big
+            # (a cell of the sweep leaves the floor on its drift alone, see sde_sweep_reference: every species has an inflow)
+            if t + 1 <= T and t + 1 not in sites and not is_sweep(name):
+                noise[b, t, d] = big
     f = lambda a: np.asarray(a, np.float32)
-    return dict(name=name, kind=kind, S=S, B=B, T=T, ch=ch, dt=0.05 if name in CRN else 0.1, pos=list(range(S)), x0=f(x0), theta=f(theta), noise=f(noise),
+    return dict(name=name, kind=kind, S=S, B=B, T=T, ch=ch, dt=0.05 if em_crn(name) else 0.1, pos=list(range(S)), x0=f(x0), theta=f(theta), noise=f(noise),
                 g_traj=f(rng.standard_normal((B, T + 1, S))), sites=sites, hit=hit)
 
 
@@ -745,7 +801,96 @@ def crn_coef_formula(name, x, th, dtype=F64):
             for k in range(j):
                 a = a - L[i][k] * L[j][k]
             L[i][j] = a / c
+    if is_sweep(name):
+        L = _first_order_factor(sig, L, S, dtype)
     return f, L, gates
+
+
+def _first_order_factor(sig, L, S, dtype):
+    """The factor's entries with the smaller of two magnitudes, for the cells of the sweep.  The recursion's own magnitude multiplies
+    the inflation of every Cholesky level into the next: harmless in the named networks (a chain does not cancel), but 1e30 to
+    1e120 times the value in the last rows of a generated network of 7 or 8 species, where a bound made from it holds a kernel to
+    nothing.  The other is the first-order perturbation of a Cholesky factor, dL = L Phi(L^-1 dSigma L^-T) with Phi the strict lower
+    triangle plus half the diagonal, taken with absolute values: |L| + |L| Phi(|L^-1| (m(Sigma) + |L| |L|^T) |L^-T|), where m(Sigma) is
+    the magnitude of the covariance's own sum and |L| |L|^T the backward error of the factorisation, both in units of the rounding.
+    A floored pivot enters as the 1e-3 it is.  Either is a magnitude of a correct evaluation's error, so their minimum is one."""
+    shape = np.broadcast(*[sig[i][k].v for i in range(S) for k in range(i + 1)]).shape
+    Lv, mS = np.zeros(shape + (S, S)), np.zeros(shape + (S, S))
+    for i in range(S):
+        for k in range(i + 1):
+            Lv[..., i, k] = L[i][k].v
+            mS[..., i, k] = mS[..., k, i] = sig[i][k].m
+    absL = np.abs(Lv)
+    finite = np.isfinite(Lv).all((-1, -2), keepdims=True)              # a path started at NaN stays NaN: no inverse to take
+    inv = np.abs(np.linalg.inv(np.where(finite, Lv, np.eye(S))))
+    M = inv @ (mS + absL @ np.swapaxes(absL, -1, -2)) @ np.swapaxes(inv, -1, -2)
+    phi = np.tril(M, -1)
+    idx = np.arange(S)
+    phi[..., idx, idx] = 0.5 * M[..., idx, idx]
+    m1 = absL + absL @ phi
+    out = [[None] * S for _ in range(S)]
+    for i in range(S):
+        for k in range(i + 1):
+            out[i][k] = VM(L[i][k].v, np.minimum(L[i][k].m, m1[..., i, k]).astype(dtype))
+    return out
+
+
+# --- the cells of the kind-4 sweep (tests/sde_sweep_reference.py): inputs around the network's own constants and start state
+SWEEP_JITTER = 0.2
+
+
+def sweep_theta(name, rng, B):
+    """[B, rate_dim] constants of a cell: its base theta jittered by +-20 %; of a rate-law cell the effective constants [B, 2R]
+    of that theta, formed in float32 as the package forms them."""
+    sde = crn_sde(name)
+    th = sde.base_theta * (1 + SWEEP_JITTER * rng.uniform(-1, 1, (B, len(sde.base_theta))))
+    return th if sde.plain else sde.rates_of(torch.tensor(th, dtype=torch.float32)).numpy()
+
+
+def sweep_states(name, rng, shape):
+    """[*shape, S] states of a cell: its start state (populations of 6..10) jittered by +-20 %."""
+    sde = crn_sde(name)
+    return sde.start * (1 + SWEEP_JITTER * rng.uniform(-1, 1, tuple(shape) + (sde.state_dim,)))
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_floored(name):
+    """The floored pivots of a cell: the columns j whose Cholesky radicand (``gates[2j]`` of ``crn_coef_formula``) is under the
+    floor in float64 at the cell's start state and base constants.  Structural: the covariance has the rank of the
+    stoichiometric vectors, so the same columns floor at every state of the case (tests/test_sde_sweep_bounds.py asserts it)."""
+    sde = crn_sde(name)
+    th = sde.base_theta if sde.plain else sde.rates_of(torch.tensor(sde.base_theta, dtype=torch.float64)).numpy()
+    gates = crn_coef_formula(name, sde.start[None], th[None])[2]
+    return tuple(j for j in range(sde.state_dim) if float(gates[2 * j].v[0]) < EM_FLOOR)
+
+
+def sweep_zeroed(name):
+    """The noise / g_diffusion columns set to exactly zero: the floored pivots of a cell with two or more of them, none otherwise.
+    The adjoint divides by the floored c = 1e-3 once per floored pivot on the way, which with two of them turns the forward's
+    rounding noise into the gradient: no float64 comparison can score that.  With one floored pivot the path stays scored."""
+    fl = sweep_floored(name)
+    return list(fl) if len(fl) >= 2 else []
+
+
+def sweep_hit_dim(name):
+    """The species clamped at the sites: the last one, whose noise enters no other row of G, as in the named networks.  A cell with
+    floored pivots: species 2, the product of the second-order reaction and reactant of none there.  A floored pivot is 1e-3 and
+    moves nothing, and the last pivot above the floored ones is what one reaction leaves after all the others are eliminated: it
+    cancels a few hundred times, and a kick through it into the rows below turns that into the gradient (float32 torch: 400 to
+    1200 times the magnitude's rounding); the pivot of species 2 cancels some ten times."""
+    fl = sweep_floored(name)
+    assert not fl or 2 not in fl
+    return 2 if fl else crn_sde(name).state_dim - 1
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_big(name):
+    """The noise at a clamp site of a cell: EM_BIG times the smallest integer that makes the kick L_dd big sqrt(dt) of the hit
+    species at the start state at least EM_BIG sqrt(dt) = 22, against populations of at most 12."""
+    sde, d = crn_sde(name), sweep_hit_dim(name)
+    th = sde.base_theta if sde.plain else sde.rates_of(torch.tensor(sde.base_theta, dtype=torch.float64)).numpy()
+    L = crn_coef_formula(name, sde.start[None], th[None])[1]
+    return EM_BIG * max(1.0, float(np.ceil(1.0 / float(L[d][d].v[0]))))
 
 
 def crn_step_formula(name, x, th, e, dt, dtype=F64):
@@ -771,7 +916,9 @@ def _crn_step_bwd(name, x, th, e, a, dt, dtype):
     sde, S = crn_sde(name), EM_KINDS[name][1]
     x, th, e = _crn_torch(name, x, th, e, dtype, grad=True)
     y = _crn_step_torch(sde, x, th, e, dt)
-    rows = [torch.autograd.grad(y[..., i].sum(), [x, th], retain_graph=True) for i in range(S)]
+    # (a rate-law cell: th are the effective constants [.., 2R]; the K of a mass-action reaction enters nothing: a zero column)
+    rows = [torch.autograd.grad(y[..., i].sum(), [x, th], retain_graph=True, allow_unused=True) for i in range(S)]
+    rows = [[torch.zeros_like(v) if g is None else g for g, v in zip(r, (x, th))] for r in rows]
     Jx, Jt = (np.stack([r[k].numpy() for r in rows], -2) for k in (0, 1))          # [.., S (output), S or P]
     vjp = lambda J: VM(np.einsum("...i,...ij->...j", a.v, J), np.einsum("...i,...ij->...j", a.m, np.abs(J)))
     return vjp(Jx), vjp(Jt)
@@ -800,7 +947,7 @@ def em_step(name, x, th, e, dt, dtype=F64):
 
 def em_step_bwd(name, x, th, e, a, dt, dtype=F64):
     """(ax, gth): the vector-Jacobian product of ``em_step`` for a = dL/dy (a VM), as VM."""
-    if name in CRN:
+    if em_crn(name):
         return _crn_step_bwd(name, x, th, e, a, dt, dtype)
     S = EM_KINDS[name][1]
     x, th, e = (VM(np.asarray(t, dtype)) for t in (x, th, e))

@@ -2,7 +2,9 @@
 ``particle_mcmc(..., dynamics="jump")``.
 
 As in test_particle_filter_gpu.py the kernel is compared STAGE BY STAGE against float64 on its own previous stage, never the whole
-filter at once: one flipped ancestor or reaction legitimately changes everything after it.
+filter at once: one flipped ancestor or reaction legitimately changes everything after it.  The three stage checks live in
+tests/jump_filter_reference.py (check_propagation, check_weights_and_summaries, check_ancestors), which tests/test_jump_sweep_gpu.py
+runs on every instantiation of the kernel.
 
 * propagation: segment k is run again in float64 (tests/jump_filter_reference.py, the reference uniforms) from the kernel's
   particles at k - 1 gathered through the kernel's ancestors.  The reference flags a (particle, segment) as undecidable when an
@@ -28,7 +30,6 @@ import torch
 
 import jump_filter_reference as ref
 import jump_process_reference as jref
-import particle_filter_reference as pref
 from reaction_networks import BD, SIR
 
 pytestmark = pytest.mark.gpu
@@ -48,27 +49,10 @@ RUN_LIST = [("bd", 64, "poisson"), ("sir", 64, "poisson"), ("net4", 64, "gauss")
 
 
 def _key(k0, k1, dev=DEV):
-    return torch.from_numpy(np.array([k0, k1], dtype=np.uint32).view(np.int32)).to(dev)
+    return ref.key_tensor(k0, k1, dev)
 
 
-def _likelihood(spec):
-    from viforsdes_amd import GaussianObservationLikelihood, NegativeBinomialObservationLikelihood, PoissonObservationLikelihood
-    H = None if spec[-1] is None else torch.tensor(spec[-1], dtype=torch.float32)
-    if spec[0] == "gaussian":
-        return GaussianObservationLikelihood(variance=spec[1], obs_matrix=H)
-    if spec[0] == "poisson":
-        return PoissonObservationLikelihood(scale=spec[1], obs_matrix=H)
-    return NegativeBinomialObservationLikelihood(dispersion=spec[1], scale=spec[2], obs_matrix=H)
-
-
-def _counted(monkeypatch=None):
-    """A list that receives one entry per launch of the kernel through ``_hip.jump_particle_filter``."""
-    from viforsdes_amd import _hip
-    calls, real = [], _hip.jump_particle_filter
-    wrapped = lambda *a, **k: (calls.append(1), real(*a, **k))[1]
-    if monkeypatch is not None:
-        monkeypatch.setattr(_hip, "jump_particle_filter", wrapped)
-    return calls, real, wrapped
+_likelihood, _counted = ref.likelihood, ref.counted       # shared with tests/test_jump_sweep_gpu.py
 
 
 _RUNS = {}
@@ -105,79 +89,21 @@ def _cached(name, N, like_name):
 @pytest.mark.parametrize("name,N,like_name", [r for r in RUN_LIST if r[2] != "nb_h" and r != ("sir", 192, "gauss")])
 def test_propagation_matches_float64_gillespie_on_the_kernels_previous_stage(name, N, like_name):
     net, th, xs, ys, like, res, key = _cached(name, N, like_name)
-    tab = jref.tables(net)
-    rates = net.kernel_parameters(th.double()).numpy()
-    parts, anc, events = res.particles.cpu().numpy().astype(np.int64), res.ancestors.cpu().numpy().astype(np.int64), res.events.cpu().numpy()
-    M, K = parts.shape[:2]
-    assert int(res.stopped.sum()) == 0
-    flagged, checked = 0, []
-    for m in range(M):
-        for k in range(K):
-            start = np.repeat(xs[m][None], N, axis=0) if k == 0 else parts[m, k - 1][anc[m, k - 1]]
-            for j in range(N):
-                x, fired, status, near = ref.run_segment(tab, start[j], rates[m], TIMES[k - 1] if k else 0.0, TIMES[k], k, m * N + j, key, 4096)
-                assert status == 0
-                flagged += bool(near)
-                if not near:
-                    checked.append(bool(np.array_equal(x, parts[m, k, j])) and fired == events[m, k, j])
-    total = M * K * N
-    print(f"{name} N={N}: the reference flags {flagged} of {total} (particle, segment) pairs ({flagged / total:.1e}); "
-          f"{len(checked) - sum(checked)} of the other {len(checked)} differ; mean events {float(res.mean_events.mean()):.1f}")
-    assert flagged <= 2e-2 * total                                  # the reference's own share first: a cap, not a tolerance
-    assert all(checked)
-    assert events.sum() > total                                     # something happened
-    mean_events = events.reshape(M, K, N).mean(axis=2)
-    np.testing.assert_allclose(res.mean_events.cpu().numpy(), mean_events, rtol=1e-5, atol=1e-6)
+    ref.check_propagation(net, th, xs, TIMES, res, key, f"{name} N={N}")
 
 
 # --------------------------------------------------------------------------------------------------- 2. weights and summaries
 @pytest.mark.parametrize("name,N,like_name", RUN_LIST)
 def test_weights_and_summaries_match_float64_on_the_kernels_particles(name, N, like_name):
     net, th, xs, ys, like, res, key = _cached(name, N, like_name)
-    parts = res.particles.double().cpu().numpy()
-    M, K = parts.shape[:2]
-    got = [t.double().cpu().numpy() for t in (res.increments, res.effective_sample_size, res.filtered_mean, res.filtered_std, res.log_weights)]
-    e_lw = e_inc = e_ess = e_mean = e_std = 0.0
-    for m in range(M):
-        for k in range(K):
-            lw = ref.log_weights(like, ys[k], parts[m, k])
-            inc, ess, mean, std, w = pref.observation_stage(lw, parts[m, k])
-            size = (w[:, None] * np.abs(parts[m, k])).sum(axis=0) / w.sum()          # weighted mean of |x|, per dim
-            scale = max(1.0, np.abs(lw[np.isfinite(lw)]).max())
-            e_lw = max(e_lw, float(np.abs(got[4][m, k] - lw).max()) / scale)
-            e_inc = max(e_inc, abs(got[0][m, k] - inc) / scale)
-            e_ess = max(e_ess, abs(got[1][m, k] - ess) / ess)
-            e_mean = max(e_mean, float((np.abs(got[2][m, k] - mean) / np.maximum(size, 1e-30)).max()))
-            e_std = max(e_std, float((np.abs(got[3][m, k] - std) / (std + 1e-2 * size + 1e-30)).max()))
-    print(f"{name} N={N} {like_name}: log-weights {e_lw:.2e}, increments {e_inc:.2e} (of max(1, |lw|), bound 1e-5), ESS {e_ess:.2e}, "
-          f"mean {e_mean:.2e}, std {e_std:.2e} (relative, bound 1e-4)")
-    assert e_lw <= 1e-5 and e_inc <= 1e-5
-    assert e_ess <= 1e-4 and e_mean <= 1e-4 and e_std <= 1e-4
-    total = res.increments.double().sum(dim=1)
-    assert torch.allclose(res.log_likelihood.double(), total, rtol=1e-6, atol=1e-5 * float(res.increments.abs().max()))
+    ref.check_weights_and_summaries(like, ys, res, f"{name} N={N} {like_name}")
 
 
 # --------------------------------------------------------------------------------------------------------------- 3. ancestors
 @pytest.mark.parametrize("name,N,like_name", RUN_LIST)
 def test_ancestors_match_float64_systematic_resampling(name, N, like_name):
     net, th, xs, ys, like, res, key = _cached(name, N, like_name)
-    parts = res.particles.double().cpu().numpy()
-    anc = res.ancestors.cpu().numpy().astype(np.int64)
-    M, K = parts.shape[:2]
-    u = pref.resampling_uniforms(M, K, key)
-    differ, low, worst = 0, float("inf"), 0
-    for m in range(M):
-        for k in range(K):
-            lw = ref.log_weights(like, ys[k], parts[m, k])
-            w = np.exp(lw - lw.max())
-            low = min(low, w.sum() ** 2 / (w * w).sum())
-            d = np.abs(anc[m, k] - pref.systematic_ancestors(w, u[m, k]))
-            worst, differ = max(worst, int(d.max())), differ + int((d != 0).sum())
-    print(f"{name} N={N} {like_name}: {differ} of {anc.size} ancestors differ from float64 ({differ / anc.size:.1e}), largest difference "
-          f"{worst}; smallest float64 ESS {low:.1f}")
-    assert low > N / 20                                            # there was something to compare
-    assert anc.min() >= 0 and anc.max() < N and (np.diff(anc, axis=-1) >= 0).all()      # never decrease in j
-    assert worst <= 1 and differ <= 1e-3 * anc.size
+    ref.check_ancestors(like, ys, res, key, f"{name} N={N} {like_name}")
 
 
 # ------------------------------------------------------------------------------------------------------- 4. other kernel checks

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import jump_process_reference as ref
+from jump_process_reference import check_stages, implied_by_log  # noqa: F401  (the checks the jump sweep shares)
 from reaction_networks import BD, ISOMER, SIR
 from viforsdes_amd import ReactionNetworkSDE, diffusion_approximation_check, jump_process
 
@@ -25,61 +26,6 @@ E = 64
 def run(net, xs, th, times, B, record, max_events=E):
     return jump_process(net, torch.as_tensor(xs), torch.as_tensor(th, dtype=torch.float32, device=DEV), times, n_paths=B, key=KEY,
                         max_events=max_events, record_events=record)
-
-
-def implied_by_log(tab, xs, times, ev_t, ev_r, max_events):
-    """(states [B, K, S], n_events [B], status [B]) that the event log implies when it holds every event (max_events <= E):
-    output k holds x0 plus the changes of the events with time <= T_k, and exists once a later event or the end was reached."""
-    fired = ev_r >= 0
-    n = fired.sum(axis=1)
-    change = np.where(fired[:, :, None], tab["change"][np.clip(ev_r, 0, None)], 0)
-    times = np.asarray(times, dtype=np.float64)
-    upto = fired[:, None, :] & (ev_t[:, None, :] <= times[None, :, None])                # [B, K, E]
-    states = xs[:, None, :] + np.einsum("bke,bes->bks", upto.astype(np.int64), change)
-    capped = n == max_events
-    last = np.where(n > 0, ev_t[np.arange(len(n)), np.clip(n - 1, 0, None)], -np.inf)
-    reached = ~capped[:, None] | (times[None, :] < last[:, None])
-    return np.where(reached[:, :, None], states, -1), n, capped.astype(np.int64)
-
-
-def check_stages(net, xs, th32, times, res, max_events=E):
-    """The stage-by-stage checks of one kernel call with the event log; returns (events, undecidable) for the record."""
-    tab = ref.tables(net)
-    ev_t, ev_r = res.event_times.cpu().numpy(), res.event_reactions.cpu().numpy().astype(np.int64)
-    B = xs.shape[0]
-    fired = ev_r >= 0
-    assert np.array_equal(np.isnan(ev_t), ~fired) and ev_r.max() < tab["change"].shape[0]
-    assert np.array_equal(fired, np.arange(ev_r.shape[1])[None, :] < fired.sum(axis=1)[:, None])     # a prefix of each row
-    change = np.where(fired[:, :, None], tab["change"][np.clip(ev_r, 0, None)], 0)
-    before = xs[:, None, :] + np.cumsum(change, axis=1) - change                                      # the state before event e
-    assert (before[fired] + change[fired]).min() >= 0
-    b_idx, e_idx = np.nonzero(fired)
-    rates = net.kernel_parameters(torch.as_tensor(th32, dtype=torch.float32)).double().numpy()
-    a = ref.propensities(tab, before[b_idx, e_idx], rates[b_idx])
-    a0 = a.sum(axis=1)
-    assert a0.min() > 0
-    u1, u2 = ref.uniforms(b_idx, e_idx, KEY)
-    # waiting time
-    tau = -np.log(u1) / a0
-    previous = np.where(e_idx > 0, ev_t[b_idx, np.clip(e_idx - 1, 0, None)], 0.0)
-    waited = ev_t[b_idx, e_idx] - previous
-    err = np.abs(waited - tau) / np.where(tau > 0, tau, 1.0)
-    assert np.all(waited[tau == 0] == 0)
-    # reaction
-    j64, near = ref.choose(a, u2)
-    share = near.mean()
-    flipped = ev_r[b_idx, e_idx] != j64
-    print(f"{len(b_idx)} events: waiting-time error max {err.max():.2e}; undecidable {near.sum()} ({share:.1e}), flipped {flipped.sum()}")
-    assert err.max() <= 1e-5
-    assert share <= 1e-3
-    assert not np.any(flipped & ~near)
-    # outputs
-    states, n, status = implied_by_log(tab, xs, times, ev_t, ev_r, max_events)
-    assert np.array_equal(res.states.cpu().numpy(), states)
-    assert np.array_equal(res.n_events.cpu().numpy(), n)
-    assert np.array_equal(res.status.cpu().numpy(), status)
-    assert res.states.dtype == torch.int32 and res.states.shape == (B, len(times), xs.shape[1])
-    return len(b_idx), int(near.sum())
 
 
 def same_outputs(a, b):
