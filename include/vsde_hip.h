@@ -933,6 +933,43 @@ int vsde_crn_kinetic_jump_particle_filter(const vsde_crn_network *net, const vsd
                                           float *filtered_std, int32_t *stopped, float *mean_events, int32_t *particles,
                                           int *ancestors, float *log_weights, int32_t *events, void *stream);
 
+/* Replay of jump-process segments read at output times inside them: the latent paths of the jump-process particle smoother
+ * (viforsdes_amd/inference/jump_smoother.py) and of particle MCMC with dynamics="jump".  B records by K segments, a thread per
+ * (segment k, record r), k slowest.  Segment k of a record runs the event of vsde_crn_jump_particle_filter from its start state on
+ * the uniforms of philox4x32_10(counter {e >> 1, k, b, 7}, key) for its path b, the float64 clock restarted at obs_times[k-1] (0 for
+ * k = 0) and the event counter at 0, until obs_times[k] < t + tau.  path_times[Q] (DEVICE float64, non-decreasing, within
+ * 0 .. obs_times[K-1]); q_begin[K+1] (DEVICE int32, q_begin[0] = 0, q_begin[K] = Q, non-decreasing; the caller's to get right,
+ * the kernel clamps it into 0 .. Q): segment k owns the outputs q_begin[k] .. q_begin[k+1] - 1, the t_q with obs_times[k-1] < t_q <=
+ * obs_times[k] (segment 0: from 0).  An output receives the state after every event with time <= t_q; a segment stopped by an
+ * invalid propensity (status 2) or by max_events events short of obs_times[k] (status 1) leaves -1 in the outputs it did not reach.
+ * Outputs: paths[B][Q][S] (int32), n_events[B][K], status[B][K].
+ *   filter replay (the smoother): a record is (filter m, draw d), B = M D; x0[M][S], theta[M][P] (kinetic: rates[M][2R]), key: 2
+ * words in DEVICE memory; particles[M][K][N][S] and ancestors[M][K][N] as the filter stored them; last_slot[M][D]: the slot of the
+ * draw at the last observation (outside 0 .. N-1: a dead filter: lineage -1, paths -1, n_events 0, status 0).  The thread traces
+ * its slots down to k and k - 1 (every entry clamped into 0 .. N-1), writes lineage[M][D][K], starts from x0[m] (k = 0) or
+ * particles[m][k-1][lineage[k-1]] and uses path b = m N + lineage[k].
+ *   anchored replay (PMMH): a record brings x0[B][S], theta[B][P], keys[B][2], anchors[B][K][S] (int32) and noise_path[B][K];
+ * segment k starts at anchors[k-1] (x0 for k = 0) on path noise_path[k]; noise_path[K-1] = 0xFFFFFFFF: a dead record, as above.
+ *   VSDE_E_BADARG before any HIP call: a bad descriptor or one that disagrees with S / P; M (B) or K < 1, N or D < 1, M N >= 2^32,
+ * B K >= 2^31, Q < 1, max_events outside 1 .. 2^23, a NULL pointer. */
+int vsde_crn_jump_filter_replay(const vsde_crn_network *net, int M, int N, int S, int P, int K, int D, int Q, const int32_t *x0,
+                                const float *theta, const double *obs_times, const double *path_times, const int *q_begin,
+                                const uint32_t *key, int max_events, const int32_t *particles, const int *ancestors,
+                                const int *last_slot, int32_t *paths, int *lineage, int32_t *n_events, int32_t *status, void *stream);
+int vsde_crn_kinetic_jump_filter_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P, int K,
+                                        int D, int Q, const int32_t *x0, const float *rates, const double *obs_times,
+                                        const double *path_times, const int *q_begin, const uint32_t *key, int max_events,
+                                        const int32_t *particles, const int *ancestors, const int *last_slot, int32_t *paths,
+                                        int *lineage, int32_t *n_events, int32_t *status, void *stream);
+int vsde_crn_jump_anchored_replay(const vsde_crn_network *net, int B, int S, int P, int K, int Q, const int32_t *x0, const float *theta,
+                                  const double *obs_times, const double *path_times, const int *q_begin, const int32_t *anchors,
+                                  const uint32_t *noise_path, const uint32_t *keys, int max_events, int32_t *paths, int32_t *n_events,
+                                  int32_t *status, void *stream);
+int vsde_crn_kinetic_jump_anchored_replay(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int S, int P, int K, int Q,
+                                          const int32_t *x0, const float *rates, const double *obs_times, const double *path_times,
+                                          const int *q_begin, const int32_t *anchors, const uint32_t *noise_path, const uint32_t *keys,
+                                          int max_events, int32_t *paths, int32_t *n_events, int32_t *status, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

@@ -20,6 +20,7 @@ from .core.reaction_network import Hill, MichaelisMenten, ReactionNetworkSDE
 from .core.sde import SDE, FunctionalSDE, make_sde
 from .infer import InferenceConfig, infer
 from .inference.jump_filter import JumpParticleFilterResult, jump_particle_filter
+from .inference.jump_smoother import SmoothedJumpPaths, jump_particle_smoother
 from .inference.particle_filter import ParticleFilterResult, particle_filter
 from .inference.particle_mcmc import ParticleMCMCResult, particle_mcmc
 from .inference.particle_smoother import SmoothedPaths, particle_smoother
@@ -33,5 +34,5 @@ __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "Trainin
            "EvidenceEstimate", "PosteriorPredictive", "ParameterReweighting", "ParticleFilterResult", "particle_filter",
            "PathReweighting", "SmoothedPaths", "particle_smoother", "ParticleMCMCResult", "particle_mcmc", "JumpProcessResult",
            "jump_process", "DiffusionApproximationCheck", "diffusion_approximation_check", "JumpParticleFilterResult",
-           "jump_particle_filter"]
+           "jump_particle_filter", "SmoothedJumpPaths", "jump_particle_smoother"]
 __version__ = "0.1.0"

@@ -79,6 +79,7 @@ EXPORTS = (
     "vsde_residual_filter_replay", "vsde_crn_residual_filter_replay", "vsde_crn_kinetic_residual_filter_replay",
     "vsde_residual_anchored_replay", "vsde_crn_residual_anchored_replay", "vsde_crn_kinetic_residual_anchored_replay",
     "vsde_crn_jump_process", "vsde_crn_kinetic_jump_process", "vsde_crn_jump_particle_filter", "vsde_crn_kinetic_jump_particle_filter",
+    "vsde_crn_jump_filter_replay", "vsde_crn_kinetic_jump_filter_replay", "vsde_crn_jump_anchored_replay", "vsde_crn_kinetic_jump_anchored_replay",
     "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
@@ -591,14 +592,16 @@ def jump_filter_max_particles(state_dim: int, n_reactions: int, kinetic: bool = 
 
 
 def jump_particle_filter(x0, theta, obs_times, obs_values, obs_matrix, variance, key, max_events: int, n_particles: int,
-                         network=None, return_particles: bool = False):
+                         network=None, return_particles: bool = False, store=None):
     """Bootstrap particle filters on the exact jump process of a reaction network (include/vsde_hip.h:
     vsde_crn_jump_particle_filter), one per row of theta fp32 [M, P] (the effective constants [M, 2R] for a CrnKineticRoute) from
     the start states x0 int32 [M, S], against obs_values fp32 [K, O] at obs_times float64 [K], with a Gaussian observation term
     (obs_matrix [O, S] or None; ``variance``: a number) or a count term (``variance``: the likelihood's ``CountKernelTerms``); key:
     2 int32 words; everything on the device.  Returns (log_likelihood [M], increments [M, K], effective_sample_size [M, K],
     filtered_mean [M, K, S], filtered_std [M, K, S], stopped int32 [M, K], mean_events [M, K], and with ``return_particles``, else
-    None: particles int32 [M, K, N, S], ancestors int32 [M, K, N], log_weights [M, K, N], events int32 [M, K, N])."""
+    None: particles int32 [M, K, N, S], ancestors int32 [M, K, N], log_weights [M, K, N], events int32 [M, K, N]).  ``store``:
+    ``(particles, ancestors)``, contiguous int32 device buffers of those shapes to write into instead (particle MCMC with paths: no
+    allocation per launch); they are returned in their places, log_weights and events stay None."""
     lib = load()
     dev = _require_hip(x0, theta, obs_times, obs_values, obs_matrix, key)
     if x0.dtype != torch.int32 or x0.ndim != 2 or obs_times.dtype != torch.float64 or obs_times.ndim != 1:
@@ -624,6 +627,13 @@ def jump_particle_filter(x0, theta, obs_times, obs_values, obs_matrix, variance,
         particles = torch.empty(M, K, N, S, **i32) if keep else None
         ancestors, events = (torch.empty(M, K, N, **i32), torch.empty(M, K, N, **i32)) if keep else (None, None)
         log_weights = torch.empty(M, K, N, **f32) if keep else None
+        if store is not None:
+            particles, ancestors = store
+            for t, shape in ((particles, (M, K, N, S)), (ancestors, (M, K, N))):
+                if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int32 or not t.is_contiguous() \
+                        or tuple(t.shape) != shape:
+                    raise ValueError(f"jump_particle_filter: store must be contiguous int32 device tensors [{M}, {K}, {N}, {S}] and "
+                                     f"[{M}, {K}, {N}]")
         prefix, term = _observation_term(variance, K, dev)
         if prefix:      # (lik_kind, scale, dispersion, row_const) -> lik_kind, variance, scale, dispersion, row_const
             term = (term[0], ctypes.c_double(1.0)) + term[1:]
@@ -635,6 +645,83 @@ def jump_particle_filter(x0, theta, obs_times, obs_values, obs_matrix, variance,
               _ptr(std), _ptr(stopped), _ptr(mean_events), _ptr(particles), _ptr(ancestors), _ptr(log_weights), _ptr(events),
               _stream(dev))
     return loglik, incr, ess, mean, std, stopped, mean_events, particles, ancestors, log_weights, events
+
+
+def _jump_replay_inputs(who: str, x0, theta, obs_times, path_times, q_begin, max_events):
+    """What the two jump replays check alike; returns the contiguous (x0, theta, obs_times, path_times, q_begin on the device)."""
+    if x0.dtype != torch.int32 or x0.ndim != 2 or obs_times.dtype != torch.float64 or obs_times.ndim != 1 \
+            or path_times.dtype != torch.float64 or path_times.ndim != 1:
+        raise ValueError(f"{who}: x0 must be an int32 [rows, S] tensor, obs_times and path_times float64 [K] and [Q] tensors")
+    theta = _f32c(theta)
+    if theta.ndim != 2 or theta.shape[0] != x0.shape[0]:
+        raise ValueError(f"{who}: theta {tuple(theta.shape)} does not have one row for each of the {x0.shape[0]} start states")
+    K, Q = obs_times.shape[0], path_times.shape[0]
+    if not isinstance(q_begin, torch.Tensor) or q_begin.dtype != torch.int32 or q_begin.device.type != "cpu" or tuple(q_begin.shape) != (K + 1,):
+        raise ValueError(f"{who}: q_begin must be an int32 CPU tensor [{K + 1}]")
+    if K < 1 or Q < 1 or int(q_begin[0]) != 0 or int(q_begin[K]) != Q or bool((q_begin[1:] < q_begin[:-1]).any()):
+        raise ValueError(f"{who}: q_begin must be non-decreasing from 0 to Q = {Q} >= 1")
+    if not 1 <= int(max_events) <= 2 ** 23:
+        raise ValueError(f"{who}: max_events must be in 1 .. 2^23, got {max_events}")
+    return x0.contiguous(), theta, obs_times.contiguous(), path_times.contiguous(), q_begin.to(x0.device)
+
+
+def jump_filter_replay(x0, theta, obs_times, path_times, q_begin, key, max_events: int, particles, ancestors, last_slot, network=None):
+    """Smoothed jump-process paths from the genealogy of ``jump_particle_filter`` (include/vsde_hip.h: vsde_crn_jump_filter_replay):
+    x0 int32 [M, S], theta [M, P], obs_times float64 [K], key and network as given to the filter, its particles int32 [M, K, N, S]
+    and ancestors int32 [M, K, N], last_slot int32 [M, D] (-1: no sample), the output times path_times float64 [Q] on the device and
+    their ownership ranges q_begin, an int32 CPU tensor [K + 1] (checked here: from 0 to Q, non-decreasing).  Returns (paths int32
+    [M, D, Q, S], lineage int32 [M, D, K], n_events int32 [M, D, K], status int32 [M, D, K])."""
+    lib = load()
+    dev = _require_hip(x0, theta, obs_times, path_times, key, particles, ancestors, last_slot)
+    x0, theta, obs_times, path_times, q_dev = _jump_replay_inputs("jump_filter_replay", x0, theta, obs_times, path_times, q_begin, max_events)
+    if key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2:
+        raise ValueError("jump_filter_replay: key must be two int32 words")
+    if particles.dtype != torch.int32 or ancestors.dtype != torch.int32 or last_slot.dtype != torch.int32:
+        raise ValueError("jump_filter_replay: particles, ancestors and last_slot must be int32 tensors")
+    key, particles, ancestors, last_slot = key.contiguous(), particles.contiguous(), ancestors.contiguous(), last_slot.contiguous()
+    M, S = x0.shape
+    K, Q = obs_times.shape[0], path_times.shape[0]
+    if particles.ndim != 4 or last_slot.ndim != 2 or tuple(particles.shape[:2]) != (M, K) or particles.shape[3] != S \
+            or tuple(ancestors.shape) != tuple(particles.shape[:3]) or last_slot.shape[0] != M or last_slot.shape[1] < 1:
+        raise ValueError(f"jump_filter_replay: particles [M, K, N, S], ancestors [M, K, N], last_slot [M, D >= 1] expected for M = {M}, "
+                         f"K = {K}, S = {S}, got {tuple(particles.shape)}, {tuple(ancestors.shape)}, {tuple(last_slot.shape)}")
+    N, D = particles.shape[2], last_slot.shape[1]
+    with torch.cuda.device(dev):
+        i32 = dict(device=dev, dtype=torch.int32)
+        paths = torch.empty(M, D, Q, S, **i32)
+        lineage, n_events, status = torch.empty(M, D, K, **i32), torch.empty(M, D, K, **i32), torch.empty(M, D, K, **i32)
+        _call(*_sde_entry(lib, "jump_filter_replay", "reaction_network", network), ctypes.c_int(M), ctypes.c_int(N), ctypes.c_int(S),
+              ctypes.c_int(theta.shape[1]), ctypes.c_int(K), ctypes.c_int(D), ctypes.c_int(Q), _ptr(x0), _ptr(theta), _ptr(obs_times),
+              _ptr(path_times), _ptr(q_dev), _ptr(key), ctypes.c_int(int(max_events)), _ptr(particles), _ptr(ancestors), _ptr(last_slot),
+              _ptr(paths), _ptr(lineage), _ptr(n_events), _ptr(status), _stream(dev))
+    return paths, lineage, n_events, status
+
+
+def jump_anchored_replay(x0, theta, obs_times, path_times, q_begin, anchors, noise_path, keys, max_events: int, network=None):
+    """Jump-process paths of B path records of particle MCMC (include/vsde_hip.h: vsde_crn_jump_anchored_replay): per record its
+    start state x0 int32 [B, S], theta [B, P] (the effective constants for a CrnKineticRoute), anchors int32 [B, K, S], noise_path
+    [B, K] and filter key keys [B, 2] (int32); obs_times, path_times and q_begin as in ``jump_filter_replay``.  Returns (paths int32
+    [B, Q, S], n_events int32 [B, K], status int32 [B, K])."""
+    lib = load()
+    dev = _require_hip(x0, theta, obs_times, path_times, anchors, noise_path, keys)
+    x0, theta, obs_times, path_times, q_dev = _jump_replay_inputs("jump_anchored_replay", x0, theta, obs_times, path_times, q_begin, max_events)
+    ints = (torch.int32, torch.uint32)
+    if anchors.dtype != torch.int32 or noise_path.dtype not in ints or keys.dtype not in ints:
+        raise ValueError("jump_anchored_replay: anchors [B, K, S], noise_path [B, K] and keys [B, 2] must be int32 tensors")
+    anchors, noise_path, keys = anchors.contiguous(), noise_path.contiguous(), keys.contiguous()
+    B, S = x0.shape
+    K, Q = obs_times.shape[0], path_times.shape[0]
+    if tuple(anchors.shape) != (B, K, S) or tuple(noise_path.shape) != (B, K) or tuple(keys.shape) != (B, 2):
+        raise ValueError(f"jump_anchored_replay: anchors [{B}, {K}, {S}], noise_path [{B}, {K}], keys [{B}, 2] expected, got "
+                         f"{tuple(anchors.shape)}, {tuple(noise_path.shape)}, {tuple(keys.shape)}")
+    with torch.cuda.device(dev):
+        i32 = dict(device=dev, dtype=torch.int32)
+        paths, n_events, status = torch.empty(B, Q, S, **i32), torch.empty(B, K, **i32), torch.empty(B, K, **i32)
+        _call(*_sde_entry(lib, "jump_anchored_replay", "reaction_network", network), ctypes.c_int(B), ctypes.c_int(S),
+              ctypes.c_int(theta.shape[1]), ctypes.c_int(K), ctypes.c_int(Q), _ptr(x0), _ptr(theta), _ptr(obs_times), _ptr(path_times),
+              _ptr(q_dev), _ptr(anchors), _ptr(noise_path), _ptr(keys), ctypes.c_int(int(max_events)), _ptr(paths), _ptr(n_events),
+              _ptr(status), _stream(dev))
+    return paths, n_events, status
 
 
 def _replay_inputs(who: str, obs_rows, words_ok: bool, words: str, guided: bool, model, state_dim: int):

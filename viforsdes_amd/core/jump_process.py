@@ -230,6 +230,73 @@ def jump_segment(net, x: Tensor, rates: Tensor, t_start: float, t_end: float, se
     return x, n_events, status
 
 
+def jump_segment_states(net, x: Tensor, rates: Tensor, t_start: float, t_end: float, segment: int, paths: Tensor, key: Tensor,
+                        max_events: int, out_times) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``jump_segment`` (the same loop on the same uniforms, the same three results bit for bit) that also reads the path at the
+    instants ``out_times`` (non-decreasing floats or a float64 tensor ``[Q]``, inside the segment): output ``t_q`` receives the state
+    after every event with time ``<= t_q``, the rule of ``jump_process``: before the event at ``t_next`` is applied, every ``t_q <
+    t_next`` not yet written takes the current state.  A path that ends the segment (status 0) has written all of them by then; a
+    stopped one (status 1 or 2) leaves -1 in those it did not reach.  Returns ``(x [B, S] int64, n_events [B] int32, status [B]
+    int32, states [B, Q, S] int32)``; the replay of the jump-process smoother and of PMMH paths (inference/jump_smoother.py).
+    ``key`` may also be ``[B, 2]``: a key per path (the records of PMMH come from filters of different iterations)."""
+    dev, dtype = rates.device, rates.dtype
+    B, R, S = x.shape[0], net.num_reactions, x.shape[1]
+    if key.ndim == 2:
+        k0, k1 = (key.to(device=dev, dtype=torch.int64) & _MASK).unbind(dim=1)
+    else:
+        k0, k1 = _key_words(key)
+    nu = torch.tensor(net.change, dtype=torch.int64, device=dev)
+    out_times = torch.as_tensor(out_times, dtype=torch.float64).reshape(-1).to(dev)
+    Q = out_times.shape[0]
+    states = torch.full((B, Q, S), -1, dtype=torch.int32, device=dev)
+    q = torch.zeros(B, dtype=torch.int64, device=dev)
+    row = torch.arange(B, dtype=torch.int64, device=dev)
+    t = torch.full((B,), float(t_start), dtype=torch.float64, device=dev)
+    n_events = torch.zeros(B, dtype=torch.int32, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    live = torch.ones(B, dtype=torch.bool, device=dev)
+    zero = torch.zeros_like(paths)
+    inf = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
+    w = None
+    for e in range(max_events):
+        if not bool(live.any()):
+            break
+        a = jump_propensities(net, x, rates)
+        c = [a[:, 0]]
+        for j in range(1, R):
+            c.append(c[-1] + a[:, j])
+        c = torch.stack(c, dim=-1)
+        a0 = c[:, -1]
+        bad = live & ((~(a >= 0) | torch.isinf(a)).any(dim=-1) | torch.isinf(a0))
+        status[bad] = STATUS_INVALID
+        live = live & ~bad
+        if e % 2 == 0:
+            w = philox4x32_10(zero + (e >> 1), zero + int(segment), paths, zero + STREAM_WORD, k0, k1)
+        u1, u2 = _uniform(w[2 * (e & 1)], dtype), _uniform(w[2 * (e & 1) + 1], dtype)
+        t_next = torch.where(a0 == 0, inf, t + (-torch.log(u1) / a0).to(torch.float64))
+        for _ in range(Q):                   # outputs before the event take the state before it
+            due = live & (q < Q)
+            due = due & (out_times[q.clamp(max=Q - 1)] < t_next)
+            if not bool(due.any()):
+                break
+            states[row[due], q[due]] = x[due].to(torch.int32)
+            q = q + due.to(torch.int64)
+        live = live & ~(t_end < t_next)
+        below = (u2 * a0).unsqueeze(-1) < c
+        first = below.to(torch.int8).argmax(dim=-1)
+        last_positive = (R - 1) - (a > 0).flip(-1).to(torch.int8).argmax(dim=-1)
+        j = torch.where(below.any(dim=-1), first, last_positive)
+        x = torch.where(live.unsqueeze(-1), x + nu[j], x)
+        t = torch.where(live, t_next, t)
+        n_events = n_events + live.to(torch.int32)
+    status[live] = STATUS_EVENT_CAP
+    if Q:
+        # status 0 wrote every output on the way (t_q <= t_end < t_next) unless an output lies past t_end: the final state
+        rest = (torch.arange(Q, device=dev)[None, :] >= q[:, None]) & (status == STATUS_COMPLETE)[:, None]
+        states = torch.where(rest[:, :, None], x.to(torch.int32)[:, None, :], states)
+    return x, n_events, status, states
+
+
 def _rows(name: str, t: Tensor, width: int, what: str) -> Tensor:
     if t.ndim == 1:
         t = t.unsqueeze(0)

@@ -83,9 +83,22 @@ into paths.  ``HIP_MCMC = False`` forces the torch step (around whatever route t
 ``jump_particle_filter`` (inference/jump_filter.py), the bootstrap filter whose particles are exact trajectories of the network's
 jump process, under the same per-iteration key.  The chains then sample the exact theta posterior of the jump process itself
 (Golightly and Wilkinson 2011): there is no grid, so ``time_step`` and ``positive_dims`` are not used, ``proposal`` must be
-``"bootstrap"``, the start state must hold integers, and paths are not kept (``return_paths=True`` raises).  Both loops take it:
-the torch loop through its estimator slot, the kernel loop by launching the jump filter's kernel where it launches the SDE
-filter's, so an iteration is still the step kernel and one filter launch."""
+``"bootstrap"`` and the start state must hold integers.  Both loops take it: the torch loop through its estimator slot, the kernel
+loop by launching the jump filter's kernel where it launches the SDE filter's, so an iteration is still the step kernel and one
+filter launch.
+
+Paths of the jump process (``return_paths=True`` with ``path_times``, float64 ``[Q]`` inside ``[0, T_{K-1}]``; without ``path_times``
+it raises: there is no grid to put a path on).  Steps 4-8 hold as they stand on the int32 particles of ``jump_particle_filter``:
+the anchors are integers, a dead record is known by its noise paths alone.  Step 9 becomes the replay of
+``jump_particle_smoother`` (inference/jump_smoother.py has the rule): segment k starts at ``anchors[k-1]`` (``x0[c]`` for k = 0)
+with the clock at exactly ``T_{k-1}``, repeats the events of path ``noise_path[k]`` under ``fkey_{path_iteration}`` with the theta
+of the kept state until ``T_k < t + tau``, and every ``t_q`` in ``(T_{k-1}, T_k]`` receives the state after every event with time
+``<= t_q``.  ``paths`` is int32 ``[n_path, C, Q, S]``, -1 for a dead record; the ``path_*`` summaries are formed in the chain's dtype.
+The torch loop calls ``jump_particle_filter(..., return_particles=True)`` and replays through
+``core.jump_process.jump_segment_states``.  The kernel loop hands the step kernel the int32 store and the anchor buffers as raw
+32-bit words under an fp32 view: its record half only copies words (the NaN it writes into a dead record's anchors is never read),
+so csrc/vsde_mcmc.hip serves unchanged, and ONE launch after the loop (csrc/vsde_jump_replay.hip) makes the paths.  The theta chain
+is the same bit for bit with and without paths."""
 from __future__ import annotations
 
 import math
@@ -133,7 +146,9 @@ class ParticleMCMCResult:
       on the grid, a draw of ``x_{0:T} | y`` JOINTLY with that state's theta; ``path_iteration [n_path, C]`` (int32): the iteration
       whose filter the path came from, -1 for a dead record (its path is NaN); ``path_mean``, ``path_std [T+1, S]`` and
       ``path_quantiles`` over all live draws of all chains; ``path_mean_standard_error [T+1, S]``: the std over chains of the
-      per-chain path means divided by sqrt(C) (NaN for C = 1)."""
+      per-chain path means divided by sqrt(C) (NaN for C = 1).  With ``dynamics="jump"`` the paths are int32 ``[n_path, C, Q, S]``,
+      read at ``path_times [Q]`` (float64; None for diffusion dynamics), -1 for a dead record, and the ``path_*`` fields are
+      ``[Q, S]`` in the chain's dtype."""
     samples: Tensor
     log_likelihood: Tensor
     log_target: Tensor
@@ -155,6 +170,7 @@ class ParticleMCMCResult:
     path_std: Optional[Tensor] = None
     path_quantiles: Any = None
     path_mean_standard_error: Optional[Tensor] = None
+    path_times: Optional[Tensor] = None
 
 
 def _words(key: Tensor, c0, c1, c2, c3) -> list[Tensor]:
@@ -305,13 +321,17 @@ def adapted_scale_tril(u_history: Tensor, current: Tensor) -> Tensor:
 
 def _validate(sde, observations, observation_likelihood, initial_theta, time_step, n_iterations, warmup, n_particles,
               filters_per_chain, thin, theta_positive_dims, initial_state, proposal, proposal_scale_tril, step_size, target_accept,
-              adapt_interval, return_paths=False, path_thin=1, estimator=None, dynamics="diffusion", max_events=2 ** 16):
+              adapt_interval, return_paths=False, path_thin=1, estimator=None, dynamics="diffusion", max_events=2 ** 16,
+              path_times=None):
     if dynamics not in DYNAMICS:
         raise ValueError(f"dynamics must be one of {DYNAMICS}, got {dynamics!r}")
     if dynamics == "jump" and proposal != "bootstrap":
         raise ValueError(f"dynamics='jump' runs the bootstrap filter on the jump process: proposal must be 'bootstrap', got {proposal!r}")
-    if dynamics == "jump" and return_paths:
-        raise ValueError("return_paths=True is not available with dynamics='jump': jump-process paths are not kept")
+    if dynamics == "jump" and return_paths and path_times is None:
+        raise ValueError("return_paths=True with dynamics='jump': a jump process has no grid, path_times (the instants to read the "
+                         "paths at) is required")
+    if path_times is not None and dynamics != "jump":
+        raise ValueError("path_times is for dynamics='jump': the paths of dynamics='diffusion' live on the grid of time_step")
     if path_thin < 1:
         raise ValueError(f"path_thin must be >= 1, got {path_thin}")
     if return_paths and estimator is not None:
@@ -365,7 +385,7 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
                   step_size: Optional[float] = None, adapt: bool = True, target_accept: float = DEFAULT_TARGET_ACCEPT,
                   adapt_interval: int = 25, key: Optional[Tensor] = None, return_paths: bool = False, path_thin: int = 1,
                   _estimator=None, _trace: Optional[list] = None, dynamics: str = "diffusion",
-                  max_events: int = 2 ** 16) -> ParticleMCMCResult:
+                  max_events: int = 2 ** 16, path_times=None) -> ParticleMCMCResult:
     """``C`` independent PMMH chains, one per row of ``initial_theta [C, P]``, run in lock-step for ``n_iterations`` iterations of
     which the first ``warmup`` adapt and are dropped; every ``thin``-th state after them is kept (the module docstring has the
     rule).  ``prior``: the package's ``Prior`` or any object with ``log_prob(theta [C, P])``; ``theta_positive_dims``: the dims of
@@ -381,13 +401,21 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
     under ``filter_key(i, key)``, the bootstrap filter on the exact jump process with ``max_events`` events per particle and
     segment, so the chains target the theta posterior of the jump process itself, with no time step and no diffusion approximation.
     ``time_step`` and ``positive_dims`` are ignored (``None`` is accepted), ``proposal`` must be ``"bootstrap"``, ``initial_state``
-    must hold integers in ``0 .. 2^30`` (default: the first observation, if it does), and ``return_paths=True`` raises
-    ``ValueError``: jump-process paths are not kept."""
+    must hold integers in ``0 .. 2^30`` (default: the first observation, if it does).  A jump process has no grid, so
+    ``return_paths=True`` needs ``path_times`` (float64 ``[Q]``, ``Q >= 1``, finite, non-decreasing, inside ``[0, T_{K-1}]``; without
+    it ``ValueError``): ``paths`` is then int32 ``[n_path, C, Q, S]``, the state after every event with time ``<= t_q``, -1 for a
+    dead record, and the result's ``path_times`` holds the instants.  ``path_times`` with ``dynamics="diffusion"`` raises."""
     theta0, x0, mask, pos_theta = _validate(sde, observations, observation_likelihood, initial_theta, time_step, n_iterations, warmup,
                                             n_particles, filters_per_chain, thin, theta_positive_dims, initial_state, proposal,
                                             proposal_scale_tril, step_size, target_accept, adapt_interval, return_paths, path_thin,
-                                            _estimator, dynamics, max_events)
+                                            _estimator, dynamics, max_events, path_times)
     jump, estimator_given = dynamics == "jump", _estimator is not None
+    jump_paths = None
+    if jump and return_paths:
+        from . import jump_smoother as _js
+        host_times = observations.times.detach().to(torch.float64).cpu()
+        t_out = _js.validated_path_times(path_times, host_times)
+        jump_paths = (t_out, _js.ownership_ranges(t_out, host_times), host_times)
     dev, dtype = theta0.device, theta0.dtype
     C, P = theta0.shape
     R = int(filters_per_chain)
@@ -401,7 +429,7 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
             L = torch.diag(u0.std(dim=0).clamp(min=DEFAULT_SCALE_FLOOR))
         else:
             L = torch.eye(P, device=dev, dtype=dtype)
-        if jump and not estimator_given:
+        if jump and not estimator_given and jump_paths is None:
             from .jump_filter import jump_particle_filter
             _estimator = lambda rows, i, fkey: jump_particle_filter(sde, obs, observation_likelihood, rows, n_particles=int(n_particles),
                                                                     initial_state=x0, key=fkey, max_events=int(max_events)).log_likelihood
@@ -410,7 +438,7 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
                    N=int(n_particles), R=R, thin=int(thin), proposal=proposal, L=L,
                    step=float(step_size) if step_size is not None else 2.38 / math.sqrt(P), adapt=bool(adapt) and C > P,
                    target_accept=float(target_accept), interval=int(adapt_interval), key=key, estimator=_estimator, trace=_trace,
-                   path_thin=int(path_thin) if return_paths else 0)
+                   path_thin=int(path_thin) if return_paths else 0, jump_paths=jump_paths, max_events=int(max_events) if jump else 0)
         route = None
         if HIP_MCMC and not estimator_given and theta0.is_cuda and dtype == torch.float32 and type(prior) is Prior and prior.dim == P:
             from .. import _hip
@@ -420,8 +448,8 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
                 from . import jump_filter as _jf
                 if _jf._kernel_route(sde, obs, observation_likelihood, theta0.repeat_interleave(R, dim=0), int(n_particles)):
                     route = ("reaction_network", sde.kernel_descriptor())
-        out = _torch_loop(**run) if route is None else _kernel_loop(route, **run, max_events=int(max_events) if jump else 0)
-        return _result(*out[:7], mask, *out[7:])
+        out = _torch_loop(**run) if route is None else _kernel_loop(route, **run)
+        return _result(*out[:7], mask, *out[7:], path_times=None if jump_paths is None else jump_paths[0].to(dev))
 
 
 def _adaptation(i, warmup, interval, adapt):
@@ -430,7 +458,7 @@ def _adaptation(i, warmup, interval, adapt):
 
 
 def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n_iterations, warmup, N, R, thin, proposal, L, step,
-                adapt, target_accept, interval, key, estimator, trace, path_thin=0):
+                adapt, target_accept, interval, key, estimator, trace, path_thin=0, jump_paths=None, max_events=0):
     dev, dtype = u0.device, u0.dtype
     C, P = u0.shape
     cur_u = u0.clone()
@@ -447,10 +475,12 @@ def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n
     if path_thin:
         K, S = obs.values.shape[0], x0.shape[1]
         n_path = (n_keep + path_thin - 1) // path_thin
-        cur_anchor = torch.full((C, K, S), float("nan"), device=dev, dtype=dtype)
+        # the jump process carries its anchors as integers (a dead record: noise_path = DEAD_PATH, the anchor's contents are irrelevant)
+        anchor_dtype = torch.int32 if jump_paths is not None else dtype
+        cur_anchor = torch.full((C, K, S), -1 if jump_paths is not None else float("nan"), device=dev, dtype=anchor_dtype)
         cur_noise = torch.full((C, K), DEAD_PATH, device=dev, dtype=torch.int64)
         cur_iter = torch.full((C,), -1, device=dev, dtype=torch.int32)
-        anchor_rows, noise_rows = torch.empty(n_path, C, K, S, device=dev, dtype=dtype), torch.empty(n_path, C, K, device=dev, dtype=torch.int64)
+        anchor_rows, noise_rows = torch.empty(n_path, C, K, S, device=dev, dtype=anchor_dtype), torch.empty(n_path, C, K, device=dev, dtype=torch.int64)
         iter_rows = torch.empty(n_path, C, device=dev, dtype=torch.int32)
     for i in range(n_iterations):
         if _ITERATION_HOOK is not None:
@@ -469,6 +499,11 @@ def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n
         fkey = filter_key(i, key)
         if estimator is not None:
             loglik = estimator(rows, i, fkey)
+        elif jump_paths is not None:
+            from .jump_filter import jump_particle_filter
+            filtered = jump_particle_filter(sde, obs, like, rows, n_particles=N, initial_state=x0, return_particles=True, key=fkey,
+                                            max_events=max_events)
+            loglik = filtered.log_likelihood
         else:
             filtered = _pf.particle_filter(sde, obs, like, rows, dt, n_particles=N, initial_state=x0, positive_dims=pos_state, key=fkey,
                                            proposal=proposal, return_particles=bool(path_thin))
@@ -477,8 +512,13 @@ def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n
         n_dead += torch.isneginf(loglik).all(dim=1).sum()
         cur_u, cur_t, cur_ll, acc = _close(i, key, loglik, prop_u, prop_lp, cur_u, cur_t, cur_ll)
         if path_thin:
-            prop_anchor, prop_noise = draw_path_records(loglik, filtered.particles, filtered.ancestors, i, key)
-            cur_anchor = torch.where(acc[:, None, None], prop_anchor.to(dtype), cur_anchor)
+            if jump_paths is not None:
+                # the int32 particles as float64 (exact), the anchors back to integers: a dead record's NaN becomes 0
+                prop_anchor, prop_noise = draw_path_records(loglik, filtered.particles.double(), filtered.ancestors, i, key)
+                prop_anchor = torch.nan_to_num(prop_anchor, nan=0.0).to(torch.int32)
+            else:
+                prop_anchor, prop_noise = draw_path_records(loglik, filtered.particles, filtered.ancestors, i, key)
+            cur_anchor = torch.where(acc[:, None, None], prop_anchor.to(anchor_dtype), cur_anchor)
             cur_noise = torch.where(acc[:, None], prop_noise, cur_noise)
             cur_iter = torch.where(acc, torch.full_like(cur_iter, i), cur_iter)
         window += acc.sum()
@@ -501,14 +541,24 @@ def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n
     if not path_thin:
         return out
     B = n_path * C
+    dead_rows = torch.where(noise_rows[:, :, -1] == DEAD_PATH, torch.full_like(iter_rows, -1), iter_rows)
+    if jump_paths is not None:
+        from . import jump_smoother as _js
+        t_out, q_begin, host_times = jump_paths
+        th = samples[::path_thin].reshape(B, P)
+        dead = noise_rows.reshape(B, K)[:, -1] == DEAD_PATH
+        paths, _, _ = _js.replay_records(sde, th if sde.plain else sde.kernel_parameters(th), x0[::R].repeat(n_path, 1), host_times, t_out,
+                                         q_begin, anchor_rows.reshape(B, K, S), torch.where(dead[:, None], 0, noise_rows.reshape(B, K)),
+                                         filter_keys(iter_rows.reshape(B), key), max_events, dead)
+        return out + (paths.reshape(n_path, C, -1, S), dead_rows)
     paths = replay_path_records(sde, obs, like, samples[::path_thin].reshape(B, P), x0[::R].repeat(n_path, 1), anchor_rows.reshape(B, K, S),
                                 noise_rows.reshape(B, K), filter_keys(iter_rows.reshape(B), key), dt, pos_state, proposal != "bootstrap",
                                 proposal == "residual_bridge")
-    return out + (paths.reshape(n_path, C, -1, S), torch.where(noise_rows[:, :, -1] == DEAD_PATH, torch.full_like(iter_rows, -1), iter_rows))
+    return out + (paths.reshape(n_path, C, -1, S), dead_rows)
 
 
 def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n_iterations, warmup, N, R, thin, proposal, L,
-                 step, adapt, target_accept, interval, key, estimator, trace, path_thin=0, max_events=0):
+                 step, adapt, target_accept, interval, key, estimator, trace, path_thin=0, jump_paths=None, max_events=0):
     """The loop with the step kernel: launch i closes iteration i - 1 and opens iteration i, the filter launch follows.  When the
     step size or L changes before iteration i (warm-up only) the proposal is opened again with the new values: the open half is a
     pure function of (state, i, key, step size, L).  With paths the filter stores particles and ancestors into two buffers
@@ -536,20 +586,27 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
         times, model = obs.times.to(torch.float64), _jf._launch_model(obs, like, u0)   # formed once for every launch of the loop
         x0 = x0.to(torch.int32).contiguous()
         filter_launch = lambda: _hip.jump_particle_filter(x0, kernel_theta(network, theta_prop), times, *model, fkey, max_events, N,
-                                                          network=network)
+                                                          network=network, store=jump_store)
     else:
         rows, model = _pf._launch_model(obs, like, u0, dt)                 # formed once for every launch of the loop
         x0 = x0.contiguous()
         filter_launch = lambda: _pf._kernel_call("particle_filter", proposal, (kind, x0, kernel_theta(network, theta_prop), rows), model,
                                                  fkey, dt, N, pos_state, network=network, store=store)
     logliks, loglik, window_base, pending = [], None, 0, None
-    store = None
+    store = jump_store = None
     if path_thin:
         K, S = obs.values.shape[0], x0.shape[1]
         i32 = dict(device=dev, dtype=torch.int32)
         n_path = (n_keep + path_thin - 1) // path_thin
-        n_steps = int(round(float(obs.times[-1]) / dt))                # read here: nothing is read back once the loop runs
-        store = (torch.empty(C * R, K, N, S, **f32), torch.empty(C * R, K, N, **i32))
+        if jump_paths is None:
+            n_steps = int(round(float(obs.times[-1]) / dt))            # read here: nothing is read back once the loop runs
+            store = (torch.empty(C * R, K, N, S, **f32), torch.empty(C * R, K, N, **i32))
+        else:
+            # the jump filter stores int32 particles; the step kernel's record half only copies 32-bit words, so it gets the same
+            # memory as fp32 words, and so do the anchors it writes: integers under an fp32 view.  The NaN it writes into a dead
+            # record's anchors is never read: deadness is noise_path
+            jump_store = (torch.empty(C * R, K, N, S, **i32), torch.empty(C * R, K, N, **i32))
+            store = (jump_store[0].view(torch.float32), jump_store[1])
         cur_anchor, cur_noise = torch.full((C, K, S), float("nan"), **f32), torch.full((C, K), -1, **i32)   # all ones: dead
         cur_iter = torch.full((C,), -1, **i32)
         anchor_rows, noise_rows, iter_rows = torch.empty(n_path, C, K, S, **f32), torch.empty(n_path, C, K, **i32), torch.empty(n_path, C, **i32)
@@ -575,7 +632,8 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
         if trace is not None and pending is not None:
             pending.update(accept=(n_acc - before) > 0, cur_u=cur_u.clone(), cur_log_target=cur_t.clone(), cur_loglik=cur_ll.clone())
             if path_thin:
-                pending.update(cur_anchor=cur_anchor.clone(), cur_noise_path=cur_noise.long() & DEAD_PATH, cur_path_iteration=cur_iter.clone())
+                pending.update(cur_anchor=(cur_anchor.view(torch.int32) if jump_paths is not None else cur_anchor).clone(),
+                               cur_noise_path=cur_noise.long() & DEAD_PATH, cur_path_iteration=cur_iter.clone())
             trace.append(pending)
         if i == n_iterations:
             break
@@ -605,10 +663,17 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
     if not path_thin:
         return out
     B = n_path * C
+    dead_rows = torch.where(noise_rows[:, :, -1] == -1, torch.full_like(iter_rows, -1), iter_rows)
+    if jump_paths is not None:
+        t_out, q_begin, _ = jump_paths
+        paths, _, _ = _hip.jump_anchored_replay(x0[::R].repeat(n_path, 1), kernel_theta(network, samples[::path_thin].reshape(B, P)), times,
+                                                t_out.to(dev), q_begin, anchor_rows.view(torch.int32).view(B, K, S), noise_rows.view(B, K),
+                                                filter_keys(iter_rows.view(B), key), max_events, network=network)
+        return out + (paths.view(n_path, C, -1, S), dead_rows)
     record = (kind, x0[::R].repeat(n_path, 1), kernel_theta(network, samples[::path_thin].reshape(B, P)), rows)
     paths = _pf._kernel_call("anchored_replay", proposal, record, model, anchor_rows.view(B, K, S), noise_rows.view(B, K),
                              filter_keys(iter_rows.view(B), key), dt, pos_state, network=network, n_steps=n_steps)
-    return out + (paths.view(n_path, C, -1, S), torch.where(noise_rows[:, :, -1] == -1, torch.full_like(iter_rows, -1), iter_rows))
+    return out + (paths.view(n_path, C, -1, S), dead_rows)
 
 
 def split_r_hat_and_ess(draws: Tensor) -> tuple[Tensor, Tensor]:
@@ -650,14 +715,18 @@ def split_r_hat_and_ess(draws: Tensor) -> tuple[Tensor, Tensor]:
     return r_hat, torch.where(torch.isfinite(r_hat), ess, nan)
 
 
-def _path_fields(paths: Tensor, path_iteration: Tensor) -> dict:
-    """The ``path_*`` fields of the result from ``paths [n_path, C, T+1, S]``: moments and quantiles over the live draws."""
+def _path_fields(paths: Tensor, path_iteration: Tensor, dtype=None) -> dict:
+    """The ``path_*`` fields of the result from ``paths [n_path, C, T+1, S]``: moments and quantiles over the live draws, in
+    ``dtype`` (the chain's; the integer paths of the jump process are converted for them, ``paths`` itself stays as it is)."""
     from ..posterior.variational_posterior import _QUANTILE_MAX_ELEMENTS, QUANTILE_LEVELS, Quantiles
+    kept = paths
+    if dtype is not None and paths.dtype != dtype:
+        paths = paths.to(dtype)
     n_path, C, T1, S = paths.shape
     live = path_iteration >= 0                                           # [n_path, C]
     flat = paths.reshape(n_path * C, T1 * S)[live.reshape(-1)]
     nan = torch.full((T1, S), float("nan"), device=paths.device, dtype=paths.dtype)
-    fields = dict(paths=paths, path_iteration=path_iteration, path_mean=nan, path_std=nan, path_mean_standard_error=nan,
+    fields = dict(paths=kept, path_iteration=path_iteration, path_mean=nan, path_std=nan, path_mean_standard_error=nan,
                   path_quantiles=Quantiles(*([nan] * len(QUANTILE_LEVELS))))
     if flat.shape[0] == 0:
         return fields
@@ -673,7 +742,7 @@ def _path_fields(paths: Tensor, path_iteration: Tensor) -> dict:
     return fields
 
 
-def _result(samples, lls, tgts, rate, step, L, n_dead, mask, paths=None, path_iteration=None) -> ParticleMCMCResult:
+def _result(samples, lls, tgts, rate, step, L, n_dead, mask, paths=None, path_iteration=None, path_times=None) -> ParticleMCMCResult:
     from ..posterior.variational_posterior import QUANTILE_LEVELS, Quantiles
     n_keep, C, P = samples.shape
     flat = samples.reshape(n_keep * C, P)
@@ -686,4 +755,4 @@ def _result(samples, lls, tgts, rate, step, L, n_dead, mask, paths=None, path_it
         std=flat.std(dim=0) if flat.shape[0] > 1 else torch.zeros_like(nan), quantiles=Quantiles(*torch.quantile(flat, levels, dim=0).unbind(0)),
         mean_standard_error=chain_means.std(dim=0) / math.sqrt(C) if C > 1 else nan, r_hat=r_hat, effective_sample_size=ess,
         step_size=float(step), proposal_scale_tril=L, n_filters_dead=int(n_dead),
-        **({} if paths is None else _path_fields(paths, path_iteration)))
+        **({} if paths is None else _path_fields(paths, path_iteration, samples.dtype)), path_times=path_times)

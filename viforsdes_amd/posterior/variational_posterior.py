@@ -570,7 +570,7 @@ class VariationalPosterior:
     def refine_parameters(self, sde: SDE, observation_likelihood: ObservationLikelihood, n_chains: int = 256,
                           n_iterations: int = 600, warmup: int = 300, n_particles: int = 512, filters_per_chain: int = 1,
                           thin: int = 1, proposal: str = "bootstrap", return_paths: bool = False, path_thin: int = 1,
-                          dynamics: str = "diffusion", max_events: int = 2 ** 16):
+                          dynamics: str = "diffusion", max_events: int = 2 ** 16, path_times=None):
         """When ``reweight_parameters`` says q(theta) is poor (a small ``effective_sample_size``: a mean-field q cannot follow a
         correlated posterior), this gives something better: ``n_chains`` independent particle-MCMC chains (``particle_mcmc``) started
         at draws of q under the EMA weights, as ``reweight_parameters`` draws them, which sample the exact theta posterior of the
@@ -583,7 +583,9 @@ class VariationalPosterior:
         ``summary().diffusion_path_mean``, where ``smooth_paths`` is an importance sample around q.  It runs on a CPU posterior too (the torch route) and touches none of ``sample()``'s caches or
         graphs.  ``dynamics="jump"`` (a ``ReactionNetworkSDE``): the chains target the theta posterior of the exact jump process
         (``particle_mcmc(..., dynamics="jump", max_events=...)``): the start state is the first observation, which must hold
-        integers, ``proposal`` must be ``"bootstrap"`` and paths are not kept."""
+        integers and ``proposal`` must be ``"bootstrap"``.  A jump process has no grid: with ``return_paths=True`` it needs
+        ``path_times`` (float64 ``[Q]``, non-decreasing, inside ``[0, T_{K-1}]``), the instants the integer paths ``[n_path, C, Q, S]``
+        are read at."""
         import dataclasses
         from ..inference import particle_mcmc as _mc
         if n_chains < 1:
@@ -600,7 +602,8 @@ class VariationalPosterior:
                                 warmup=warmup, n_particles=n_particles, filters_per_chain=filters_per_chain, thin=thin,
                                 theta_positive_dims=q._positive_dims, positive_dims=self.state_space.positive_dims,
                                 initial_state=self.observations.values[0], proposal=proposal, proposal_scale_tril=scale,
-                                return_paths=return_paths, path_thin=path_thin, dynamics=dynamics, max_events=max_events)
+                                return_paths=return_paths, path_thin=path_thin, dynamics=dynamics, max_events=max_events,
+                                path_times=path_times)
         v_std = theta.std(dim=0) if n_chains > 1 else torch.zeros_like(theta[0])
         return dataclasses.replace(res, variational_mean=theta.mean(dim=0), variational_std=v_std)
 
