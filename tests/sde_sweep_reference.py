@@ -54,7 +54,9 @@ reactant of the second-order reaction, and the step from the floor, 1e-6 + f dt,
 to 16 reactions in its magnitude.  The rate-law cells have one for the coefficients: a Hill / Michaelis-Menten propensity makes
 three or four roundings more than the mass-action product its magnitude stands for.
 
-The jump kernels run the same networks (second half of this module; tests/test_jump_sweep.py, tests/test_jump_sweep_gpu.py).
+The jump kernels run the same networks (second half of this module; tests/test_jump_sweep.py, tests/test_jump_sweep_gpu.py), and
+so does the jump-segment replay kernel (last part; DESIGN section 3.33, tests/test_jump_replay_sweep.py,
+tests/test_jump_replay_sweep_gpu.py).
 """
 import functools
 
@@ -240,3 +242,91 @@ def filter_conditions(name, big=False, salt=None):
 def find_salts(conditions, names, tries=200, **kw):
     """Per case the first key salt whose float64 run meets ``conditions`` (-1: none in ``tries``)."""
     return tuple(next((s for s in range(tries) if conditions(n, salt=s, **kw)["ok"]), -1) for n in names)
+
+
+# ====================================================================================================== jump-segment replay
+# The same cases on the replay kernel (csrc/vsde_jump_replay.hip: jr_kernel<S, NR, KIN, ANCHORED>; DESIGN section 3.33;
+# tests/test_jump_replay_sweep.py, tests/test_jump_replay_sweep_gpu.py): the filter case of a cell, D = 22 draws per filter whose final
+# slots come from a seeded generator, the output times of tests/jump_smoother_reference.py.
+JR_D = 22                       # B K = 3 * 22 * 4 = 264 threads: a full 256-thread block and a block of 8; B = 66 is no power of two
+JR_CAP = 4096                   # = JF_MAX_EVENTS: no segment stops
+JR_SMALL_CAP = 4                # the smallest cap at which the float64 replay alone meets ``replay_conditions`` and the two sweep-wide
+#                                 conditions of tests/test_jump_replay_sweep.py (``find_small_cap`` reproduces it)
+JR_INTERIOR = ((1, 0, 3), (2, 0, 3), (4, 3, 6), (5, 3, 6))      # (interior output, the observation-time outputs on either side)
+
+
+def last_slots(name):
+    """last_slot int32 [M, D] of a case: every row holds slot 0, slot N - 1, one slot twice and one -1 (a dead draw among live
+    ones), at positions shuffled per row."""
+    rng = np.random.default_rng(400 + NAMES.index(name))
+    rows = rng.integers(0, JF_N, size=(JF_M, JR_D))
+    rows[:, 0], rows[:, 1], rows[:, 3], rows[:, 4] = 0, JF_N - 1, rows[:, 2], -1
+    return np.stack([row[rng.permutation(JR_D)] for row in rows]).astype(np.int32)
+
+
+def replay_case(name, salt=None):
+    """``filter_case(name)`` and the final slots: (net, theta fp32 [M, P] (torch), xs [M, S], ys, likelihood, key, N, last_slot)."""
+    return filter_case(name, salt=salt) + (last_slots(name),)
+
+
+@functools.lru_cache(maxsize=None)
+def replay_lineages(name, salt=None):
+    """The float64 filter of a case alone and the records along the lineages of ``last_slots``: (tab, times, path times, the
+    arguments (x0, rates, anchors, noise_path, keys) of ``jump_smoother_reference.replay_records``).  No kernel output enters."""
+    import jump_filter_reference as jf
+    import jump_process_reference as jref
+    import jump_smoother_reference as js
+    net, th, xs, ys, like, key, N, last = replay_case(name, salt)
+    tab = jref.tables(net)
+    rates = net.kernel_parameters(th.double()).numpy()
+    flt = jf.run_filter(tab, xs, rates, JUMP_TIMES, ys, like, N, key, JF_MAX_EVENTS, vectorized=True)
+    assert int(flt["stopped"].sum()) == 0
+    lineage = js.trace(flt["ancestors"], last)
+    return tab, JUMP_TIMES, js.REPLAY_PATH_TIMES, js.records_of_lineage(flt["particles"], lineage, xs, rates, key)
+
+
+@functools.lru_cache(maxsize=None)
+def replay_reference(name, cap, salt=None):
+    import jump_smoother_reference as js
+    tab, times, path_times, records = replay_lineages(name, salt)
+    return js.replay_records(tab, *records, times, path_times, cap)
+
+
+def replay_conditions(name, cap, salt=None):
+    """What the float64 replay of a case shows at the event cap ``cap``: flagged pairs, segments by status, whether some interior
+    output differs from the outputs at both neighbouring observation times in some record, and the status-1 segments that wrote
+    some of their outputs / none of them (among those that own any)."""
+    import jump_smoother_reference as js
+    out = replay_reference(name, cap, salt)
+    p, st = out["paths"], out["status"]
+    begin = js.ownership(js.REPLAY_PATH_TIMES, JUMP_TIMES)
+    live = replay_lineages(name, salt)[3][3][:, -1] != js.DEAD_PATH
+    moved = any(bool(((p[live, q] != p[live, a]).any(axis=1) & (p[live, q] != p[live, b]).any(axis=1) & (p[live, q] >= 0).all(axis=1)).any())
+                for q, a, b in JR_INTERIOR)
+    partial = empty = 0
+    for k in range(st.shape[1]):
+        own = p[:, begin[k]:begin[k + 1]]
+        if own.shape[1]:
+            written = (own >= 0).all(axis=2).sum(axis=1)
+            partial += int(((st[:, k] == 1) & (written > 0) & (written < own.shape[1])).sum())
+            empty += int(((st[:, k] == 1) & (written == 0)).sum())
+    by_status = np.bincount(st[live].reshape(-1), minlength=3).tolist()
+    flagged, pairs = int(out["undecidable"].sum()), st.size
+    # a complete segment of three events: with the cap's stopped segments it has drawn both halves of the first Philox block and
+    # from the second (``e >> 1`` = 0, 0, 1, 1)
+    three = bool(((st == 0) & (out["n_events"] == 3)).any())
+    ok = flagged <= js.CAP * pairs and (by_status[1:] == [0, 0] and moved if cap == JR_CAP else by_status[0] > 0 and by_status[1] > 0)
+    return dict(flagged=flagged, pairs=pairs, by_status=by_status, moved=moved, partial=partial, empty=empty, three=three,
+                events=int(out["n_events"].sum()), ok=ok)
+
+
+def find_small_cap(tries=8, second_block=True):
+    """The smallest cap in 1 .. tries at which every case meets ``replay_conditions`` and the sweep shows a status-1 segment that
+    wrote some of its outputs and one that wrote none (-1: no such cap).  ``second_block``: every case also shows a complete
+    segment of three events, so that complete and stopped segments both reach the second Philox block; without it a cap of 1
+    would do, at which no segment ever takes the odd half of a block."""
+    for cap in range(1, tries + 1):
+        cs = [replay_conditions(n, cap) for n in NAMES]
+        if all(c["ok"] and (c["three"] or not second_block) for c in cs) and sum(c["partial"] for c in cs) > 0 and sum(c["empty"] for c in cs) > 0:
+            return cap
+    return -1
