@@ -24,19 +24,45 @@ __device__ __forceinline__ float to_f32(float x) { return x; }
 __device__ __forceinline__ float to_f32(bf16_t x) { return __uint_as_float(((uint32_t)x.v) << 16); }
 template <typename T> __device__ __forceinline__ T from_f32(float x);
 template <> __device__ __forceinline__ float from_f32<float>(float x) { return x; }
-template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float x) {  // round to nearest even
-    uint32_t u = __float_as_uint(x);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return bf16_t{(uint16_t)((u >> 16) | 0x40)};
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return bf16_t{(uint16_t)(u >> 16)};
+// fp32 -> bf16 is the hardware conversion (v_cvt_pk_bf16_f32: round to nearest even, a NaN becomes a quiet NaN), two values per
+// instruction where a pair is at hand.  The integer form it replaced (a NaN test, an add and a shift per value) gives the same bits
+// for every finite input and was over half of the VALU work of the LayerNorm backward.
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 hwbf16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+    const f32x2_t v = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, hwbf16x2_t));
 }
+template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float x) { return bf16_t{__builtin_bit_cast(uint16_t, (__bf16)x)}; }
 template <typename T> __device__ __forceinline__ float rnd(float x) { return to_f32(from_f32<T>(x)); }
 
 __device__ __forceinline__ float sigm(float x) { return fast_rcp(1.0f + __expf(-x)); }
 
 // V contiguous elements of T <-> V floats with one (8/16-byte) memory instruction
+// Raw / load_raw / unpack: the same load with the words left as they arrive -- a look-ahead load that is unpacked where it is issued
+//   makes the compiler wait for it there, and holds twice the registers (bf16).
+// round: o <- rnd<T>(o) in place;  store_rounded: store, and leave in o the values as stored
 template <typename T, int V> struct Pack;
-template <int V> struct Pack<float, V> {
+template <typename T, int V> struct PackRaw {
+    static constexpr int BYTES = (int)sizeof(T) * V, NW = (BYTES + 3) / 4;
+    struct Raw { uint32_t w[NW]; };
+    static __device__ __forceinline__ Raw load_raw(const T *p) {
+        Raw r;
+        if (BYTES == 16) { const uint4 t = *(const uint4 *)p; r.w[0] = t.x; r.w[1 % NW] = t.y; r.w[2 % NW] = t.z; r.w[3 % NW] = t.w; }
+        else if (BYTES == 8) { const uint2 t = *(const uint2 *)p; r.w[0] = t.x; r.w[1 % NW] = t.y; }
+        else if (BYTES == 4) r.w[0] = *(const uint32_t *)p;
+        else r.w[0] = *(const uint16_t *)p;
+        return r;
+    }
+};
+template <int V> struct Pack<float, V> : PackRaw<float, V> {
+    using typename PackRaw<float, V>::Raw;
+    static __device__ __forceinline__ void unpack(const Raw &r, float (&o)[V]) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) o[i] = __uint_as_float(r.w[i]);
+    }
+    static __device__ __forceinline__ void round(float (&)[V]) {}
+    static __device__ __forceinline__ void store_rounded(float *p, float (&o)[V]) { store(p, o); }
     static __device__ __forceinline__ void load(const float *p, float (&o)[V]) {
         if (V == 4) { float4 t = *(const float4 *)p; o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w; }
         else if (V == 2) { float2 t = *(const float2 *)p; o[0] = t.x; o[1] = t.y; }
@@ -54,7 +80,37 @@ template <int V> struct Pack<float, V> {
         }
     }
 };
-template <int V> struct Pack<bf16_t, V> {
+template <int V> struct Pack<bf16_t, V> : PackRaw<bf16_t, V> {
+    using typename PackRaw<bf16_t, V>::Raw;
+    static __device__ __forceinline__ void unpack(const Raw &r, float (&o)[V]) {
+        if (V == 1) o[0] = __uint_as_float(r.w[0] << 16);
+#pragma unroll
+        for (int i = 0; i < V / 2; ++i) { o[2 * i] = __uint_as_float(r.w[i] << 16); o[2 * i + 1] = __uint_as_float(r.w[i] & 0xffff0000u); }
+    }
+    static __device__ __forceinline__ void round(float (&o)[V]) {
+        if (V == 1) o[0] = rnd<bf16_t>(o[0]);
+#pragma unroll
+        for (int i = 0; i < V / 2; ++i) {
+            const uint32_t w = pack_bf16x2(o[2 * i], o[2 * i + 1]);
+            o[2 * i] = __uint_as_float(w << 16); o[2 * i + 1] = __uint_as_float(w & 0xffff0000u);
+        }
+    }
+    static __device__ __forceinline__ void store_rounded(bf16_t *p, float (&o)[V]) {
+        if (V == 8 || V == 4 || V == 2) {
+            uint32_t w[V / 2 > 0 ? V / 2 : 1];
+#pragma unroll
+            for (int i = 0; i < V / 2; ++i) {
+                w[i] = pack_bf16x2(o[2 * i], o[2 * i + 1]);
+                o[2 * i] = __uint_as_float(w[i] << 16); o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+            }
+            store_words(p, w);
+        } else { round(o); store(p, o); }
+    }
+    static __device__ __forceinline__ void store_words(bf16_t *p, const uint32_t (&w)[V / 2 > 0 ? V / 2 : 1]) {
+        if (V == 8) *(uint4 *)p = make_uint4(w[0], w[1], w[2 % (V / 2 > 0 ? V / 2 : 1)], w[3 % (V / 2 > 0 ? V / 2 : 1)]);
+        else if (V == 4) *(uint2 *)p = make_uint2(w[0], w[1 % (V / 2 > 0 ? V / 2 : 1)]);
+        else *(uint32_t *)p = w[0];
+    }
     static __device__ __forceinline__ void load(const bf16_t *p, float (&o)[V]) {
         if (V == 8) { uint4 t = *(const uint4 *)p; const uint32_t w[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
@@ -72,10 +128,8 @@ template <int V> struct Pack<bf16_t, V> {
         if (V == 8 || V == 4 || V == 2) {
             uint32_t w[V / 2 > 0 ? V / 2 : 1];
 #pragma unroll
-            for (int i = 0; i < V / 2; ++i) w[i] = (uint32_t)from_f32<bf16_t>(o[2 * i]).v | ((uint32_t)from_f32<bf16_t>(o[2 * i + 1]).v << 16);
-            if (V == 8) *(uint4 *)p = make_uint4(w[0], w[1], w[2 % (V / 2)], w[3 % (V / 2)]);
-            else if (V == 4) *(uint2 *)p = make_uint2(w[0], w[1 % (V / 2)]);
-            else *(uint32_t *)p = w[0];
+            for (int i = 0; i < V / 2; ++i) w[i] = pack_bf16x2(o[2 * i], o[2 * i + 1]);
+            store_words(p, w);
         } else {
 #pragma unroll
             for (int i = 0; i < V; ++i) p[i] = from_f32<bf16_t>(o[i]);
@@ -92,6 +146,112 @@ __device__ __forceinline__ float seg_sum(float v, int width) {
     return v;
 }
 
+// The token walk of ln_mod_fwd_kernel.  RES: the input of the norm is the gated residual x + gate * res_y, which is also written
+// to xnew (same rounding points as gated_residual followed by ln_modulate).
+// Grid-stride over the tokens: a capped grid of resident workgroups keeps more bytes in flight per CU than one tiny workgroup per
+// 8 tokens (round 3).  Everything the NEXT token needs -- its x / res_y rows and the gate, scale and shift rows of its batch row --
+// is requested before the current token is reduced and stays packed until then; two buffers take turns, so nothing is copied and
+// the wait for a token comes after the requests for the next one.  The stride of the walk (grid x tokens per workgroup) exceeds N
+// at every shape that strides at all, so the batch row changes with every token: its vectors cannot be kept, only asked for early;
+// the row index is stepped (one 64-bit division per thread, not one per token).
+// The last trip requests its own token again, and RES is a template argument: a load in a branch of its own makes the compiler
+// wait for every load there.
+// Contraction is off and each fused multiply-add is written out, so the bits do not depend on what the compiler decides to fuse.
+template <typename T, int V, int LPR, int NSLAB, bool RES>
+__device__ __forceinline__ void ln_mod_fwd_tokens(const T *__restrict__ x, const T *__restrict__ scale,
+                                                  const T *__restrict__ shift, T *__restrict__ y,
+                                                  float *__restrict__ mean, float *__restrict__ rstd, int64_t M,
+                                                  int N, int C, float eps, const T *__restrict__ res_y,
+                                                  const T *__restrict__ res_gate, T *__restrict__ xnew, int64_t mp) {
+#pragma clang fp contract(off)
+    using P = Pack<T, V>;
+    using Raw = typename P::Raw;
+    constexpr int SLOTS = 256 / LPR;
+    const int lane = threadIdx.x & (LPR - 1);
+    const int64_t stride = (int64_t)gridDim.x * SLOTS;
+    int64_t m = (int64_t)blockIdx.x * SLOTS + threadIdx.x / LPR;
+    if (m >= M) return;
+    const int64_t db = stride / N;
+    const int dn = (int)(stride - db * N);
+    int64_t b = m / N;
+    int n = (int)(m - b * N);
+    struct Token { Raw x[NSLAB], ry[NSLAB], gate[NSLAB], sc[NSLAB], sh[NSLAB]; };
+    auto fetch = [&](int64_t mm, int64_t bb, Token &t) {
+#pragma unroll
+        for (int sl = 0; sl < NSLAB; ++sl) {
+            const int c = (sl * LPR + lane) * V;
+            t.x[sl] = P::load_raw(x + mm * C + c);
+            if (RES) { t.ry[sl] = P::load_raw(res_y + mm * C + c); t.gate[sl] = P::load_raw(res_gate + bb * mp + c); }
+            t.sc[sl] = P::load_raw(scale + bb * mp + c); t.sh[sl] = P::load_raw(shift + bb * mp + c);
+        }
+    };
+    auto token = [&](int64_t mm, const Token &cur) {
+        float v[NSLAB][V];
+        float s = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < NSLAB; ++sl) {
+            P::unpack(cur.x[sl], v[sl]);
+            if (RES) {
+                float rg[V], t[V];
+                P::unpack(cur.gate[sl], rg); P::unpack(cur.ry[sl], t);
+#pragma unroll
+                for (int e = 0; e < V; ++e) t[e] = sizeof(T) == 4 ? t[e] : rg[e] * t[e];
+                P::round(t);
+#pragma unroll   // fp32 rounds nothing in between: one fused multiply-add
+                for (int e = 0; e < V; ++e) v[sl][e] = sizeof(T) == 4 ? __builtin_fmaf(rg[e], t[e], v[sl][e]) : v[sl][e] + t[e];
+                P::store_rounded(xnew + mm * C + (sl * LPR + lane) * V, v[sl]);
+            }
+#pragma unroll
+            for (int e = 0; e < V; ++e) s += v[sl][e];
+        }
+        const float mu = seg_sum(s, LPR) / C;
+        // sum of squares as the compiler contracted `q += d * d` from q = 0 before it was written out: the first two terms are
+        // fma(d0, d0, d1 * d1) (V = 1, where they sit in different slabs: fma(d1, d1, d0 * d0)), every further one is an fma onto the sum
+        const float d0 = v[0][0] - mu;
+        float q = d0 * d0;
+#pragma unroll
+        for (int sl = 0; sl < NSLAB; ++sl)
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const float d = v[sl][e] - mu;
+                if (sl * V + e == 1) q = V == 1 ? __builtin_fmaf(d, d, q) : __builtin_fmaf(d0, d0, d * d);
+                else if (sl * V + e > 1) q = __builtin_fmaf(d, d, q);
+            }
+        // (one channel per lane: that contraction reached the first step of the lane sum instead)
+        const float qs = NSLAB * V == 1 ? seg_sum(__builtin_fmaf(d0, d0, __shfl_xor(q, LPR >> 1, 64)), LPR >> 1) : seg_sum(q, LPR);
+        const float rs = rsqrtf(qs / C + eps);
+        if (lane == 0) { mean[mm] = mu; rstd[mm] = rs; }
+#pragma unroll
+        for (int sl = 0; sl < NSLAB; ++sl) {
+            float sc[V], sh[V], o[V];
+            P::unpack(cur.sc[sl], sc); P::unpack(cur.sh[sl], sh);
+#pragma unroll
+            for (int e = 0; e < V; ++e) o[e] = __builtin_fmaf((v[sl][e] - mu) * rs, 1.0f + sc[e], sh[e]);
+            P::store(y + mm * C + (sl * LPR + lane) * V, o);
+        }
+    };
+    // Two tokens per trip, no exit between a request and its use, and a scheduling barrier behind each request: left alone, the
+    // compiler moves a request down to its use -- below such an exit, or below the other token's arithmetic
+    Token ta, tb;
+    fetch(m, b, ta);
+    while (m + stride < M) {
+        const int64_t m1 = m + stride, m2 = m1 + stride;
+        int64_t b1 = b + db, b2;
+        int n1 = n + dn, n2;
+        if (n1 >= N) { n1 -= N; ++b1; }
+        b2 = b1 + db; n2 = n1 + dn;
+        if (n2 >= N) { n2 -= N; ++b2; }
+        fetch(m1, b1, tb);
+        __builtin_amdgcn_sched_barrier(0);
+        token(m, ta);
+        fetch(m2 < M ? m2 : m1, m2 < M ? b2 : b1, ta);
+        __builtin_amdgcn_sched_barrier(0);
+        token(m1, tb);
+        m = m2; b = b2; n = n2;
+    }
+    if (m < M) token(m, ta);
+}
+
 // LPR lanes (64 or 32) per token, 256/LPR tokens per block; a lane owns V contiguous channels of each
 // LPR*V-wide slab (<= 4 slabs).  C = 256 in bf16 runs as 32 lanes x 16 bytes: two tokens per wavefront.
 template <typename T, int V, int LPR, int NSLAB>
@@ -100,8 +260,46 @@ __global__ void __launch_bounds__(256) ln_mod_fwd_kernel(const T *__restrict__ x
                                                          float *__restrict__ mean, float *__restrict__ rstd, int64_t M,
                                                          int N, int C, float eps, const T *__restrict__ res_y,
                                                          const T *__restrict__ res_gate, T *__restrict__ xnew, int64_t mp) {
-    // res_y != nullptr: the input of the norm is the gated residual x + gate * res_y, which is also written to xnew
-    // (same rounding points as gated_residual followed by ln_modulate).
+    if (res_y) ln_mod_fwd_tokens<T, V, LPR, NSLAB, true>(x, scale, shift, y, mean, rstd, M, N, C, eps, res_y, res_gate, xnew, mp);
+    else ln_mod_fwd_tokens<T, V, LPR, NSLAB, false>(x, scale, shift, y, mean, rstd, M, N, C, eps, res_y, res_gate, xnew, mp);
+}
+
+#ifdef VSDE_ABLATIONS
+// VSDE_LN_STREAM=0 (tools' build): ln_mod_fwd_kernel / ln_mod_bwd_kernel as they were before the streaming form, with the integer
+// bf16 rounding they were built on -- the reference of tests/test_ln_stream_gpu.py (bit-identical outputs) and of tools/lnbench.py.
+namespace v0 {
+template <typename T> __device__ __forceinline__ T from_f32(float x);
+template <> __device__ __forceinline__ float from_f32<float>(float x) { return x; }
+template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float x) {  // round to nearest even
+    uint32_t u = __float_as_uint(x);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return bf16_t{(uint16_t)((u >> 16) | 0x40)};
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return bf16_t{(uint16_t)(u >> 16)};
+}
+template <typename T> __device__ __forceinline__ float rnd(float x) { return to_f32(from_f32<T>(x)); }
+template <typename T, int V> struct Pack : vsde::Pack<T, V> {};
+template <int V> struct Pack<bf16_t, V> : vsde::Pack<bf16_t, V> {
+    static __device__ __forceinline__ void store(bf16_t *p, const float (&o)[V]) {
+        if (V == 8 || V == 4 || V == 2) {
+            uint32_t w[V / 2 > 0 ? V / 2 : 1];
+#pragma unroll
+            for (int i = 0; i < V / 2; ++i) w[i] = (uint32_t)from_f32<bf16_t>(o[2 * i]).v | ((uint32_t)from_f32<bf16_t>(o[2 * i + 1]).v << 16);
+            if (V == 8) *(uint4 *)p = make_uint4(w[0], w[1], w[2 % (V / 2)], w[3 % (V / 2)]);
+            else if (V == 4) *(uint2 *)p = make_uint2(w[0], w[1 % (V / 2)]);
+            else *(uint32_t *)p = w[0];
+        } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i) p[i] = from_f32<bf16_t>(o[i]);
+        }
+    }
+};
+
+template <typename T, int V, int LPR, int NSLAB>
+__global__ void __launch_bounds__(256) ln_mod_fwd_kernel(const T *__restrict__ x, const T *__restrict__ scale,
+                                                         const T *__restrict__ shift, T *__restrict__ y,
+                                                         float *__restrict__ mean, float *__restrict__ rstd, int64_t M,
+                                                         int N, int C, float eps, const T *__restrict__ res_y,
+                                                         const T *__restrict__ res_gate, T *__restrict__ xnew, int64_t mp) {
     // Grid-stride over the tokens with the next token's x / res_y rows requested before the current one is normalised: a capped
     // grid of resident workgroups keeps more bytes in flight per CU than one tiny workgroup per 8 tokens (round 3).
     const int lane = threadIdx.x & (LPR - 1);
@@ -161,6 +359,8 @@ __global__ void __launch_bounds__(256) ln_mod_fwd_kernel(const T *__restrict__ x
             for (int e = 0; e < V; ++e) { v[sl][e] = nv[sl][e]; ry[sl][e] = nry[sl][e]; }
     }
 }
+}  // namespace v0
+#endif
 
 // Backward passes that also need a per-(batch row, channel) sum over the N tokens.  Grid (nchunk, B): a block
 // walks one chunk of the tokens of one batch row, 256/LPR tokens at a time, writes the token gradients and keeps
@@ -195,6 +395,94 @@ __device__ __forceinline__ void colsum_block_reduce(float *red, const float (&ac
     }
 }
 
+// The token walk of ln_mod_bwd_kernel: tokens n, n + SLOTS, ... < n1 of batch row row0 / N for one token slot.
+// Two-stage pipeline: every load of the next token (x, dy, dres, res_y rows, mean, rstd) is requested before the current token is
+// reduced across its lanes, and stays packed until then (18 registers at C = 256 bf16); two buffers take turns, so nothing is copied
+// and the wait for a token comes after the requests for the next one.  The last trip requests its own token again (in bounds,
+// unused), and DRES / RES are template arguments: a load in a branch of its own makes the compiler wait for every load there.
+// Contraction is off and each fused multiply-add is written out, so the bits do not depend on what the compiler decides to fuse.
+template <typename T, int V, int LPR, int NSLAB, bool DRES, bool RES>
+__device__ __forceinline__ void ln_mod_bwd_tokens(const T *__restrict__ x, const T *__restrict__ dy, const float *__restrict__ mean,
+                                                  const float *__restrict__ rstd, const T *__restrict__ dres, T *__restrict__ dx,
+                                                  const T *__restrict__ res_y, T *__restrict__ res_dy, int64_t row0, int C, int n,
+                                                  int n1, int lane, const float (&sc1)[NSLAB][V], const typename Pack<T, V>::Raw (&gate)[NSLAB],
+                                                  float (&a1)[NSLAB][V], float (&a2)[NSLAB][V], float (&a3)[NSLAB][V]) {
+#pragma clang fp contract(off)
+    using P = Pack<T, V>;
+    using Raw = typename P::Raw;
+    constexpr int SLOTS = 256 / LPR;
+    struct Token { Raw x[NSLAB], dy[NSLAB], dres[NSLAB], ry[NSLAB]; float mu, rs; };
+    auto fetch = [&](int nn, Token &t) {
+        const int64_t m = row0 + nn;
+        t.mu = mean[m]; t.rs = rstd[m];
+#pragma unroll
+        for (int sl = 0; sl < NSLAB; ++sl) {
+            const int64_t o = m * C + (sl * LPR + lane) * V;
+            t.x[sl] = P::load_raw(x + o); t.dy[sl] = P::load_raw(dy + o);
+            if (DRES) t.dres[sl] = P::load_raw(dres + o);
+            if (RES) t.ry[sl] = P::load_raw(res_y + o);
+        }
+    };
+    auto token = [&](int nn, const Token &cur) {
+        const int64_t m = row0 + nn;
+        const float mu = cur.mu, rs = cur.rs;
+        float g[NSLAB][V], xh[NSLAB][V];   // g: dy as loaded; dy * (1 + scale) is formed where it is used
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < NSLAB; ++sl) {
+            P::unpack(cur.x[sl], xh[sl]); P::unpack(cur.dy[sl], g[sl]);
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                xh[sl][e] = (xh[sl][e] - mu) * rs;
+                a1[sl][e] = __builtin_fmaf(g[sl][e], xh[sl][e], a1[sl][e]); a2[sl][e] += g[sl][e];
+                s1 = __builtin_fmaf(g[sl][e], sc1[sl][e], s1);
+                s2 = __builtin_fmaf(g[sl][e] * sc1[sl][e], xh[sl][e], s2);
+            }
+        }
+        s1 = seg_sum(s1, LPR) / C; s2 = seg_sum(s2, LPR) / C;
+#pragma unroll
+        for (int sl = 0; sl < NSLAB; ++sl) {
+            const int64_t oc = m * C + (sl * LPR + lane) * V;
+            float o[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {   // (the compiler's contraction had reached dy * (1 + scale) - s1 in the first slab only)
+                const float t = sl == 0 ? __builtin_fmaf(g[sl][e], sc1[sl][e], -s1) : g[sl][e] * sc1[sl][e] - s1;
+                o[e] = rs * __builtin_fmaf(-s2, xh[sl][e], t);
+            }
+            if (DRES) {  // x also feeds the residual branch: fold that gradient in here instead of a separate add
+                float r[V];
+                P::unpack(cur.dres[sl], r);
+#pragma unroll
+                for (int e = 0; e < V; ++e) o[e] += r[e];
+            }
+            P::store_rounded(dx + oc, o);   // o: dx as stored, which is what the residual branch sees
+            if (RES) {
+                float ry[V], gt[V], od[V];   // the gate stays packed between tokens: half the registers (bf16)
+                P::unpack(cur.ry[sl], ry); P::unpack(gate[sl], gt);
+#pragma unroll
+                for (int e = 0; e < V; ++e) { a3[sl][e] = __builtin_fmaf(o[e], ry[e], a3[sl][e]); od[e] = gt[e] * o[e]; }
+                P::store(res_dy + oc, od);
+            }
+        }
+    };
+    if (n >= n1) return;
+    // Two tokens per trip, no exit between a request and its use, and a scheduling barrier behind each request: left alone, the
+    // compiler moves a request down to its use -- below such an exit, or below the other token's arithmetic
+    Token ta, tb;
+    fetch(n, ta);
+    while (n + SLOTS < n1) {
+        const int n2 = n + 2 * SLOTS;
+        fetch(n + SLOTS, tb);
+        __builtin_amdgcn_sched_barrier(0);
+        token(n, ta);
+        fetch(n2 < n1 ? n2 : n + SLOTS, ta);
+        __builtin_amdgcn_sched_barrier(0);
+        token(n + SLOTS, tb);
+        n = n2;
+    }
+    if (n < n1) token(n, ta);
+}
+
 // ln_modulate backward: dx (+ dres) per token, and partial sums of dy*xhat (part0) and dy (part1)
 template <typename T, int V, int LPR, int NSLAB>
 __global__ void __launch_bounds__(256) ln_mod_bwd_kernel(const T *__restrict__ x, const T *__restrict__ scale,
@@ -205,6 +493,54 @@ __global__ void __launch_bounds__(256) ln_mod_bwd_kernel(const T *__restrict__ x
                                                          T *__restrict__ res_dy, int64_t mp) {
     // res_y != nullptr: x is the output of a gated residual x0 + gate * res_y; dx is then also the gradient of x0, and the
     // kernel additionally writes res_dy = gate * dx and the partial sums of dx * res_y (part2: gradient of the gate)
+    extern __shared__ float red[];
+    constexpr int SLOTS = 256 / LPR;
+    const int lane = threadIdx.x & (LPR - 1), slot = threadIdx.x / LPR;
+    const int b = blockIdx.y, nchunk = gridDim.x, B = gridDim.y;
+    const int CL = (N + nchunk - 1) / nchunk;
+    const int n0 = blockIdx.x * CL, n1 = min(N, n0 + CL);
+    float sc1[NSLAB][V], a1[NSLAB][V], a2[NSLAB][V], a3[NSLAB][V];
+    typename Pack<T, V>::Raw gate[NSLAB] = {};
+#pragma unroll
+    for (int sl = 0; sl < NSLAB; ++sl) {
+        Pack<T, V>::load(scale + (int64_t)b * mp + (sl * LPR + lane) * V, sc1[sl]);
+#pragma unroll
+        for (int e = 0; e < V; ++e) sc1[sl][e] += 1.0f;
+        if (res_y) gate[sl] = Pack<T, V>::load_raw(res_gate + (int64_t)b * mp + (sl * LPR + lane) * V);
+#pragma unroll
+        for (int e = 0; e < V; ++e) { a1[sl][e] = 0.f; a2[sl][e] = 0.f; a3[sl][e] = 0.f; }
+    }
+    const int64_t row0 = (int64_t)b * N;
+    const int n = n0 + slot;
+#define LN_BWD_WALK(DRES, RES)                                                                                                \
+    ln_mod_bwd_tokens<T, V, LPR, NSLAB, DRES, RES>(x, dy, mean, rstd, dres, dx, res_y, res_dy, row0, C, n, n1, lane, sc1, gate, \
+                                                   a1, a2, a3)
+    if (dres) { if (res_y) LN_BWD_WALK(true, true); else LN_BWD_WALK(true, false); }
+    else { if (res_y) LN_BWD_WALK(false, true); else LN_BWD_WALK(false, false); }
+#undef LN_BWD_WALK
+    float *p0 = part + (((int64_t)0 * B + b) * nchunk + blockIdx.x) * C;
+    float *p1 = part + (((int64_t)1 * B + b) * nchunk + blockIdx.x) * C;
+#pragma unroll
+    for (int sl = 0; sl < NSLAB; ++sl) {
+        const int off = sl * LPR * V;
+        colsum_block_reduce<V>(red, a1[sl], slot, SLOTS, lane * V, LPR * V, p0 + off, C - off);
+        colsum_block_reduce<V>(red, a2[sl], slot, SLOTS, lane * V, LPR * V, p1 + off, C - off);
+        if (res_y) {
+            float *p2 = part + (((int64_t)2 * B + b) * nchunk + blockIdx.x) * C;
+            colsum_block_reduce<V>(red, a3[sl], slot, SLOTS, lane * V, LPR * V, p2 + off, C - off);
+        }
+    }
+}
+
+#ifdef VSDE_ABLATIONS
+namespace v0 {
+template <typename T, int V, int LPR, int NSLAB>
+__global__ void __launch_bounds__(256) ln_mod_bwd_kernel(const T *__restrict__ x, const T *__restrict__ scale,
+                                                         const T *__restrict__ dy, const float *__restrict__ mean,
+                                                         const float *__restrict__ rstd, const T *__restrict__ dres,
+                                                         T *__restrict__ dx, float *__restrict__ part, int N, int C,
+                                                         const T *__restrict__ res_y, const T *__restrict__ res_gate,
+                                                         T *__restrict__ res_dy, int64_t mp) {
     extern __shared__ float red[];
     constexpr int SLOTS = 256 / LPR;
     const int lane = threadIdx.x & (LPR - 1), slot = threadIdx.x / LPR;
@@ -280,6 +616,8 @@ __global__ void __launch_bounds__(256) ln_mod_bwd_kernel(const T *__restrict__ x
             }
         }
 }
+}  // namespace v0
+#endif
 
 // gated_residual backward: dy = gate * dout per token, and partial sums of dout * y (part0)
 template <typename T, int V>
@@ -632,8 +970,31 @@ static int ln_mod_dispatch(int which, const void *x, const void *scale, const vo
     constexpr int VF = VecOf<T>::v;  // 8 bf16 / 4 f32 = 16 bytes per lane
     const int64_t M = B * N;
     dim3 block(256);
+#ifdef VSDE_ABLATIONS
+    // VSDE_LN_STREAM=0: the kernel bodies before the streaming form (namespace v0), same launch plan; read at every call
+#define LNM_V0(V, LPR, NS)                                                                                                    \
+    if (vsde_knob("VSDE_LN_STREAM", 1) == 0) {                                                                                \
+        if (which == 0) {                                                                                                     \
+            int64_t nblk = (M + 256 / LPR - 1) / (256 / LPR);                                                                 \
+            const int64_t cap = ln_fwd_grid_cap();                                                                            \
+            dim3 grid((unsigned)(nblk < cap ? nblk : cap));                                                                   \
+            hipLaunchKernelGGL((v0::ln_mod_fwd_kernel<T, V, LPR, NS>), grid, block, 0, s, (const T *)x, (const T *)scale,     \
+                               (const T *)shift_or_dy, (T *)out, mean, rstd, M, N, C, eps, (const T *)res.y,                  \
+                               (const T *)res.gate, (T *)res.out, res.mp ? res.mp : (int64_t)C);                              \
+        } else {                                                                                                              \
+            hipLaunchKernelGGL((v0::ln_mod_bwd_kernel<T, V, LPR, NS>), dim3(colsum_chunks(B, N), (unsigned)B), block,         \
+                               256 * V * sizeof(float), s, (const T *)x, (const T *)scale, (const T *)shift_or_dy,            \
+                               (const float *)mean, (const float *)rstd, (const T *)dres, (T *)out, part, N, C,               \
+                               (const T *)res.y, (const T *)res.gate, (T *)res.out, res.mp ? res.mp : (int64_t)C);            \
+        }                                                                                                                     \
+        break;                                                                                                                \
+    }
+#else
+#define LNM_V0(V, LPR, NS)
+#endif
 #define LNM_N(V, LPR, NS)                                                                                                     \
     do {                                                                                                                      \
+        LNM_V0(V, LPR, NS)                                                                                                    \
         if (which == 0) {                                                                                                     \
             int64_t nblk = (M + 256 / LPR - 1) / (256 / LPR);                                                                 \
             const int64_t cap = ln_fwd_grid_cap();                                                                            \
@@ -665,6 +1026,7 @@ static int ln_mod_dispatch(int which, const void *x, const void *scale, const vo
         VSDE_CHECK_ARG(C / 64 <= 4, VSDE_E_BADARG, "ln_modulate: unsupported channel count %d", C);
         LNM(1, 64);
     }
+#undef LNM_V0
 #undef LNM_N
 #undef LNM
     VSDE_CHECK_HIP(hipGetLastError());
