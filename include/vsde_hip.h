@@ -970,6 +970,63 @@ int vsde_crn_kinetic_jump_anchored_replay(const vsde_crn_network *net, const vsd
                                           const int *q_begin, const int32_t *anchors, const uint32_t *noise_path, const uint32_t *keys,
                                           int max_events, int32_t *paths, int32_t *n_events, int32_t *status, void *stream);
 
+/* Tau-leaping for the jump process above: a fixed step tau = time_step with Poisson-many firings of every reaction on the integer
+ * state (viforsdes_amd/core/tau_leap.py is the specification).  B trajectories, a thread each: x0[B][S] (int32, 0 .. 2^30),
+ * theta[B][P] (P = R; the kinetic entry point takes rates[B][2R]), out_rows[K] (DEVICE int32, non-decreasing, >= 0: row r is read
+ * after the steps 0 .. r - 1), key: 2 words in DEVICE memory.
+ *   Step t of path b from the state x: a_j = the propensity of vsde_crn_jump_process (fp32); lam_j = a_j * (float)time_step, one
+ * fp32 product, then widened to float64; n_j = the Poisson draw below for every j, all on the propensities at the start of the
+ * step; then in reaction order on the running state (int64): n_j <- min(n_j, min over the species i with r_ji > 0 of floor(x_i /
+ * r_ji)), x <- x + n_j nu_j; a reduced n_j adds 1 to capped[b].  The path stops with status 2 at a NaN, infinite or negative a_j,
+ * a lam_j > 2^30, a failed draw, or an x_i > 2^30 after the last reaction of the step; it keeps the state from before that step,
+ * the step adds nothing to capped[b], and the rows it has not reached hold -1.  status 0: complete.
+ *   The draw, entirely in float64.  lam == 0: 0, no words read.  lam < 10: inversion on u1 of attempt 0: p = F = exp(-lam), n = 0;
+ * while u1 > F and n < 63: n += 1, p = p (lam / n), F = F + p.  lam >= 10: Hoermann's PTRS (1993): b = 0.931 + 2.53 sqrt(lam), a =
+ * -0.059 + 0.02483 b, 1/alpha = 1.1239 + 1.1328 / (b - 3.4), v_r = 0.9277 - 3.6224 / (b - 2); attempt q: Uc = u1 - 0.5, V = u2,
+ * us = 0.5 - |Uc|; reject if us < 0.013 and V > us; n = floor(((2 a) / us + b) Uc + lam + 0.43); accept if us >= 0.07 and V <=
+ * v_r; reject if n < 0; accept if (log V + log(1/alpha)) - log(a / (us us) + b) <= (-lam + n log lam) - lgamma(n + 1); the draw
+ * fails after 32 attempts.  Attempt q of reaction j at step t reads w = philox4x32_10(counter {t, j | ((q >> 1) << 16), b, 8},
+ * key): u1, u2 = the uniforms ((w >> 8) + 0.5) 2^-24 (fp32) of words 2 (q & 1), 2 (q & 1) + 1.
+ *   E > 0: draws[B][E][R] takes the raw draws (before the cap) of steps 0 .. E - 1, -1 from the step the path stopped at (or never
+ * took) on; E = 0: draws may be NULL.
+ *   VSDE_E_BADARG before any HIP call: a bad descriptor or one that disagrees with S / P; B or K < 1, E < 0, a time_step that is
+ * not positive and finite, a NULL pointer, a NULL draws with E > 0. */
+int vsde_crn_tau_leap_process(const vsde_crn_network *net, int B, int S, int P, int K, int E, const int32_t *x0, const float *theta,
+                              const int32_t *out_rows, const uint32_t *key, double time_step, int32_t *states, int32_t *status,
+                              int32_t *capped, int32_t *draws, void *stream);
+int vsde_crn_kinetic_tau_leap_process(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int B, int S, int P, int K, int E,
+                                      const int32_t *x0, const float *rates, const int32_t *out_rows, const uint32_t *key,
+                                      double time_step, int32_t *states, int32_t *status, int32_t *capped, int32_t *draws,
+                                      void *stream);
+
+/* Bootstrap particle filter whose particles are tau-leap trajectories (viforsdes_amd/inference/tau_leap_filter.py is the
+ * specification).  M filters, a workgroup each, N particles (a multiple of 64 up to 512: the float64 sampler needs more registers
+ * than a 1024-thread workgroup leaves a lane), a thread each: x0[M][S] (int32, 0 .. 2^30), theta[M][P] (the kinetic entry point:
+ * rates[M][2R]), obs_rows[K] (DEVICE int32, non-decreasing, >= 0), obs_values[K][O], obs_matrix[O][S] or NULL (O == S), key: 2
+ * words in DEVICE memory.
+ *   Segment k runs the steps obs_rows[k-1] .. obs_rows[k] - 1 (obs_rows[-1] = 0) of vsde_crn_tau_leap_process for particle slot j
+ * of filter m as path b = m N + j: a slot keeps its stream across resampling, and the tau-leap process is segment 0.  A stopped
+ * particle keeps its state, its log-weight at k is -inf, and it carries on from that state only if the whole filter is dead.
+ *   Observation k, the outputs log_likelihood[M], increments, ess [M][K], filtered_mean, filtered_std [M][K][S] and the optional
+ * particles[M][K][N][S] (int32, before resampling), ancestors[M][K][N], log_weights[M][K][N] are those of
+ * vsde_crn_jump_particle_filter.  stopped[M][K] counts the stopped particles of segment k, capped[M][K] the reduced draws of its
+ * particles (summed in fp32: exact up to 2^24).
+ *   VSDE_E_BADARG before any HIP call: as vsde_crn_jump_particle_filter, with time_step (positive, finite) in place of
+ * max_events. */
+int vsde_crn_tau_leap_particle_filter(const vsde_crn_network *net, int M, int N, int S, int P, int K, int O, const int32_t *x0,
+                                      const float *theta, const int32_t *obs_rows, const float *obs_values, const float *obs_matrix,
+                                      int lik_kind, double variance, double scale, double dispersion, const float *row_const,
+                                      const uint32_t *key, double time_step, float *log_likelihood, float *increments, float *ess,
+                                      float *filtered_mean, float *filtered_std, int32_t *stopped, int32_t *capped,
+                                      int32_t *particles, int *ancestors, float *log_weights, void *stream);
+int vsde_crn_kinetic_tau_leap_particle_filter(const vsde_crn_network *net, const vsde_crn_kinetics *kin, int M, int N, int S, int P,
+                                              int K, int O, const int32_t *x0, const float *rates, const int32_t *obs_rows,
+                                              const float *obs_values, const float *obs_matrix, int lik_kind, double variance,
+                                              double scale, double dispersion, const float *row_const, const uint32_t *key,
+                                              double time_step, float *log_likelihood, float *increments, float *ess,
+                                              float *filtered_mean, float *filtered_std, int32_t *stopped, int32_t *capped,
+                                              int32_t *particles, int *ancestors, float *log_weights, void *stream);
+
 /* Measurement aid (no reference counterpart): when enabled, the launchers bracket their kernels with hipEvents on the
  * launch stream.  which: 0 = serial time-stepping forward kernel (training variant), 1 = serial backward kernel,
  * 2 = everything vsde_head_forward enqueues (training variant), 3 = everything vsde_head_backward enqueues,

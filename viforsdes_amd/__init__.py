@@ -16,6 +16,7 @@ from .core.observations import (GaussianObservationLikelihood, NegativeBinomialO
 from .core.jump_process import (DiffusionApproximationCheck, JumpProcessResult, diffusion_approximation_check,
                                 jump_process)
 from .core.priors import Prior, PriorType
+from .core.tau_leap import TauLeapResult, tau_leap_process
 from .core.reaction_network import Hill, MichaelisMenten, ReactionNetworkSDE
 from .core.sde import SDE, FunctionalSDE, make_sde
 from .infer import InferenceConfig, infer
@@ -24,6 +25,7 @@ from .inference.jump_smoother import SmoothedJumpPaths, jump_particle_smoother
 from .inference.particle_filter import ParticleFilterResult, particle_filter
 from .inference.particle_mcmc import ParticleMCMCResult, particle_mcmc
 from .inference.particle_smoother import SmoothedPaths, particle_smoother
+from .inference.tau_leap_filter import TauLeapFilterResult, tau_leap_particle_filter
 from .posterior.variational_posterior import (EvidenceEstimate, ParameterReweighting, PathReweighting, PosteriorPredictive,
                                               VariationalPosterior)
 
@@ -34,5 +36,6 @@ __all__ = ["AmpDtype", "EncoderConfig", "HeadConfig", "PretrainConfig", "Trainin
            "EvidenceEstimate", "PosteriorPredictive", "ParameterReweighting", "ParticleFilterResult", "particle_filter",
            "PathReweighting", "SmoothedPaths", "particle_smoother", "ParticleMCMCResult", "particle_mcmc", "JumpProcessResult",
            "jump_process", "DiffusionApproximationCheck", "diffusion_approximation_check", "JumpParticleFilterResult",
-           "jump_particle_filter", "SmoothedJumpPaths", "jump_particle_smoother"]
+           "jump_particle_filter", "SmoothedJumpPaths", "jump_particle_smoother", "TauLeapResult", "tau_leap_process",
+           "TauLeapFilterResult", "tau_leap_particle_filter"]
 __version__ = "0.1.0"

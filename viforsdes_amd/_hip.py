@@ -80,6 +80,7 @@ EXPORTS = (
     "vsde_residual_anchored_replay", "vsde_crn_residual_anchored_replay", "vsde_crn_kinetic_residual_anchored_replay",
     "vsde_crn_jump_process", "vsde_crn_kinetic_jump_process", "vsde_crn_jump_particle_filter", "vsde_crn_kinetic_jump_particle_filter",
     "vsde_crn_jump_filter_replay", "vsde_crn_kinetic_jump_filter_replay", "vsde_crn_jump_anchored_replay", "vsde_crn_kinetic_jump_anchored_replay",
+    "vsde_crn_tau_leap_process", "vsde_crn_kinetic_tau_leap_process", "vsde_crn_tau_leap_particle_filter", "vsde_crn_kinetic_tau_leap_particle_filter",
     "vsde_linear_bf16_supported", "vsde_linear_bf16", "vsde_linear_qknorm_bf16", "vsde_linear_gated_bf16", "vsde_linear_gate_bwd_bf16",
     "vsde_mlp_image_bytes", "vsde_mlp_fwd_bf16", "vsde_mlp_block_fwd_bf16", "vsde_mlp_attn_block_fwd_bf16", "vsde_linear_deep256_bf16", "vsde_mlp_debug_trace", "vsde_wgrad_debug_trace", "vsde_attn_debug_trace", "vsde_mlp_bwd_image_bytes", "vsde_mlp_bwd_bf16",
     "vsde_pack_tile_bytes", "vsde_pack_refresh", "vsde_optim_chunk_bytes", "vsde_optim_chunk_elems", "vsde_optim_step",
@@ -645,6 +646,104 @@ def jump_particle_filter(x0, theta, obs_times, obs_values, obs_matrix, variance,
               _ptr(std), _ptr(stopped), _ptr(mean_events), _ptr(particles), _ptr(ancestors), _ptr(log_weights), _ptr(events),
               _stream(dev))
     return loglik, incr, ess, mean, std, stopped, mean_events, particles, ancestors, log_weights, events
+
+
+def tau_leap_process(x0, theta, out_rows, key, time_step: float, record_steps: int = 0, network=None):
+    """Tau-leap trajectories of a reaction network (include/vsde_hip.h: vsde_crn_tau_leap_process): x0 int32 [B, S], theta fp32
+    [B, P] (the effective constants [B, 2R] for a CrnKineticRoute), out_rows int32 [K] (non-decreasing grid rows >= 0) and key (2
+    int32 words), all on the device.  Returns ``(states int32 [B, K, S], status int32 [B], capped int32 [B], draws int32 [B, E, R]
+    or None)`` with E = ``record_steps``."""
+    lib = load()
+    dev = _require_hip(x0, theta, out_rows, key)
+    if x0.dtype != torch.int32 or x0.ndim != 2 or out_rows.dtype != torch.int32 or out_rows.ndim != 1:
+        raise ValueError("tau_leap_process: x0 must be an int32 [B, S] tensor and out_rows an int32 [K] tensor")
+    if key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2:
+        raise ValueError("tau_leap_process: key must be two int32 words")
+    x0, theta, out_rows, key = x0.contiguous(), _f32c(theta), out_rows.contiguous(), key.contiguous()
+    B, S = x0.shape
+    K, E = out_rows.shape[0], int(record_steps)
+    if theta.ndim != 2 or theta.shape[0] != B:
+        raise ValueError(f"tau_leap_process: theta {tuple(theta.shape)} does not have one row for each of the {B} start states")
+    if B < 1 or K < 1 or E < 0:
+        raise ValueError(f"tau_leap_process: bad dims B={B} K={K} E={E}")
+    net = network.network if isinstance(network, CrnKineticRoute) else network
+    R = int(net.R) if isinstance(net, CrnNetwork) else 0
+    with torch.cuda.device(dev):
+        i32 = dict(device=dev, dtype=torch.int32)
+        states, status, capped = torch.empty(B, K, S, **i32), torch.empty(B, **i32), torch.empty(B, **i32)
+        draws = torch.empty(B, E, R, **i32) if E and R else None
+        _call(*_sde_entry(lib, "tau_leap_process", "reaction_network", network), ctypes.c_int(B), ctypes.c_int(S),
+              ctypes.c_int(theta.shape[1]), ctypes.c_int(K), ctypes.c_int(E), _ptr(x0), _ptr(theta), _ptr(out_rows), _ptr(key),
+              ctypes.c_double(time_step), _ptr(states), _ptr(status), _ptr(capped), _ptr(draws), _stream(dev))
+    return states, status, capped, draws
+
+
+TAU_LEAP_FILTER_MAX_PARTICLES = PF_MAX_PARTICLES // 2
+
+
+def tau_leap_filter_max_particles(state_dim: int, n_reactions: int, kinetic: bool = False) -> int:
+    """The largest ``n_particles`` (a multiple of 64) the tau-leap filter kernel takes for a network of ``state_dim`` species and
+    ``n_reactions`` reactions, with rate laws or without (csrc/vsde_tau_leap.hip: tlf_max_n): the float64 Poisson sampler takes
+    118 .. 171 VGPRs, more than the 128 a lane has in a 1024-thread workgroup, so every instantiation is built for 512."""
+    if not (1 <= state_dim <= CRN_MAX_SPECIES and 1 <= n_reactions <= CRN_MAX_REACTIONS):
+        raise ValueError(f"tau_leap_filter_max_particles: {state_dim} species / {n_reactions} reactions outside 1..{CRN_MAX_SPECIES} / "
+                         f"1..{CRN_MAX_REACTIONS}")
+    return TAU_LEAP_FILTER_MAX_PARTICLES
+
+
+def tau_leap_particle_filter(x0, theta, obs_rows, obs_values, obs_matrix, variance, key, time_step: float, n_particles: int,
+                             network=None, return_particles: bool = False, store=None):
+    """Bootstrap particle filters on the tau-leap of a reaction network (include/vsde_hip.h: vsde_crn_tau_leap_particle_filter), one
+    per row of theta fp32 [M, P] (the effective constants [M, 2R] for a CrnKineticRoute) from the start states x0 int32 [M, S],
+    against obs_values fp32 [K, O] at the grid rows obs_rows int32 [K], with a Gaussian observation term (obs_matrix [O, S] or
+    None; ``variance``: a number) or a count term (``variance``: the likelihood's ``CountKernelTerms``); key: 2 int32 words;
+    everything on the device.  Returns (log_likelihood [M], increments [M, K], effective_sample_size [M, K], filtered_mean [M, K,
+    S], filtered_std [M, K, S], stopped int32 [M, K], capped int32 [M, K], and with ``return_particles``, else None: particles int32
+    [M, K, N, S], ancestors int32 [M, K, N], log_weights [M, K, N]).  ``store``: ``(particles, ancestors)``, contiguous int32
+    device buffers of those shapes to write into instead (no allocation per launch); they are returned in their places,
+    log_weights stays None."""
+    lib = load()
+    dev = _require_hip(x0, theta, obs_rows, obs_values, obs_matrix, key)
+    if x0.dtype != torch.int32 or x0.ndim != 2 or obs_rows.dtype != torch.int32 or obs_rows.ndim != 1:
+        raise ValueError("tau_leap_particle_filter: x0 must be an int32 [M, S] tensor and obs_rows an int32 [K] tensor")
+    if key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2:
+        raise ValueError("tau_leap_particle_filter: key must be two int32 words")
+    x0, theta, obs_rows, obs_values, key = x0.contiguous(), _f32c(theta), obs_rows.contiguous(), _f32c(obs_values), key.contiguous()
+    obs_matrix = None if obs_matrix is None else _f32c(obs_matrix)
+    if theta.ndim != 2 or theta.shape[0] != x0.shape[0] or obs_values.ndim != 2 or obs_values.shape[0] != obs_rows.shape[0]:
+        raise ValueError(f"tau_leap_particle_filter: x0 [M, S], theta [M, P], obs_values [K, O], obs_rows [K] expected, got "
+                         f"{tuple(x0.shape)}, {tuple(theta.shape)}, {tuple(obs_values.shape)}, {tuple(obs_rows.shape)}")
+    M, S = x0.shape
+    K, O = obs_values.shape
+    N = int(n_particles)
+    if obs_matrix is not None and tuple(obs_matrix.shape) != (O, S):
+        raise ValueError(f"tau_leap_particle_filter: obs_matrix must be [{O}, {S}], got {tuple(obs_matrix.shape)}")
+    with torch.cuda.device(dev):
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        loglik, incr, ess = torch.empty(M, **f32), torch.empty(M, K, **f32), torch.empty(M, K, **f32)
+        mean, std = torch.empty(M, K, S, **f32), torch.empty(M, K, S, **f32)
+        stopped, capped = torch.empty(M, K, **i32), torch.empty(M, K, **i32)
+        keep = return_particles and 0 < N <= PF_MAX_PARTICLES   # a bad N is the entry point's to refuse: allocate nothing for it
+        particles = torch.empty(M, K, N, S, **i32) if keep else None
+        ancestors = torch.empty(M, K, N, **i32) if keep else None
+        log_weights = torch.empty(M, K, N, **f32) if keep else None
+        if store is not None:
+            particles, ancestors = store
+            for t, shape in ((particles, (M, K, N, S)), (ancestors, (M, K, N))):
+                if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int32 or not t.is_contiguous() \
+                        or tuple(t.shape) != shape:
+                    raise ValueError(f"tau_leap_particle_filter: store must be contiguous int32 device tensors [{M}, {K}, {N}, {S}] "
+                                     f"and [{M}, {K}, {N}]")
+        prefix, term = _observation_term(variance, K, dev)
+        if prefix:      # (lik_kind, scale, dispersion, row_const) -> lik_kind, variance, scale, dispersion, row_const
+            term = (term[0], ctypes.c_double(1.0)) + term[1:]
+        else:
+            term = (ctypes.c_int(0),) + term + (ctypes.c_double(1.0), ctypes.c_double(1.0), _ptr(None))
+        _call(*_sde_entry(lib, "tau_leap_particle_filter", "reaction_network", network), ctypes.c_int(M), ctypes.c_int(N),
+              ctypes.c_int(S), ctypes.c_int(theta.shape[1]), ctypes.c_int(K), ctypes.c_int(O), _ptr(x0), _ptr(theta), _ptr(obs_rows),
+              _ptr(obs_values), _ptr(obs_matrix), *term, _ptr(key), ctypes.c_double(time_step), _ptr(loglik), _ptr(incr), _ptr(ess),
+              _ptr(mean), _ptr(std), _ptr(stopped), _ptr(capped), _ptr(particles), _ptr(ancestors), _ptr(log_weights), _stream(dev))
+    return loglik, incr, ess, mean, std, stopped, capped, particles, ancestors, log_weights
 
 
 def _jump_replay_inputs(who: str, x0, theta, obs_times, path_times, q_begin, max_events):

@@ -98,7 +98,14 @@ The torch loop calls ``jump_particle_filter(..., return_particles=True)`` and re
 ``core.jump_process.jump_segment_states``.  The kernel loop hands the step kernel the int32 store and the anchor buffers as raw
 32-bit words under an fp32 view: its record half only copies words (the NaN it writes into a dead record's anchors is never read),
 so csrc/vsde_mcmc.hip serves unchanged, and ONE launch after the loop (csrc/vsde_jump_replay.hip) makes the paths.  The theta chain
-is the same bit for bit with and without paths."""
+is the same bit for bit with and without paths.
+
+``dynamics="tau_leap"`` (a ``ReactionNetworkSDE``).  Again ONE thing is replaced: the estimator of step 2 is
+``tau_leap_particle_filter`` (inference/tau_leap_filter.py) with the step ``time_step``, under the same per-iteration key: the chains
+sample the theta posterior of the tau-leap model, at a cost per iteration that does not grow with the population.  ``proposal`` must
+be ``"bootstrap"`` and the start state must hold integers; ``positive_dims`` is not used.  There is no tau-leap replay:
+``return_paths=True`` and ``path_times`` raise.  Both loops take it: the torch loop through its estimator slot, the kernel loop by
+launching the tau-leap filter's kernel (csrc/vsde_tau_leap.hip) where it launches the SDE filter's; the step kernel is untouched."""
 from __future__ import annotations
 
 import math
@@ -118,7 +125,8 @@ HIP_MCMC = True   # set False to force the torch step (A/B tests); the filter ke
 DEFAULT_TARGET_ACCEPT = 0.15
 COVARIANCE_JITTER = 1e-8
 DEFAULT_SCALE_FLOOR = 1e-3
-DYNAMICS = ("diffusion", "jump")   # what the filter propagates: the Euler-Maruyama SDE, or the exact jump process of a reaction network
+# what the filter propagates: the Euler-Maruyama SDE, the exact jump process of a reaction network, or its tau-leap
+DYNAMICS = ("diffusion", "jump", "tau_leap")
 DEAD_PATH = 0xFFFFFFFF   # noise_path of a record without a path
 _ITERATION_HOOK = None   # measurement aid (tools/particle_mcmc_bench.py): called with i at the top of every iteration of either loop
 
@@ -327,11 +335,16 @@ def _validate(sde, observations, observation_likelihood, initial_theta, time_ste
         raise ValueError(f"dynamics must be one of {DYNAMICS}, got {dynamics!r}")
     if dynamics == "jump" and proposal != "bootstrap":
         raise ValueError(f"dynamics='jump' runs the bootstrap filter on the jump process: proposal must be 'bootstrap', got {proposal!r}")
+    if dynamics == "tau_leap" and proposal != "bootstrap":
+        raise ValueError(f"dynamics='tau_leap' runs the bootstrap filter on the tau-leap: proposal must be 'bootstrap', got {proposal!r}")
+    if dynamics == "tau_leap" and return_paths:
+        raise ValueError("return_paths=True with dynamics='tau_leap': there is no tau-leap replay to make the paths with")
     if dynamics == "jump" and return_paths and path_times is None:
         raise ValueError("return_paths=True with dynamics='jump': a jump process has no grid, path_times (the instants to read the "
                          "paths at) is required")
     if path_times is not None and dynamics != "jump":
-        raise ValueError("path_times is for dynamics='jump': the paths of dynamics='diffusion' live on the grid of time_step")
+        raise ValueError("path_times is for dynamics='jump': the paths of dynamics='diffusion' live on the grid of time_step, and "
+                         "dynamics='tau_leap' returns no paths")
     if path_thin < 1:
         raise ValueError(f"path_thin must be >= 1, got {path_thin}")
     if return_paths and estimator is not None:
@@ -357,6 +370,9 @@ def _validate(sde, observations, observation_likelihood, initial_theta, time_ste
     if dynamics == "jump":
         from . import jump_filter as _jf
         rows, x0, _ = _jf._validate(sde, observations, rows, n_particles, x0, max_events)
+    elif dynamics == "tau_leap":
+        from . import tau_leap_filter as _tlf
+        rows, x0, _ = _tlf._validate(sde, observations, rows, time_step, n_particles, x0)
     else:
         rows, x0 = _pf._validate(sde, observations, rows, time_step, n_particles, x0)
     C, P = initial_theta.shape
@@ -404,12 +420,18 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
     must hold integers in ``0 .. 2^30`` (default: the first observation, if it does).  A jump process has no grid, so
     ``return_paths=True`` needs ``path_times`` (float64 ``[Q]``, ``Q >= 1``, finite, non-decreasing, inside ``[0, T_{K-1}]``; without
     it ``ValueError``): ``paths`` is then int32 ``[n_path, C, Q, S]``, the state after every event with time ``<= t_q``, -1 for a
-    dead record, and the result's ``path_times`` holds the instants.  ``path_times`` with ``dynamics="diffusion"`` raises."""
+    dead record, and the result's ``path_times`` holds the instants.  ``path_times`` with ``dynamics="diffusion"`` raises.
+
+    ``dynamics="tau_leap"`` (``sde`` must be a ``ReactionNetworkSDE``): the estimator of every iteration is
+    ``tau_leap_particle_filter`` under ``filter_key(i, key)`` with the step ``time_step``: the chains target the theta posterior of
+    the tau-leap model (``core/tau_leap.py``), which keeps the integers and the extinctions of the jump process at a cost that does
+    not grow with the population.  ``proposal`` must be ``"bootstrap"``, ``initial_state`` must hold integers in ``0 .. 2^30``
+    (default: the first observation, if it does), ``positive_dims`` is ignored; ``return_paths=True`` and ``path_times`` raise."""
     theta0, x0, mask, pos_theta = _validate(sde, observations, observation_likelihood, initial_theta, time_step, n_iterations, warmup,
                                             n_particles, filters_per_chain, thin, theta_positive_dims, initial_state, proposal,
                                             proposal_scale_tril, step_size, target_accept, adapt_interval, return_paths, path_thin,
                                             _estimator, dynamics, max_events, path_times)
-    jump, estimator_given = dynamics == "jump", _estimator is not None
+    jump, tau_leap, estimator_given = dynamics == "jump", dynamics == "tau_leap", _estimator is not None
     jump_paths = None
     if jump and return_paths:
         from . import jump_smoother as _js
@@ -433,16 +455,24 @@ def particle_mcmc(sde: SDE, observations: Observations, observation_likelihood: 
             from .jump_filter import jump_particle_filter
             _estimator = lambda rows, i, fkey: jump_particle_filter(sde, obs, observation_likelihood, rows, n_particles=int(n_particles),
                                                                     initial_state=x0, key=fkey, max_events=int(max_events)).log_likelihood
+        if tau_leap and not estimator_given:
+            from .tau_leap_filter import tau_leap_particle_filter
+            _estimator = lambda rows, i, fkey: tau_leap_particle_filter(sde, obs, observation_likelihood, rows, float(time_step),
+                                                                        n_particles=int(n_particles), initial_state=x0, key=fkey).log_likelihood
         run = dict(sde=sde, obs=obs, like=observation_likelihood, prior=prior, dt=0.0 if jump else float(time_step), u0=u0, x0=x0, mask=mask,
-                   pos_theta=pos_theta, pos_state=() if jump else tuple(positive_dims), n_iterations=int(n_iterations), warmup=int(warmup),
+                   pos_theta=pos_theta, pos_state=() if jump or tau_leap else tuple(positive_dims), n_iterations=int(n_iterations), warmup=int(warmup),
                    N=int(n_particles), R=R, thin=int(thin), proposal=proposal, L=L,
                    step=float(step_size) if step_size is not None else 2.38 / math.sqrt(P), adapt=bool(adapt) and C > P,
                    target_accept=float(target_accept), interval=int(adapt_interval), key=key, estimator=_estimator, trace=_trace,
-                   path_thin=int(path_thin) if return_paths else 0, jump_paths=jump_paths, max_events=int(max_events) if jump else 0)
+                   path_thin=int(path_thin) if return_paths else 0, jump_paths=jump_paths, max_events=int(max_events) if jump else 0, tau_leap=tau_leap)
         route = None
         if HIP_MCMC and not estimator_given and theta0.is_cuda and dtype == torch.float32 and type(prior) is Prior and prior.dim == P:
             from .. import _hip
-            if P <= _hip.PMMH_MAX_PARAMS and not jump:
+            if P <= _hip.PMMH_MAX_PARAMS and tau_leap:
+                from . import tau_leap_filter as _tlf
+                if _tlf._kernel_route(sde, obs, observation_likelihood, theta0.repeat_interleave(R, dim=0), int(n_particles)):
+                    route = ("reaction_network", sde.kernel_descriptor())
+            elif P <= _hip.PMMH_MAX_PARAMS and not jump:
                 route = _pf._kernel_route(sde, obs, observation_likelihood, theta0.repeat_interleave(R, dim=0), int(n_particles), proposal)
             elif P <= _hip.PMMH_MAX_PARAMS:
                 from . import jump_filter as _jf
@@ -458,7 +488,7 @@ def _adaptation(i, warmup, interval, adapt):
 
 
 def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n_iterations, warmup, N, R, thin, proposal, L, step,
-                adapt, target_accept, interval, key, estimator, trace, path_thin=0, jump_paths=None, max_events=0):
+                adapt, target_accept, interval, key, estimator, trace, path_thin=0, jump_paths=None, max_events=0, tau_leap=False):
     dev, dtype = u0.device, u0.dtype
     C, P = u0.shape
     cur_u = u0.clone()
@@ -558,13 +588,15 @@ def _torch_loop(sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n
 
 
 def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_state, n_iterations, warmup, N, R, thin, proposal, L,
-                 step, adapt, target_accept, interval, key, estimator, trace, path_thin=0, jump_paths=None, max_events=0):
+                 step, adapt, target_accept, interval, key, estimator, trace, path_thin=0, jump_paths=None, max_events=0,
+                 tau_leap=False):
     """The loop with the step kernel: launch i closes iteration i - 1 and opens iteration i, the filter launch follows.  When the
     step size or L changes before iteration i (warm-up only) the proposal is opened again with the new values: the open half is a
     pure function of (state, i, key, step size, L).  With paths the filter stores particles and ancestors into two buffers
     allocated here, launch i draws the records of the chains it accepts from them (the filter launch of iteration i overwrites
     them only afterwards), and one replay launch after the loop turns the kept records into paths.  ``max_events > 0`` (``dynamics="jump"``): the filter
-    launch is the jump-process filter's (csrc/vsde_jump_filter.hip); everything else is the same loop."""
+    launch is the jump-process filter's (csrc/vsde_jump_filter.hip); ``tau_leap`` (``dynamics="tau_leap"``): it is the tau-leap filter's
+    (csrc/vsde_tau_leap.hip) on the grid of ``dt``; everything else is the same loop."""
     from .. import _hip
     kind, network = route
     dev = u0.device
@@ -581,7 +613,15 @@ def _kernel_loop(route, sde, obs, like, prior, dt, u0, x0, mask, pos_theta, pos_
     history = torch.empty(max(w2 - w4, 0), C, P, **f32) if adapt else None
     L_host = L.detach().float().cpu().contiguous()
     prior_args = (1 if prior.type == PriorType.LOG_NORMAL else 0, float(prior.mean), float(prior.std), pos_theta)
-    if max_events:
+    if tau_leap:
+        from ..core.tau_leap import grid_rows
+        from . import jump_filter as _jf
+        model = _jf._launch_model(obs, like, u0)                           # formed once for every launch of the loop
+        leap_rows = grid_rows(obs.times, dt, "observation times").to(device=dev, dtype=torch.int32)
+        x0 = x0.to(torch.int32).contiguous()
+        filter_launch = lambda: _hip.tau_leap_particle_filter(x0, kernel_theta(network, theta_prop), leap_rows, *model, fkey, dt, N,
+                                                              network=network)
+    elif max_events:
         from . import jump_filter as _jf
         times, model = obs.times.to(torch.float64), _jf._launch_model(obs, like, u0)   # formed once for every launch of the loop
         x0 = x0.to(torch.int32).contiguous()

@@ -443,7 +443,8 @@ class VariationalPosterior:
         ``"residual_bridge"`` (the same step around the noise-free Euler path of the segment) is the one to try.
         ``dynamics="jump"`` (a ``ReactionNetworkSDE``): ``log p(y | theta)`` is that of the exact jump process instead
         (``jump_particle_filter`` with ``max_events`` events per particle and segment; ``proposal`` must be ``"bootstrap"``); the
-        start state is the first observation, which must hold integers."""
+        start state is the first observation, which must hold integers.  ``dynamics="tau_leap"``: that of the tau-leap of the jump
+        process on this posterior's grid (``tau_leap_particle_filter``), with the same conditions."""
         from ..inference import jump_filter as _jf
         from ..inference import particle_filter as _pf
         from ..inference.particle_mcmc import DYNAMICS
@@ -451,8 +452,8 @@ class VariationalPosterior:
             raise ValueError(f"proposal must be one of {_pf.PROPOSALS}, got {proposal!r}")
         if dynamics not in DYNAMICS:
             raise ValueError(f"dynamics must be one of {DYNAMICS}, got {dynamics!r}")
-        if dynamics == "jump" and proposal != "bootstrap":
-            raise ValueError(f"dynamics='jump' runs the bootstrap filter on the jump process: proposal must be 'bootstrap', got {proposal!r}")
+        if dynamics != "diffusion" and proposal != "bootstrap":
+            raise ValueError(f"dynamics={dynamics!r} runs the bootstrap filter on the jump process: proposal must be 'bootstrap', got {proposal!r}")
         if n_samples < 1 or chunk_size < 1 or n_particles < 1:
             raise ValueError(f"n_samples, n_particles and chunk_size must be >= 1 (got {n_samples}, {n_particles}, {chunk_size})")
         q = self.model.sde_parameter_posterior
@@ -473,6 +474,10 @@ class VariationalPosterior:
             if dynamics == "jump":
                 res = _jf.jump_particle_filter(sde, self.observations, observation_likelihood, theta[lo:lo + chunk_size],
                                                n_particles=n_particles, initial_state=x0, max_events=max_events)
+            elif dynamics == "tau_leap":
+                from ..inference.tau_leap_filter import tau_leap_particle_filter
+                res = tau_leap_particle_filter(sde, self.observations, observation_likelihood, theta[lo:lo + chunk_size], self.time_step,
+                                               n_particles=n_particles, initial_state=x0)
             else:
                 res = _pf.particle_filter(sde, self.observations, observation_likelihood, theta[lo:lo + chunk_size], self.time_step,
                                           n_particles=n_particles, initial_state=x0, positive_dims=self.state_space.positive_dims,
@@ -585,7 +590,9 @@ class VariationalPosterior:
         (``particle_mcmc(..., dynamics="jump", max_events=...)``): the start state is the first observation, which must hold
         integers and ``proposal`` must be ``"bootstrap"``.  A jump process has no grid: with ``return_paths=True`` it needs
         ``path_times`` (float64 ``[Q]``, non-decreasing, inside ``[0, T_{K-1}]``), the instants the integer paths ``[n_path, C, Q, S]``
-        are read at."""
+        are read at.  ``dynamics="tau_leap"`` (a ``ReactionNetworkSDE``): the chains target the theta posterior of the tau-leap of the
+        jump process on this posterior's grid (``particle_mcmc(..., dynamics="tau_leap")``), with the same start state and
+        ``proposal``; ``return_paths=True`` and ``path_times`` raise."""
         import dataclasses
         from ..inference import particle_mcmc as _mc
         if n_chains < 1:
